@@ -13,11 +13,18 @@ its own pair; no data-path collective (stereo pairs are independent, SURVEY.md Â
 
 --mode train (BASELINE.json configs[2]): batch = 4 pairs x 4096 rays x 64 samples per GPU; a step is get_z + render +
 L1 loss + backward + fused finite guard + clip + bucketed RCCL gradient all-reduce + Adam (coponerf_amd/train_step.py,
-mirroring /root/reference wrapper.py:104-151, train.py:58-60,141-147).  The default render run appends a short
+mirroring the upstream reference's wrapper.py:104-151, train.py:58-60,141-147).  A render run with --full appends a short
 training measurement as the secondary `train` block, so the all-reduce is exercised at every N the driver runs.
 
-Prints ONE JSON line on rank 0 (driver contract) with `roofline` (dominant kernel, timed with HIP events on the launch
-stream inside the timed region) and `cpu_baseline` (the CPU oracle on a bounded sample of the same workload).
+Prints ONE JSON line on rank 0 (driver contract).  A plain run sets up, warms up, times the --steps steps and prints the
+headline figures (`value`, `ms_per_step`, ...).  Everything else runs with --full only: the secondary loops (two streams, a new
+pair every step, the f32 mode, the image pipeline, the callers' 18-call loop, the `train` block), `roofline` (dominant
+kernel, timed with HIP events on the launch stream inside the timed region) and `cpu_baseline` (the CPU oracle on a bounded
+sample of the same workload); in train mode the extra pass without the exchange at N > 1.
+
+--dump-outputs DIR writes what the last timed step returned to its caller (rank 0) as DIR/<name>.npy, float32 (float64 for
+64-bit inputs), at most 64 MB in all: an array larger than its share is replaced by a fixed, seeded sample of its elements.
+The inputs are seeded, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import hashlib
@@ -34,6 +41,7 @@ sys.path.insert(0, ROOT)
 
 F16_MFMA_PEAK_TFLOPS = 2500.0          # MI355X dense fp16/bf16 MFMA (MI355X_MICROARCH.md)
 HBM_PEAK_GBS = 8000.0                  # MI355X HBM3E spec peak (MI355X_MICROARCH.md)
+DUMP_BUDGET_BYTES = 60 * 2 ** 20       # --dump-outputs: all arrays together (files < 64 MB)
 
 
 def f_ray(S: int) -> float:
@@ -75,7 +83,12 @@ def parse_args(argv=None):
                     help="camera rig of the synthetic pairs: RealEstate10K-like (configs[1]) or ACID-like wide baseline "
                          "(configs[3])")
     ap.add_argument("--train-steps", type=int, default=6,
-                    help="steps of the secondary training measurement in render mode (0 = skip)")
+                    help="steps of the secondary training measurement in render mode with --full (0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the secondary measurements (other loops, f32 mode, image pipeline, callers' loop, train "
+                         "block, roofline, CPU baseline); a plain run times the headline loop only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as DIR/<name>.npy (float32 / float64, <= 64 MB in all)")
     return ap.parse_args(argv)
 
 
@@ -96,6 +109,53 @@ def _max_over_ranks(x: float, dev, distributed: bool) -> float:
     return float(t.item())
 
 
+def _named_tensors(obj, prefix, skip):
+    """(name, tensor) for every tensor in a nest of dicts / lists / tuples, each object once, none whose id is in `skip`; a
+    dict's own tensors come before those in its containers (out["at_wt"], not out["at_wts"][0])."""
+    if torch.is_tensor(obj):
+        if id(obj) not in skip:
+            skip.add(id(obj))
+            yield prefix, obj
+    elif isinstance(obj, dict):
+        for k, v in sorted(obj.items(), key=lambda kv: not torch.is_tensor(kv[1])):
+            yield from _named_tensors(v, f"{prefix}.{k}" if prefix else str(k), skip)
+    elif isinstance(obj, (list, tuple)):
+        for i, v in enumerate(obj):
+            yield from _named_tensors(v, f"{prefix}.{i}" if prefix else str(i), skip)
+
+
+def dump_outputs(arrays, out_dir, budget=DUMP_BUDGET_BYTES, seed=0):
+    """Write `arrays` ((name, tensor) pairs) as out_dir/<name>.npy: float64 for 64-bit and int32 inputs, float32 otherwise.
+    The budget is shared out smallest array first; an array larger than its share is written as a sample of its flattened
+    elements at sorted indices drawn by a generator seeded with `seed` (the same for every run of the same shapes).
+    Returns name -> "full" or "sample k of n"."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    items = []
+    for name, t in arrays:
+        dt = torch.float64 if t.dtype in (torch.float64, torch.int64, torch.int32) else torch.float32
+        items.append((name, t, dt, t.numel(), torch.tensor([], dtype=dt).element_size()))
+    take, left = {}, budget
+    order = sorted(range(len(items)), key=lambda i: items[i][3] * items[i][4])
+    for k, i in enumerate(order):
+        n, size = items[i][3], items[i][4]
+        take[i] = min(n, (left // (len(order) - k)) // size)
+        left -= take[i] * size
+    written = {}
+    for i, (name, t, dt, n, _) in enumerate(items):
+        flat = t.detach().reshape(-1)
+        if take[i] < n:
+            g = torch.Generator().manual_seed(seed)
+            idx = torch.randperm(n, generator=g)[:take[i]].sort().values
+            arr = flat.index_select(0, idx.to(flat.device)).to(dt).cpu().numpy()
+            written[name] = f"sample {take[i]} of {n}"
+        else:
+            arr = t.detach().to(dt).cpu().numpy()
+            written[name] = "full"
+        np.save(os.path.join(out_dir, f"{name}.npy"), arr)
+    return written
+
+
 def _fence(distributed: bool):
     torch.cuda.synchronize()
     if distributed:
@@ -105,8 +165,10 @@ def _fence(distributed: bool):
 
 
 # --------------------------------------------------------------------------------------------------------------
-def measure_train(args, dev, rank, world, steps, warmup):
-    """configs[2] on this rank's GPU: returns the dict of the training measurement (all ranks must call it)."""
+def measure_train(args, dev, rank, world, steps, warmup, full=True, dump_dir=None):
+    """configs[2] on this rank's GPU: returns the dict of the training measurement (all ranks must call it).  full=False
+    leaves out the extra pass without the exchange at N > 1; dump_dir: rank 0 writes what the last timed step returned and
+    the parameters it left (dump_outputs)."""
     from coponerf_amd import CoPoNeRF, dist as cdist, synthetic as syn
     from coponerf_amd.train_step import TrainStep
     distributed = world > 1
@@ -137,6 +199,11 @@ def measure_train(args, dev, rank, world, steps, warmup):
         info = step(inp, gt)
     _fence(distributed)
     elapsed = _max_over_ranks(time.perf_counter() - t0, dev, distributed)
+    if dump_dir is not None and rank == 0:
+        out = {k: info[k] for k in ("loss", "at_wt", "ray_order")}
+        out["param"] = dict(model.named_parameters())
+        dumped = dump_outputs(list(_named_tensors(out, "", set())), dump_dir)
+        print(f"bench.py: wrote {len(dumped)} arrays to {dump_dir}", file=sys.stderr)
     phases = step.timing_summary()
     rays = B * R * world * steps / elapsed
     # what the communicator itself reports (not the WORLD_SIZE this process was given): ranks, backend, the device every rank
@@ -157,7 +224,7 @@ def measure_train(args, dev, rank, world, steps, warmup):
     # what a 1-GPU run does); ms_per_step(1 rank's work) / ms_per_step(N ranks exchanging).  The replicas diverge here, so
     # this runs last.
     local_ms = None
-    if distributed:
+    if distributed and full:
         solo = TrainStep(model, exchange=False)
         for _ in range(2):
             solo(inp, gt)
@@ -213,7 +280,7 @@ def run(args):
         dist.init_process_group("nccl", device_id=dev)          # "nccl" on PyTorch-ROCm is RCCL
 
     if args.mode == "train":
-        tr = measure_train(args, dev, rank, world, args.steps, args.warmup)
+        tr = measure_train(args, dev, rank, world, args.steps, args.warmup, full=args.full, dump_dir=args.dump_outputs)
         if rank == 0:
             line = {
                 "metric": "training rays/sec (RealEstate10K-shaped 256x256 pairs, 4096 rays/pair, 64 samples/ray, "
@@ -260,12 +327,14 @@ def run(args):
     R = inp["query"]["uv"].shape[2]
     rays_per_step = B * R
 
-    def step():
+    def step(sink=None):
         with torch.no_grad():
             out0 = None
             for job in jobs:
                 o = model(job[4], z=job[5], rel_pose=job[6], val=True, flow=job[7])
                 out0 = o if out0 is None else out0
+                if sink is not None:
+                    sink.append(o)
             return out0
 
     # the headline loop runs every call on ONE stream (call_lanes = 1): with consecutive forward() calls alternating over
@@ -273,24 +342,34 @@ def run(args):
     # per-kernel HIP-event timings behind `roofline` would include the other stream's kernels
     lanes_default = model._engine.call_lanes
     model._engine.call_lanes = 1
-    # the warm-up steps run with the per-kernel event timing of the timed region switched on as well (first-time creation of the
-    # timing events then happens here); their readings are dropped.  (What made --warmup 1 read 8 % slower than --warmup 2 was
-    # the SECOND pinned pixel_val buffer, pinned inside the second call: RenderEngine._start_host_copy now parks it with the first)
-    model._engine.profile = {}
+    # with --full the warm-up steps run with the per-kernel event timing of the timed region (behind `roofline`) switched on as
+    # well (first-time creation of the timing events then happens here); their readings are dropped.  A plain run times no
+    # kernel.  (What made --warmup 1 read 8 % slower than --warmup 2 was the SECOND pinned pixel_val buffer, pinned inside the
+    # second call: RenderEngine._start_host_copy now parks it with the first)
+    model._engine.profile = {} if args.full else None
     for _ in range(args.warmup):
         out = step()
     _fence(distributed)
-    model._engine.profile = {}
+    model._engine.profile = {} if args.full else None
+    last = []                                               # every call's output of the last timed step
     t0 = time.perf_counter()
-    for _ in range(args.steps):
-        out = step()
+    for i in range(args.steps):
+        out = step(last if i == args.steps - 1 else None)
     _fence(distributed)
     elapsed = time.perf_counter() - t0
     prof, model._engine.profile = model._engine.profile, None
     elapsed = _max_over_ranks(elapsed, dev, distributed)
+    if args.dump_outputs is not None and rank == 0:
+        # what the callers receive, less the inputs handed back unchanged (z, flow, uv, rel_pose)
+        given = {id(t) for job in jobs for _, t in _named_tensors(job[4:], "", set())}
+        named = [nt for j, o in enumerate(last) for nt in _named_tensors(o, f"call{j}" if len(last) > 1 else "", given)]
+        dumped = dump_outputs(named, args.dump_outputs)
+        print(f"bench.py: wrote {len(dumped)} arrays to {args.dump_outputs}: "
+              + ", ".join(f"{k} ({v})" for k, v in dumped.items()), file=sys.stderr)
+    del last
     model._engine.call_lanes = lanes_default
     overlapped = None
-    if lanes_default > 1 and not args.pair_by_pair and not args.no_two_stream_pass:
+    if args.full and lanes_default > 1 and not args.pair_by_pair and not args.no_two_stream_pass:
         for _ in range(2):
             step()
         _fence(distributed)
@@ -304,7 +383,7 @@ def run(args):
     #      copies of the latent maps, the node tables (node features + a 97 GFLOP projection GEMM per pair), the camera
     #      block upload, the flow products â€” is rebuilt inside the timed region (four pairs in turn; the caches hold one)
     fresh = announced = None
-    if not args.pair_by_pair and B == 1 and not args.no_fresh_pair:
+    if args.full and not args.pair_by_pair and B == 1 and not args.no_fresh_pair:
         fjobs = []
         for j in range(4):
             ic = syn.make_inputs(1, H, H, 0, seed=500 + rank + 1000 * j, full_image=True, rig=args.rig)
@@ -348,7 +427,7 @@ def run(args):
     #      (hi, lo) pairs with exact products, exact-fp32 small layers (csrc/encode_f32.hip) - the same-precision number beside
     #      the headline, how far the fp16-operand image is from it, and its roofline view.  One untimed + three timed steps.
     f32 = None
-    if B == 1 and not args.pair_by_pair and not args.no_f32 and world == 1:
+    if args.full and B == 1 and not args.pair_by_pair and not args.no_f32 and world == 1:
         eng = model._engine
         rgb16 = out["rgb"].clone()
         eng.precision = "f32"
@@ -407,22 +486,25 @@ def run(args):
                                f"render path only (z/rel_pose/flow given, val=True)",
                    "chunk_rays": args.chunk_rays or model._engine._auto_chunk(S, dev), "lanes": args.lanes, "pairs_per_gpu": B,
                    "first_layer": "projected tables + K=80 MFMA + folded key_map layer on the register-resident slices (cpn_encode_key)"},
-        "rays_per_s_calls_on_two_streams": None if overlapped is None else rays_per_step * world * args.steps / overlapped,
-        # a new pair every step (tables, NHWC copies, camera upload and flow products rebuilt inside the timed region)
-        "rays_per_s_fresh_pair": None if fresh is None else rays_per_step * world * args.steps / fresh,
-        "ms_per_step_fresh_pair": None if fresh is None else 1e3 * fresh / args.steps,
-        "rays_per_s_fresh_pair_announced": None if announced is None else rays_per_step * world * args.steps / announced,
-        "ms_per_step_fresh_pair_announced": None if announced is None else 1e3 * announced / args.steps,
-        # the reference's arithmetic (fp32 operands, layer by layer) on the same workload, and the image's distance from it
-        "rays_per_s_f32": None if f32 is None else f32["rays_per_s_f32"],
-        "rgb_max_abs_f16_vs_f32": None if f32 is None else f32["rgb_max_abs_f16_vs_f32"],
-        "f32_mode": None if f32 is None else {k: f32[k] for k in ("form", "seconds_per_step", "executed_tflops", "roofline")},
         "path_tflops": value * f_ray(S) / 1e12,          # algorithmic FLOPs of the reference formulation
         "executed_tflops": value * exec_per_ray / 1e12,  # what the kernels execute after the restructurings
     }
+    if args.full:
+        line.update({
+            "rays_per_s_calls_on_two_streams": None if overlapped is None else rays_per_step * world * args.steps / overlapped,
+            # a new pair every step (tables, NHWC copies, camera upload and flow products rebuilt inside the timed region)
+            "rays_per_s_fresh_pair": None if fresh is None else rays_per_step * world * args.steps / fresh,
+            "ms_per_step_fresh_pair": None if fresh is None else 1e3 * fresh / args.steps,
+            "rays_per_s_fresh_pair_announced": None if announced is None else rays_per_step * world * args.steps / announced,
+            "ms_per_step_fresh_pair_announced": None if announced is None else 1e3 * announced / args.steps,
+            # the reference's arithmetic (fp32 operands, layer by layer) on the same workload, and the image's distance from it
+            "rays_per_s_f32": None if f32 is None else f32["rays_per_s_f32"],
+            "rgb_max_abs_f16_vs_f32": None if f32 is None else f32["rgb_max_abs_f16_vs_f32"],
+            "f32_mode": None if f32 is None else {k: f32[k] for k in ("form", "seconds_per_step", "executed_tflops", "roofline")},
+        })
 
     # ---- secondary figure: the whole image pipeline (get_z once per pair + the render pass), SURVEY.md Â§8(d)
-    if H == 256 and not args.no_image:
+    if args.full and H == 256 and not args.no_image:
         with torch.no_grad():
             for _ in range(5):                               # (the library picks its convolution kernels on first use)
                 zz = model.get_z(inp)
@@ -513,16 +595,16 @@ def run(args):
 
     # ---- secondary figure: the loop the reference's callers run (test.py:164-212): get_z once, then 18 forward() calls
     #      on torch.chunk(uv, 18) with the callers' del / .cpu() / per-key concat, at batch 1 and batch 2 (test.py:130)
-    if H == 256 and not args.no_ref_loop and B == 1:
+    if args.full and H == 256 and not args.no_ref_loop and B == 1:
         line["ref_loop"] = ref_loop_block(model, syn, dev, rank, H, inp, z, rel, flow, elapsed / args.steps)
 
-    if rank == 0:
+    if rank == 0 and args.full:
         line.update(roofline_block(prof, args, tables))
         if args.cpu_rays > 0 and world == 1:          # CPU baseline: rank 0 at N = 1 only
             line.update(cpu_baseline_block(args, syn, inp_cpu, z_cpu, rel_cpu, flow_cpu, out, Bc, H, S))
 
     # ---- secondary: configs[2] training step on the same ranks (exercises the RCCL gradient all-reduce at N > 1)
-    if H == 256 and args.train_steps > 0:
+    if args.full and H == 256 and args.train_steps > 0:
         del out, model, z, flow
         torch.cuda.empty_cache()
         try:

@@ -35,3 +35,48 @@ def test_modes_parse():
     assert bench.parse_args([]).mode == "render"
     # round 5: the reference-arithmetic pass of the same step runs by default and can be switched off
     assert bench.parse_args([]).no_f32 is False and bench.parse_args(["--no-f32"]).no_f32 is True
+
+
+def test_full_and_dump_flags_parse():
+    sys.path.insert(0, ROOT)
+    import bench
+    a = bench.parse_args([])
+    assert a.full is False and a.dump_outputs is None
+    a = bench.parse_args(["--full", "--dump-outputs", "out"])
+    assert a.full is True and a.dump_outputs == "out"
+
+
+def test_dump_outputs_keeps_the_budget_and_samples_the_same_elements(tmp_path):
+    """--dump-outputs: float32 / float64 files, small arrays whole, the large one a seeded sample, the whole under budget,
+    the same elements in two runs."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    g = torch.Generator().manual_seed(3)
+    big = torch.randn(300_000, generator=g)
+    arrays = [("rgb", torch.rand(4, 3, generator=g)), ("big", big), ("idx", torch.arange(10, dtype=torch.int64)),
+              ("mask", torch.tensor([True, False])), ("half", torch.ones(5, dtype=torch.float16))]
+    budget = 2 ** 20
+    written = [bench.dump_outputs(arrays, str(tmp_path / d), budget=budget) for d in ("a", "b")]
+    assert written[0] == written[1] and written[0]["big"].startswith("sample ")
+    assert all(written[0][k] == "full" for k in ("rgb", "idx", "mask", "half"))
+    total = sum(os.path.getsize(tmp_path / "a" / f"{k}.npy") for k in written[0])
+    assert total <= budget + 128 * len(arrays)                         # + the .npy headers
+    load = lambda d, k: np.load(tmp_path / d / f"{k}.npy")
+    assert load("a", "idx").dtype == np.float64 and load("a", "idx").tolist() == list(range(10))
+    assert load("a", "mask").dtype == np.float32 and load("a", "mask").tolist() == [1.0, 0.0]
+    assert load("a", "half").dtype == np.float32 and load("a", "rgb").shape == (4, 3)
+    s = load("a", "big")
+    assert s.dtype == np.float32 and 0 < s.size < big.numel() and np.array_equal(s, load("b", "big"))
+    assert np.isin(s, big.numpy()).all()
+
+
+def test_named_tensors_skips_inputs_and_repeats():
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    z, rgb = torch.zeros(2), torch.ones(3)
+    out = {"z": [z], "at_wts": [rgb], "rgb": rgb, "aux": {"depth": torch.ones(1)}, "n": 3}
+    names = [n for n, _ in bench._named_tensors(out, "", {id(z)})]
+    assert names == ["rgb", "aux.depth"]

@@ -10,6 +10,6 @@ python tools/trace_step.py "$T" project_rays 60 > "$OUT/train_step_kernels.txt" 
 rm -rf "$OUT/train_prof"
 head -1 $OUT/train_step_kernels.txt
 python tools/aten_time.py --top 120 > "$OUT/aten_train.txt" 2>&1
-python bench.py > $OUT/bench.json 2> $OUT/bench.err; python tools/show_rates.py $OUT/bench.json | head -3
+python bench.py --full > $OUT/bench.json 2> $OUT/bench.err; python tools/show_rates.py $OUT/bench.json | head -3
 python -c "
 import json; d=json.load(open('$OUT/bench.json')); print(d['train']['ms_per_step'], d['roofline']['frac'], d['get_z_ms'])"

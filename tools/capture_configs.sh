@@ -9,8 +9,8 @@ OUT=$ROOT/gpurun_out/$TAG
 mkdir -p "$OUT"
 export TMPDIR=/tmp PYTHONPATH=$ROOT
 cd "$ROOT"
-C4="--rig wide --train-steps 0 --no-image --no-ref-loop --no-f32"
-C5="--height 512 --samples 128 --pairs 8 --pair-by-pair --steps 2 --warmup 1 --train-steps 0 --no-image --no-ref-loop"
+C4="--full --rig wide --train-steps 0 --no-image --no-ref-loop --no-f32"
+C5="--full --height 512 --samples 128 --pairs 8 --pair-by-pair --steps 2 --warmup 1 --train-steps 0 --no-image --no-ref-loop"
 python bench.py $C4 --cpu-rays 4096 > "$OUT/c4_bench.json" 2> "$OUT/c4_bench.err"
 python bench.py $C5 --cpu-rays 1024 > "$OUT/c5_bench.json" 2> "$OUT/c5_bench.err"
 ( cd /tmp && rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/c4_prof" -o r -- python "$ROOT/bench.py" $C4 --cpu-rays 0 ) > "$OUT/c4_bench_under_rocprof.json" 2> "$OUT/c4_prof.log"

@@ -10,8 +10,8 @@ OUT=$ROOT/gpurun_out/$TAG
 mkdir -p "$OUT"
 export TMPDIR=/tmp PYTHONPATH=$ROOT
 cd "$ROOT"
-python bench.py > "$OUT/bench.json" 2> "$OUT/bench.err"
-( cd /tmp && rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/render_prof" -o r -- python "$ROOT/bench.py" --no-image --no-ref-loop --no-two-stream-pass --no-fresh-pair --no-f32 --cpu-rays 0 --train-steps 0 --steps 5 ) > "$OUT/bench_under_rocprof.json" 2> "$OUT/render_prof.log"
+python bench.py --full > "$OUT/bench.json" 2> "$OUT/bench.err"
+( cd /tmp && rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/render_prof" -o r -- python "$ROOT/bench.py" --full --no-image --no-ref-loop --no-two-stream-pass --no-fresh-pair --no-f32 --cpu-rays 0 --train-steps 0 --steps 5 ) > "$OUT/bench_under_rocprof.json" 2> "$OUT/render_prof.log"
 python tools/summarize_pmc.py "$(find "$OUT/render_prof" -name '*kernel_stats.csv' | head -1)" "$OUT/render_kernel_stats.summary.csv" 40
 # sidecar of the kernel statistics: which kernel source / launch shape they were taken on (bench.py roofline.rocprof)
 python - "$OUT" <<'PY'
@@ -20,11 +20,11 @@ root = os.environ.get("GRAFT_REPO_ROOT", os.getcwd())
 src = os.path.join(root, "coponerf_amd", "csrc", "encode_fused.hip")
 json.dump({"kernel": "encode_fused_kernel",
            "kernel_source_sha16": hashlib.sha256(open(src, "rb").read()).hexdigest()[:16], "rows_per_launch": 16777216,
-           "command": "python bench.py --no-image --no-ref-loop --no-two-stream-pass --no-fresh-pair --no-f32 --cpu-rays 0 --train-steps 0 --steps 5 (under rocprofv3 --kernel-trace --stats)"},
+           "command": "python bench.py --full --no-image --no-ref-loop --no-two-stream-pass --no-fresh-pair --no-f32 --cpu-rays 0 --train-steps 0 --steps 5 (under rocprofv3 --kernel-trace --stats)"},
           open(os.path.join(sys.argv[1], "render_kernel_stats.meta.json"), "w"), indent=1)
 PY
 # PMC passes (one counter group per run) of the dominant kernel on the headline command itself: 65 536-ray launches
-tools/pmc_passes.sh "$OUT/pmc_encode" encode_fused -- python "$ROOT/bench.py" --no-image --no-ref-loop --no-two-stream-pass --no-fresh-pair --no-f32 --cpu-rays 0 --train-steps 0 --steps 3 --warmup 1 > "$OUT/pmc_encode.log" 2>&1
+tools/pmc_passes.sh "$OUT/pmc_encode" encode_fused -- python "$ROOT/bench.py" --full --no-image --no-ref-loop --no-two-stream-pass --no-fresh-pair --no-f32 --cpu-rays 0 --train-steps 0 --steps 3 --warmup 1 > "$OUT/pmc_encode.log" 2>&1
 python tools/make_traffic_json.py "$OUT/pmc_encode/summary.json" 16777216 "$OUT/traffic.json" encode_key >> "$OUT/pmc_encode.log" 2>&1
 # the reference-arithmetic mode: per-kernel statistics of one image (one stream)
 ( cd /tmp && rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/f32_prof" -o f -- python "$ROOT/tools/f32_time.py" --steps 2 ) > "$OUT/f32_time.log" 2>&1

@@ -19,7 +19,7 @@ if [ "$1" = build ]; then
 else
   OUT=$2; mkdir -p "$OUT"; export PYTHONPATH=$ROOT TMPDIR=/tmp
   for rep in 1 2; do for A in 0 2048 4096 6144; do
-    COPONERF_HIP_LIB=$B/libcpn_ef_$A.so python $ROOT/bench.py --no-image --no-ref-loop --no-two-stream-pass --no-fresh-pair --no-f32 --cpu-rays 0 --train-steps 0 --steps 5 > "$OUT/ef_${A}_$rep.json" 2> "$OUT/ef_${A}_$rep.err"
+    COPONERF_HIP_LIB=$B/libcpn_ef_$A.so python $ROOT/bench.py --full --no-image --no-ref-loop --no-two-stream-pass --no-fresh-pair --no-f32 --cpu-rays 0 --train-steps 0 --steps 5 > "$OUT/ef_${A}_$rep.json" 2> "$OUT/ef_${A}_$rep.err"
     python - "$OUT/ef_${A}_$rep.json" $A <<'PY'
 import json, sys
 d = json.load(open(sys.argv[1]))
