@@ -390,7 +390,7 @@ __global__ __launch_bounds__(256) void attend_hidden_bwd_kernel(
 // hid feeds the key path (a GEMM, gradient dkey) and the two attention-weighted hidden sums (gradients w_i (x) dhbar_i,
 // rank one per ray).  Autograd used to materialise the three 7 GB tensors, add them twice and mask the sum (84 GB of
 // traffic per step at 4 x 4096 rays); this kernel reads hid and dkey once and writes the masked sum once (21 GB).
-// thread = (row, 8-channel chunk); all gradient operands carry the pass's power-of-two scale (train_fns.GradScale).
+// thread = (row, 8-channel chunk); all gradient operands carry the pass's power-of-two scale (train_fns.BackwardPass).
 __global__ __launch_bounds__(256) void hid_grad_combine_kernel(
     const __half* __restrict__ dkey, const __half* __restrict__ hid, const float* __restrict__ w1,
     const float* __restrict__ dh1, const float* __restrict__ w2, const float* __restrict__ dh2, int V, int R, int S,

@@ -63,28 +63,28 @@ class _TrunkBatchNorm(nn.BatchNorm2d):
                 torch._foreach_add_(pend, 1)
 
 
-# Training: data and weight gradient of the trunk's 3x3 / 1x1 convolutions with fp16 operands (fp32 accumulation in the
-# library's implicit-GEMM kernels), every layer's incoming gradient scaled by a power of two found on the device
-# (cpn_scale_to_f16).  The forward stays fp32.  tools/conv_bwd_precision_bench.py, 8 images of 256 x 256: 6.8 -> 4.6 ms for
-# the 36 layers including the casts; each layer's dx / dw within 8e-4 / 1.4e-3 (relative L2) of the fp32 kernels' — a
-# tenth of what the forward's fp16 operands already leave upstream of z (tests/test_gpu_step.py).  0 = the library's fp32 backward.
-F16_TRUNK_BACKWARD = os.environ.get("CPN_TRUNK_BWD_F16", "1") != "0"
+class TrunkBackward:
+    """Training: data and weight gradient of the trunk's 3x3 / 1x1 convolutions with fp16 operands (fp32 accumulation in the
+    library's implicit-GEMM kernels), every layer's incoming gradient scaled by a power of two found on the device
+    (cpn_scale_to_f16).  The forward stays fp32.  tools/conv_bwd_precision_bench.py, 8 images of 256 x 256: 6.8 -> 4.6 ms
+    for the 36 layers including the casts; each layer's dx / dw within 8e-4 / 1.4e-3 (relative L2) of the fp32 kernels' — a
+    tenth of what the forward's fp16 operands already leave upstream of z (tests/test_gpu_step.py).
 
+    One per SpatialEncoder, shared by its blocks.  enabled: this backward (CPN_TRUNK_BWD_F16=0: the library's fp32 one);
+    target: where each layer's largest |dy| lands, moved by `after_step`; trace: set to a list to collect (x shape,
+    max |dx16|, max |dw16|) per layer (device scalars, no sync)."""
 
-_TRUNK_BWD_TARGET = [4.0]
+    def __init__(self):
+        self.enabled = os.environ.get("CPN_TRUNK_BWD_F16", "1") != "0"
+        self.target = 4.0
+        self.trace = None
 
-
-def trunk_bwd_target_backoff(stepped: bool) -> None:
-    """Called with the outcome of every optimizer step (coponerf_amd.train_step): non-finite gradients quarter the target
-    of the trunk's fp16 backward (an overflowing dw / dx would otherwise repeat for ever), a finite step doubles it back
-    towards 4."""
-    t = _TRUNK_BWD_TARGET
-    # floor 2^-4: 64 x more room than the 146 x of target 4 — beyond that an overflow here is not what made the step
-    # non-finite, and a smaller target only pushes the small entries of dy into fp16's subnormals
-    t[0] = min(4.0, t[0] * 2.0) if stepped else max(2.0 ** -4, t[0] * 0.25)
-
-
-F16_BWD_TRACE = None          # set to a list to collect (x shape, max |dx16|, max |dw16|) per layer (device scalars, no sync)
+    def after_step(self, stepped: bool) -> None:
+        """Called with the outcome of every optimizer step (coponerf_amd.train_step): non-finite gradients quarter the target
+        (an overflowing dw / dx would otherwise repeat for ever), a finite step doubles it back towards 4."""
+        # floor 2^-4: 64 x more room than the 146 x of target 4 — beyond that an overflow here is not what made the step
+        # non-finite, and a smaller target only pushes the small entries of dy into fp16's subnormals
+        self.target = min(4.0, self.target * 2.0) if stepped else max(2.0 ** -4, self.target * 0.25)
 
 
 class _ScaleSlots:
@@ -101,12 +101,12 @@ class _ScaleSlots:
 
 
 class _ConvF16BwdFn(torch.autograd.Function):
-    """F.conv2d(x, w, None, stride, padding) whose backward runs on fp16 operands (see F16_TRUNK_BACKWARD)."""
+    """F.conv2d(x, w, None, stride, padding) whose backward runs on fp16 operands (see TrunkBackward)."""
 
     @staticmethod
-    def forward(ctx, x, w, stride, padding):
+    def forward(ctx, x, w, stride, padding, state: TrunkBackward):
         ctx.save_for_backward(x, w)
-        ctx.geo = (int(stride), int(padding))
+        ctx.geo, ctx.state = (int(stride), int(padding)), state
         return F.conv2d(x, w, None, stride, padding)
 
     @staticmethod
@@ -120,20 +120,20 @@ class _ConvF16BwdFn(torch.autograd.Function):
             dy = dy.contiguous()
         if dy.numel() % 4:                                     # cpn_scale_to_f16 works on 16-byte pieces
             return tuple(torch.ops.aten.convolution_backward(dy, x, w, None, [st, st], [pd, pd], [1, 1], False, [0, 0], 1,
-                                                             [ctx.needs_input_grad[0], ctx.needs_input_grad[1], False])[:2]) + (None, None)
+                                                             [ctx.needs_input_grad[0], ctx.needs_input_grad[1], False])[:2]) + (None,) * 3
         slot = _ScaleSlots.take(dy.device)
         dy16 = torch.empty_like(dy, dtype=torch.float16)       # keeps dy's layout
         # the largest |dy| lands in [target / 2, target]: dx and dw come back as fp16 tensors, and dw sums dy . x over up to
         # 131 072 positions per image batch — at target 64 its largest entry reached 7 160 of fp16's 65 504 on the synthetic
         # step (tools/trunk_bwd_headroom.py); at 4 there are two decades of room, and entries down to 1.5e-5 of the largest
-        # keep all their bits.  A skipped step backs the target off further (trunk_bwd_target_backoff, called by TrainStep).
-        call("cpn_scale_to_f16", dy.data_ptr(), dy.numel(), float(_TRUNK_BWD_TARGET[0]), slot.data_ptr(), dy16.data_ptr(),
+        # keep all their bits.  A skipped step backs the target off further (TrunkBackward.after_step, called by TrainStep).
+        call("cpn_scale_to_f16", dy.data_ptr(), dy.numel(), float(ctx.state.target), slot.data_ptr(), dy16.data_ptr(),
              slot[1:].data_ptr(), _stream_handle())
         need = [ctx.needs_input_grad[0], ctx.needs_input_grad[1], False]
         dx16, dw16, _ = torch.ops.aten.convolution_backward(dy16, x.half(), w.half(), None, [st, st], [pd, pd], [1, 1], False,
                                                             [0, 0], 1, need)
-        if F16_BWD_TRACE is not None:                          # tests / tools: the largest fp16 entries, still on the device
-            F16_BWD_TRACE.append((tuple(x.shape), dx16.abs().max() if need[0] else None, dw16.abs().max() if need[1] else None))
+        if ctx.state.trace is not None:                        # tests / tools: the largest fp16 entries, still on the device
+            ctx.state.trace.append((tuple(x.shape), dx16.abs().max() if need[0] else None, dw16.abs().max() if need[1] else None))
         inv = slot[2:3]                                        # 1-d fp32: the product is fp32
         dw = None
         if need[1]:
@@ -141,19 +141,20 @@ class _ConvF16BwdFn(torch.autograd.Function):
             # written contiguous, or the norm / clip / Adam passes over the gradients fall off their multi-tensor paths
             dw = torch.empty(w.shape, dtype=torch.float32, device=w.device)
             torch.mul(dw16, inv, out=dw)
-        return (dx16 * inv if need[0] else None), dw, None, None
+        return (dx16 * inv if need[0] else None), dw, None, None, None
 
 
-def _conv(conv: nn.Conv2d, x):
-    if (F16_TRUNK_BACKWARD and x.is_cuda and x.dtype == torch.float32 and torch.is_grad_enabled() and conv.bias is None
+def _conv(conv: nn.Conv2d, x, state: TrunkBackward):
+    if (state.enabled and x.is_cuda and x.dtype == torch.float32 and torch.is_grad_enabled() and conv.bias is None
             and x.numel() % 4 == 0 and (x.is_contiguous() or x.is_contiguous(memory_format=torch.channels_last))):
-        return _ConvF16BwdFn.apply(x, conv.weight, conv.stride[0], conv.padding[0])
+        return _ConvF16BwdFn.apply(x, conv.weight, conv.stride[0], conv.padding[0], state)
     return conv(x)
 
 
 class _BasicBlock(nn.Module):
-    def __init__(self, cin: int, cout: int, stride: int):
+    def __init__(self, cin: int, cout: int, stride: int, trunk_bwd: TrunkBackward):
         super().__init__()
+        self.trunk_bwd = trunk_bwd
         self.conv1 = nn.Conv2d(cin, cout, 3, stride, 1, bias=False)
         self.bn1 = _TrunkBatchNorm(cout)
         self.relu = nn.ReLU(inplace=True)
@@ -164,13 +165,14 @@ class _BasicBlock(nn.Module):
             self.downsample = nn.Sequential(nn.Conv2d(cin, cout, 1, stride, bias=False), _TrunkBatchNorm(cout))
 
     def forward(self, x):
-        idt = x if self.downsample is None else self.downsample[1](_conv(self.downsample[0], x))
-        out = self.bn2(_conv(self.conv2, self.relu(self.bn1(_conv(self.conv1, x)))))
+        st = self.trunk_bwd
+        idt = x if self.downsample is None else self.downsample[1](_conv(self.downsample[0], x, st))
+        out = self.bn2(_conv(self.conv2, self.relu(self.bn1(_conv(self.conv1, x, st))), st))
         return self.relu(out + idt)
 
 
 class _ResNet34Trunk(nn.Module):
-    def __init__(self):
+    def __init__(self, trunk_bwd: TrunkBackward):
         super().__init__()
         self.conv1 = nn.Conv2d(3, 64, 7, 2, 3, bias=False)
         self.bn1 = _TrunkBatchNorm(64)
@@ -178,7 +180,7 @@ class _ResNet34Trunk(nn.Module):
         self.maxpool = nn.MaxPool2d(3, 2, 1)
         cin = 64
         for i, (cout, n, s) in enumerate([(64, 3, 1), (128, 4, 2), (256, 6, 2), (512, 3, 2)], start=1):
-            setattr(self, f"layer{i}", nn.Sequential(*[_BasicBlock(cin if j == 0 else cout, cout, s if j == 0 else 1)
+            setattr(self, f"layer{i}", nn.Sequential(*[_BasicBlock(cin if j == 0 else cout, cout, s if j == 0 else 1, trunk_bwd)
                                                        for j in range(n)]))
             cin = cout
         self.avgpool = nn.Sequential()      # the reference replaces both by empty Sequentials (backbone.py:56-57)
@@ -228,7 +230,8 @@ class SpatialEncoder(nn.Module):
 
     def __init__(self):
         super().__init__()
-        self.model = _ResNet34Trunk()
+        self.trunk_bwd = TrunkBackward()            # not a parameter or buffer: state_dict is unchanged
+        self.model = _ResNet34Trunk(self.trunk_bwd)
 
     def _forward_infer(self, x):
         """eval() + no_grad on the GPU: library convolutions, each followed by ONE pass for batch norm, residual and ReLU

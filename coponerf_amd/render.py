@@ -385,7 +385,7 @@ class RenderEngine:
         # ramp / tail of the persistent grids: 26.6 -> 24.7 ms per image against chunks of 16 384
         self.chunk_rays = int(chunk_rays) or int(os.environ.get("COPONERF_CHUNK_RAYS", "0"))
         # training: every fp16 activation gradient carries a power-of-two scale chosen per backward pass so that the
-        # largest entry of the first fp32 -> fp16 gradient lands near this value (train_fns.GradScale)
+        # largest entry of the first fp32 -> fp16 gradient lands near this value (train_fns.BackwardPass)
         self.grad_scale_target = 256.0
         # ray chunks are independent: `lanes` HIP streams, each with its own workspace, take the chunks round-robin so
         # that the HBM-bound stages of one chunk (gather, hidden sums) run under the MFMA-bound GEMMs of another
@@ -921,7 +921,8 @@ class RenderEngine:
                      z: Sequence[torch.Tensor], rel_pose, val: bool, S: int, H: int, W: int) -> Dict[str, torch.Tensor]:
         """Same forward kernels as render(), wrapped in autograd Functions (coponerf_amd/train_fns.py); all rays of
         the call form one chunk (training uses <= 4096 rays per pair, /root/reference train.py:87)."""
-        from .train_fns import GemmFn, GradScale, HidGradParts, KeyForward, LinearF32Fn, LocalHiddenFn, AttendHiddenFn, EncodeFn
+        from .train_fns import (AttendHiddenFn, BackwardPass, EncodeFn, GemmFn, KeyForward, KeyLayerFn, LinearF32Fn,
+                                LocalHiddenFn)
         dev = uv.device
         if dev.type != "cuda":
             raise RuntimeError("coponerf_amd renders on a HIP device only (got uv on %s)" % dev)
@@ -931,8 +932,7 @@ class RenderEngine:
         g = self._geometry(ctx_c2w, ctx_K, qry_c2w, qry_K, uv, rel_pose, val, S, H, W)
         pixel_val_cpu, copy_done = self._start_host_copy(g["pixel_val"])    # the caller contract's CPU copy, off the main stream
         dims = (B, V, R, S)
-        gs = GradScale(self.grad_scale_target)      # one scale for all fp16 activation gradients of this pass
-        hp = HidGradParts()                         # rank-one gradients of hid, combined in its producer's backward
+        bp = BackwardPass(self.grad_scale_target)   # the fp16 gradient scale and the nodes' hand-offs of this backward pass
         P = params
         mat = lambda n, rows: P[n + ".weight"].reshape(rows, -1)
         bias = lambda n: P[n + ".bias"]
@@ -947,22 +947,23 @@ class RenderEngine:
         kf = KeyForward(Wkf, ckf)                   # the folded key layer's forward rides in the first layer's kernel
         # the first layer on the node tables with the key layer behind it, as in inference: no gathered input in the forward pass
         hid = EncodeFn.apply(z[0], z[1], z[2], z[3], mat("query_encode_latent", 832), bias("query_encode_latent"),
-                             g["pixel_val"], g["sec_grid"], g["pe6"], dims, (H, W), gs, hp, kf)
+                             g["pixel_val"], g["sec_grid"], g["pe6"], dims, (H, W), bp, kf)
         hid2 = hid.view(-1, 1664)
-        # (last consumer of hid in the backward pass; its incoming gradient arrives masked by kh > 0 from key_map_2's node)
-        kh = GemmFn.apply(hid2, Wkf, ckf, True, False, gs, None, dims, hp, kf, False, True)
-        key2 = GemmFn.apply(kh, mat("key_map_2", 128), bias("key_map_2"), False, False, gs, None, None, None, None, True)
-        hq = LocalHiddenFn.apply(g["loc8"], g["coords9"], mat("query_embed", 128), bias("query_embed"), None, dims, gs)
-        ce = GemmFn.apply(hq, mat("query_embed_2", 128), bias("query_embed_2"), False, False, gs)
-        hbar1, w1 = AttendHiddenFn.apply(key2, ce, hid2, dims, gs, hp, True)       # coords_embed is shared by the two rounds
-        z1 = GemmFn.apply(hbar1, Wvf, cvf, False, True, gs)
+        # the last consumer of hid in the backward pass: adds the parts the attention sums parked and masks by hid > 0
+        kh = KeyLayerFn.apply(hid2, Wkf, ckf, kf, dims, bp)
+        # in_relu: its data gradient comes back masked by kh > 0, handed over to the key layer
+        key2 = GemmFn.apply(kh, mat("key_map_2", 128), bias("key_map_2"), False, False, bp, True)
+        hq = LocalHiddenFn.apply(g["loc8"], g["coords9"], mat("query_embed", 128), bias("query_embed"), None, dims, bp)
+        ce = GemmFn.apply(hq, mat("query_embed_2", 128), bias("query_embed_2"), False, False, bp)
+        hbar1, w1 = AttendHiddenFn.apply(key2, ce, hid2, dims, bp, True)       # coords_embed is shared by the two rounds
+        z1 = GemmFn.apply(hbar1, Wvf, cvf, False, True, bp)
         ze = LinearF32Fn.apply(z1, mat("encode_latent", 128), bias("encode_latent"), None, False, False)
         Wr_z, Wr_l = mat("query_repeat_embed", 128).split((128, 16), 1)
         aq = LinearF32Fn.apply(ze, Wr_z.contiguous(), None, None, False, False)
-        q2h = LocalHiddenFn.apply(g["loc8"], g["coords9"], Wr_l.contiguous(), bias("query_repeat_embed"), aq, dims, gs)
-        q2 = GemmFn.apply(q2h, mat("query_repeat_embed_2", 128), bias("query_repeat_embed_2"), False, False, gs)
-        hbar2, _ = AttendHiddenFn.apply(q2, ce, hid2, dims, gs, hp, False)
-        zs = GemmFn.apply(hbar2, Wvf, cvf, False, True, gs)
+        q2h = LocalHiddenFn.apply(g["loc8"], g["coords9"], Wr_l.contiguous(), bias("query_repeat_embed"), aq, dims, bp)
+        q2 = GemmFn.apply(q2h, mat("query_repeat_embed_2", 128), bias("query_repeat_embed_2"), False, False, bp)
+        hbar2, _ = AttendHiddenFn.apply(q2, ce, hid2, dims, bp, False)
+        zs = GemmFn.apply(hbar2, Wvf, cvf, False, True, bp)
         zl = zs + float(V) * z1                                  # CoPoNeRF.py:481-485
         nray = B * R
         c18 = torch.zeros(nray, 32, dtype=torch.float32, device=dev)

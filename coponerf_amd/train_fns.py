@@ -23,21 +23,33 @@ def _stream() -> int:
     return _hip.stream_handle()
 
 
-class GradScale:
-    """Power-of-two scale carried by every fp16 activation gradient of ONE backward pass.
+class BackwardPass:
+    """What the nodes of ONE backward pass of render_train hand each other: the gradient scale, the parts of hid's gradient
+    parked for its producer, the parked shared coords_embed gradient, and the records of gradients already masked / combined.
 
-    The reference trains in fp32 (no GradScaler, /root/reference wrapper.py:107-151) and its loss is an L1 `.mean()`
+    Scale.  The reference trains in fp32 (no GradScaler, /root/reference wrapper.py:107-151) and its loss is an L1 `.mean()`
     over B*R*3 ~ 5e4 elements, so dL/drgb ~ 2e-5 — already below fp16's smallest normal (6.1e-5) — and the gradient of
     the per-sample hidden activations (softmax weight ~1/128 times that) would flush to zero if stored as plain
     fp16.  Convention on this path: a gradient tensor of dtype fp16 holds `s * true gradient`, one of dtype fp32 holds
     the true gradient.  `s` is fixed by the first backward function that turns an fp32 gradient into an fp16 one
     (2^k such that its largest entry lands near `target`), lives on the device (no host sync), and is divided out
     wherever an fp16 gradient is reduced into an fp32 one (weight / bias / feature-map gradients).  An overflow shows
-    up as a non-finite parameter gradient and makes the step's guard skip the update, like a lost AMP step."""
+    up as a non-finite parameter gradient and makes the step's guard skip the update, like a lost AMP step.
+
+    Hand-offs.  A node that returns a gradient already masked by its input's ReLU ("masked": key_map_2 -> the key layer) or
+    already combined ("combined": the key layer -> EncodeFn) records that tensor; the receiver skips the work only if its
+    incoming gradient is that storage (hid2 is a view of hid).  Anything else — e.g. a sum with a second consumer's gradient —
+    gets the full mask / combine, idempotent on what went through it already.  The record holds a reference, so autograd
+    cannot accumulate another gradient into that storage in place."""
 
     def __init__(self, target: float = 256.0):
         self.target = float(target)
         self.s = None
+        self.parts = []                     # rank-one parts of hid's gradient: (w (N,R,S) fp32, dhbar (rays,1664) fp32 scaled)
+        self.dqb = None                     # gradient of the shared qb (coords_embed) parked by the round that runs first
+        self.dqb_done = False
+        self.handed = {}                    # "masked" / "combined" -> the gradient tensor its producer returned
+        self.taken = []                     # the hand-offs whose shortcut was taken, in order
 
     def ensure(self, d32: torch.Tensor) -> torch.Tensor:
         if self.s is None:
@@ -49,24 +61,25 @@ class GradScale:
         """Incoming gradient -> the scaled representation (fp16 tensors already carry the scale)."""
         return d if d.dtype == torch.float16 else d * self.ensure(d)
 
+    def part_ptrs(self):
+        """(w1, dh1, w2, dh2) of the parked parts for cpn_hid_grad_combine / cpn_gemm_f16_combine, 0 where there is none."""
+        return ([t.data_ptr() for part in self.parts for t in part] + [0] * 4)[:4]
+
+    def hand_over(self, name: str, grad: torch.Tensor) -> torch.Tensor:
+        self.handed[name] = grad
+        return grad
+
+    def take(self, name: str, grad: torch.Tensor) -> bool:
+        """True if `grad` is the tensor handed over as `name`; the record is dropped either way."""
+        sent = self.handed.pop(name, None)
+        ok = sent is not None and grad.data_ptr() == sent.data_ptr() and grad.numel() == sent.numel()
+        if ok:
+            self.taken.append(name)
+        return ok
+
 
 # cpn_hid_grad_combine as the epilogue of the key path's data-gradient GEMM (cpn_gemm_f16_combine; round 6); 0 = two kernels
 FUSE_COMBINE = os.environ.get("COPONERF_FUSE_COMBINE", "1") != "0"
-
-
-class HidGradParts:
-    """Gradient contributions to the hidden activations `hid` that are rank one per ray (w (x) dhbar, from the two
-    attention-weighted hidden sums).  Their backward functions park them here instead of materialising a 7 GB tensor
-    each; the backward of the layer that PRODUCED hid (autograd runs it after all of hid's consumers) combines them with
-    the key path's gradient and the ReLU mask in one kernel (cpn_hid_grad_combine)."""
-
-    def __init__(self):
-        self.parts = []                     # (w (N,R,S) fp32, dhbar (rays,1664) fp32 scaled)
-        self.combined = False               # the key path's data-gradient GEMM already formed the masked sum (FUSE_COMBINE)
-        self.dqb = None                     # gradient of the shared qb (coords_embed) parked by the round that runs first
-        self.dqb_done = False
-
-
 # coords_embed feeds both attention rounds: the second backward call adds the first one's gradient in its kernel
 SHARE_QB_GRAD = os.environ.get("COPONERF_SHARE_QB_GRAD", "1") != "0"
 # grad_input of key_map_2 with the ReLU mask of its input as the GEMM's epilogue (cpn_gemm_f16_masked)
@@ -74,14 +87,14 @@ MASKED_DGRAD = os.environ.get("COPONERF_MASKED_DGRAD", "1") != "0"
 
 
 class KeyForward:
-    """Hand-over between EncodeFn and the GemmFn node of the folded key layer (kh = ReLU(W' . [hid_own ; hid_other] + c')): the
-    first layer's kernel also forms kh (cpn_encode_key, as in inference: hid is not read back for it), and the GemmFn node only
+    """Hand-over between EncodeFn and KeyLayerFn, the node of the folded key layer (kh = ReLU(W' . [hid_own ; hid_other] + c')):
+    the first layer's kernel also forms kh (cpn_encode_key, as in inference: hid is not read back for it), and KeyLayerFn only
     records what its backward needs.  W (128, 1664) / b (128): the folded, differentiable fp32 weights (render_train)."""
 
     def __init__(self, W, b):
         self.W, self.b = W, b
         self.W16 = None                      # (128, 1664) fp16 image of W, packed once for both nodes
-        self.kh = None                       # (rows, 128) fp16, set by EncodeFn.forward, taken by GemmFn.forward
+        self.kh = None                       # (rows, 128) fp16, set by EncodeFn.forward, taken by KeyLayerFn.forward
 
 
 def _mm_f32(a16: torch.Tensor, b16: torch.Tensor) -> torch.Tensor:
@@ -132,106 +145,107 @@ def _data_grad(d16: torch.Tensor, W16: torch.Tensor, mask: torch.Tensor = None) 
     return dA if mask is None else torch.ops.aten.threshold_backward(dA, mask, 0)
 
 
+def _weight_grads(d, d16, A16, K: int, s: torch.Tensor, need_w: bool, need_b: bool):
+    """(dW (N, K), db (N)) fp32 of a layer with input A16 (M, lda) fp16 from its scaled output gradient d16 (M, N) fp16, s
+    divided out.  The bias sums `d`, the same gradient before its rounding to fp16 where the layer received it in fp32."""
+    inv = 1.0 / s
+    if d16.shape[1] == 128 and A16.shape[1] == 128 and d16.is_contiguous() and need_w:
+        # 128 x 128 outputs over millions of rows: a streaming reduction, not a GEMM the library handles well
+        dW = torch.zeros(128, 128, dtype=torch.float32, device=d16.device)
+        db = torch.zeros(128, dtype=torch.float32, device=d16.device)
+        call("cpn_wgrad_skinny_f16", d16.data_ptr(), A16.data_ptr(), 128, d16.shape[0], dW.data_ptr(), db.data_ptr(),
+             _stream())
+        return dW[:, :K] * inv, (db * inv if need_b else None)
+    n_out, k_in = d16.shape[1], A16.shape[1]
+    both = d16.is_contiguous() and A16.is_contiguous()
+    if need_w and both and n_out % 208 == 0 and k_in % 128 == 0:
+        dW = _wgrad_tall(d16, A16, s)[:, :K]                              # the 832 x 896 first layer in its gather form
+    elif need_w and both and k_in % 208 == 0 and n_out % 128 == 0:
+        # 128 x 1664 (key map over the paired hidden rows): the same kernel on the transposed problem, dW^T = A^T . d
+        dW = _wgrad_tall(A16, d16, s).t()[:, :K]
+    else:
+        dW = _mm_f32(d16.t(), A16)[:, :K] * inv if need_w else None
+    db = _colsum_f32(d) * inv if need_b else None
+    return dW, db
+
+
 class GemmFn(Function):
     """C = act(A . W^T + b) through cpn_gemm_f16.  A (M, lda) fp16 (row stride lda >= K), W (N, K) fp32, b (N)."""
 
     @staticmethod
-    def forward(ctx, A16, W, b, relu: bool, out_f32: bool, gs: GradScale, hid_parts=None, dims=None, in_parts=None, pre=None,
-                in_relu: bool = False, premasked: bool = False):
-        """in_relu: A16 is a ReLU output whose producer was told `premasked` - this node's backward returns the data gradient
-        already masked by A16 > 0 (cpn_gemm_f16_masked), the producer skips its threshold pass."""
+    def forward(ctx, A16, W, b, relu: bool, out_f32: bool, bp: BackwardPass, in_relu: bool = False):
+        """in_relu: A16 is a ReLU output (kh) - the backward returns the data gradient already masked by A16 > 0
+        (cpn_gemm_f16_masked) and hands it over to A16's producer as "masked"."""
         M, lda = A16.shape
         N, K = W.shape
         Kp = ((K + 31) // 32) * 32
         assert Kp <= lda, (K, lda)
-        if pre is not None and pre.kh is not None:
-            # the product already exists (cpn_encode_key formed it with the first layer, same MFMA sequence): record only
-            assert relu and not out_f32 and pre.kh.shape == (M, N) and pre.W16.shape == (N, lda)
-            W16, C = pre.W16, pre.kh
-            pre.kh = pre.W16 = None
-        else:
-            W16 = torch.zeros(N, lda, dtype=torch.float16, device=A16.device)
-            Wc = W.detach().contiguous().float()
-            call("cpn_pack_weight_f16", Wc.data_ptr(), N, K, W16.data_ptr(), lda, _stream())
-            bc = b.detach().contiguous().float()
-            C = torch.empty(M, N, dtype=torch.float32 if out_f32 else torch.float16, device=A16.device)
-            call("cpn_gemm_f16", A16.data_ptr(), lda, W16.data_ptr(), lda, bc.data_ptr(), C.data_ptr(), N, M, N, Kp,
-                 int(relu), int(out_f32), _stream())
+        W16 = torch.zeros(N, lda, dtype=torch.float16, device=A16.device)
+        Wc = W.detach().contiguous().float()
+        call("cpn_pack_weight_f16", Wc.data_ptr(), N, K, W16.data_ptr(), lda, _stream())
+        bc = b.detach().contiguous().float()
+        C = torch.empty(M, N, dtype=torch.float32 if out_f32 else torch.float16, device=A16.device)
+        call("cpn_gemm_f16", A16.data_ptr(), lda, W16.data_ptr(), lda, bc.data_ptr(), C.data_ptr(), N, M, N, Kp,
+             int(relu), int(out_f32), _stream())
         ctx.save_for_backward(A16, W16, C if relu else None)
-        ctx.relu, ctx.K, ctx.gs = relu, K, gs
-        ctx.hid_parts, ctx.dims, ctx.in_parts = hid_parts, dims, in_parts
-        ctx.in_relu, ctx.premasked = in_relu and MASKED_DGRAD, premasked and MASKED_DGRAD
+        ctx.relu, ctx.K, ctx.bp, ctx.in_relu = relu, K, bp, in_relu and MASKED_DGRAD
         return C
-
-    @staticmethod
-    def _combined_data_grad(ctx, d16, A16, W16):
-        """A16 = hid (rows, 1664): dA and the gradients parked by the two attention sums, masked, in one kernel — this layer
-        is the LAST consumer of hid that autograd runs (its gradient depends on both sums' backward passes)."""
-        hp = ctx.in_parts
-        B, V, R, S = ctx.dims
-        K = d16.shape[1]
-        if not (FUSE_COMBINE and hp is not None and hp.parts and A16.shape[1] == 1664 and S % 16 == 0 and K % 32 == 0
-                and d16.is_contiguous() and A16.is_contiguous() and ctx.needs_input_grad[0]):
-            return None
-        parts = hp.parts
-        (w1, dh1), (w2, dh2) = parts[0], (parts[1] if len(parts) > 1 else (None, None))
-        Wt = W16.t().contiguous()                                              # (1664, K)
-        out = torch.empty_like(A16)
-        call("cpn_gemm_f16_combine", d16.data_ptr(), K, Wt.data_ptr(), K, A16.data_ptr(), w1.data_ptr(), dh1.data_ptr(),
-             0 if w2 is None else w2.data_ptr(), 0 if dh2 is None else dh2.data_ptr(), B, V, R, S, 0, B * R, K, out.data_ptr(),
-             _stream())
-        hp.parts = []
-        hp.combined = True
-        return out
 
     @staticmethod
     def backward(ctx, dC):
         A16, W16, C = ctx.saved_tensors
-        if ctx.hid_parts is not None and ctx.hid_parts.parts:
-            # C = hid: key-path gradient (dC) + the parked rank-one contributions + ReLU mask in ONE pass
-            B, V, R, S = ctx.dims
-            d = ctx.gs.scaled16(dC.contiguous()).to(torch.float16)
-            parts = ctx.hid_parts.parts
-            (w1, dh1), (w2, dh2) = parts[0], (parts[1] if len(parts) > 1 else (None, None))
-            d16 = torch.empty_like(C)
-            call("cpn_hid_grad_combine", d.data_ptr(), C.data_ptr(), w1.data_ptr(), dh1.data_ptr(),
-                 0 if w2 is None else w2.data_ptr(), 0 if dh2 is None else dh2.data_ptr(), B, V, R, S, 0, B * R,
-                 d16.data_ptr(), _stream())
-            ctx.hid_parts.parts = []
-            ctx.hid_parts.combined = False
-            d = d16
-            inv = 1.0 / ctx.gs.s
-        else:
-            if ctx.hid_parts is not None:
-                ctx.hid_parts.combined = False
-            d = ctx.gs.scaled16(dC.contiguous())                                 # s * dC (GradScale convention)
-            inv = 1.0 / ctx.gs.s
-            if ctx.relu and not (ctx.premasked and d.dtype == torch.float16):
-                d = torch.ops.aten.threshold_backward(d, C.to(d.dtype) if C.dtype != d.dtype else C, 0)   # d where C > 0
-            d16 = d.to(torch.float16)
-        dA = GemmFn._combined_data_grad(ctx, d16, A16, W16) if ctx.in_parts is not None else None
-        if dA is None and ctx.in_relu and ctx.needs_input_grad[0]:
-            dA = _data_grad(d16, W16, mask=A16)
-        if dA is None:
-            dA = _data_grad(d16, W16) if ctx.needs_input_grad[0] else None           # (M, lda) fp16, scaled; pad columns get 0
-        if d16.shape[1] == 128 and A16.shape[1] == 128 and d16.is_contiguous() and ctx.needs_input_grad[1]:
-            # 128 x 128 outputs over millions of rows: a streaming reduction, not a GEMM the library handles well
-            dW = torch.zeros(128, 128, dtype=torch.float32, device=d16.device)
-            db = torch.zeros(128, dtype=torch.float32, device=d16.device)
-            call("cpn_wgrad_skinny_f16", d16.data_ptr(), A16.data_ptr(), 128, d16.shape[0], dW.data_ptr(), db.data_ptr(),
-                 _stream())
-            return (dA, dW[:, :ctx.K] * inv, (db * inv if ctx.needs_input_grad[2] else None)) + (None,) * 9
-        n_out, k_in = d16.shape[1], A16.shape[1]
-        both = d16.is_contiguous() and A16.is_contiguous()
-        if ctx.needs_input_grad[1] and both and n_out % 208 == 0 and k_in % 128 == 0:
-            dW = _wgrad_tall(d16, A16, ctx.gs.s)[:, :ctx.K]              # the 832 x 896 first layer in its gather form
-        elif ctx.needs_input_grad[1] and both and k_in % 208 == 0 and n_out % 128 == 0:
-            # 128 x 1664 (key map over the paired hidden rows): the same kernel on the transposed problem, dW^T = A^T . d
-            dW = _wgrad_tall(A16, d16, ctx.gs.s).t()[:, :ctx.K]
-        else:
-            dW = _mm_f32(d16.t(), A16)[:, :ctx.K] * inv if ctx.needs_input_grad[1] else None
-        db = _colsum_f32(d) * inv if ctx.needs_input_grad[2] else None
-        return (dA, dW, db) + (None,) * 9
+        bp = ctx.bp
+        d = bp.scaled16(dC.contiguous())                                     # s * dC (BackwardPass convention)
+        if ctx.relu:
+            d = torch.ops.aten.threshold_backward(d, C.to(d.dtype) if C.dtype != d.dtype else C, 0)   # d where C > 0
+        d16 = d.to(torch.float16)
+        dA = None                                                            # (M, lda) fp16, scaled; pad columns get 0
+        if ctx.needs_input_grad[0] and ctx.in_relu:
+            dA = bp.hand_over("masked", _data_grad(d16, W16, mask=A16))
+        elif ctx.needs_input_grad[0]:
+            dA = _data_grad(d16, W16)
+        dW, db = _weight_grads(d, d16, A16, ctx.K, bp.s, ctx.needs_input_grad[1], ctx.needs_input_grad[2])
+        return (dA, dW, db) + (None,) * 4
+
+
+class KeyLayerFn(Function):
+    """kh = ReLU(W' . [hid_own ; hid_other] + c') on hid2 = hid viewed as (rows, 1664): the folded key layer, whose product
+    EncodeFn's kernel already formed (KeyForward).  In the backward it is the LAST consumer of hid that autograd runs (its
+    gradient depends on both attention sums' backward passes), so its data-gradient GEMM also adds the parts those parked
+    and applies hid's ReLU mask (cpn_gemm_f16_combine), handing the result over to EncodeFn as "combined"."""
+
+    @staticmethod
+    def forward(ctx, hid2, W, b, key: KeyForward, dims, bp: BackwardPass):
+        kh, W16 = key.kh, key.W16
+        assert kh is not None and kh.shape == (hid2.shape[0], W.shape[0]) and W16.shape == (W.shape[0], hid2.shape[1])
+        key.kh = key.W16 = None
+        ctx.save_for_backward(hid2, W16, kh)
+        ctx.K, ctx.dims, ctx.bp = W.shape[1], dims, bp
+        return kh
+
+    @staticmethod
+    def backward(ctx, dkh):
+        hid2, W16, kh = ctx.saved_tensors
+        bp = ctx.bp
+        B, V, R, S = ctx.dims
+        d = bp.scaled16(dkh.contiguous())
+        if not bp.take("masked", dkh):                                       # (key_map_2's GEMM masked it already)
+            d = torch.ops.aten.threshold_backward(d, kh.to(d.dtype) if kh.dtype != d.dtype else kh, 0)   # d where kh > 0
+        d16 = d.to(torch.float16)
+        K = d16.shape[1]
+        dA = None
+        if (ctx.needs_input_grad[0] and FUSE_COMBINE and bp.parts and hid2.shape[1] == 1664 and S % 16 == 0 and K % 32 == 0
+                and d16.is_contiguous() and hid2.is_contiguous()):
+            # d16 . W16 plus the parts parked by the two attention sums, masked by hid > 0, in one kernel
+            Wt = W16.t().contiguous()                                        # (1664, K)
+            dA = bp.hand_over("combined", torch.empty_like(hid2))
+            call("cpn_gemm_f16_combine", d16.data_ptr(), K, Wt.data_ptr(), K, hid2.data_ptr(), *bp.part_ptrs(), B, V, R, S, 0,
+                 B * R, K, dA.data_ptr(), _stream())
+            bp.parts = []
+        elif ctx.needs_input_grad[0]:
+            dA = _data_grad(d16, W16)
+        dW, db = _weight_grads(d, d16, hid2, ctx.K, bp.s, ctx.needs_input_grad[1], ctx.needs_input_grad[2])
+        return dA, dW, db, None, None, None
 
 
 class LinearF32Fn(Function):
@@ -269,7 +283,7 @@ class LocalHiddenFn(Function):
     """out = fp16(relu(W . L(row) + b + add[ray])) through cpn_local_hidden."""
 
     @staticmethod
-    def forward(ctx, loc8, coords9, W, b, add, dims, gs: GradScale):
+    def forward(ctx, loc8, coords9, W, b, add, dims, bp: BackwardPass):
         B, V, R, S = dims
         nrays = B * R
         Wc, bc = W.detach().contiguous().float(), b.detach().contiguous().float()
@@ -278,33 +292,34 @@ class LocalHiddenFn(Function):
         call("cpn_local_hidden", loc8.data_ptr(), coords9.data_ptr(), Wc.data_ptr(), Wc.shape[1], bc.data_ptr(),
              0 if ac is None else ac.data_ptr(), B, V, R, S, 0, nrays, out.data_ptr(), _stream())
         ctx.save_for_backward(loc8, coords9, out)
-        ctx.dims, ctx.has_add, ctx.gs = dims, add is not None, gs
+        ctx.dims, ctx.has_add, ctx.bp = dims, add is not None, bp
         return out
 
     @staticmethod
     def backward(ctx, dout):
         loc8, coords9, out = ctx.saved_tensors
         B, V, R, S = ctx.dims
-        ds = ctx.gs.scaled16(dout.contiguous()).to(torch.float16)
+        ds = ctx.bp.scaled16(dout.contiguous()).to(torch.float16)
         dev = ds.device
         # ReLU mask, un-scaling, the 128 x 16 weight gradient, the bias gradient and the per-ray sum in one pass over ds
         dW = torch.zeros(128, 16, dtype=torch.float32, device=dev)
         db = torch.zeros(128, dtype=torch.float32, device=dev)
         dadd = torch.empty(B * R, 128, dtype=torch.float32, device=dev) if ctx.has_add else None
-        scale = ctx.gs.s.reshape(1).float().contiguous()
+        scale = ctx.bp.s.reshape(1).float().contiguous()
         call("cpn_local_hidden_bwd", ds.data_ptr(), out.data_ptr(), loc8.data_ptr(), coords9.data_ptr(), scale.data_ptr(),
              B, V, R, S, dW.data_ptr(), db.data_ptr(), 0 if dadd is None else dadd.data_ptr(), _stream())
         return None, None, dW, db, dadd, None, None
 
 
 class AttendHiddenFn(Function):
-    """(hbar fp16 (rays,1664), w fp32 (N,R,S)) = cpn_attend_hidden(qa, qb, hid)."""
+    """(hbar fp16 (rays,1664), w fp32 (N,R,S)) = cpn_attend_hidden(qa, qb, hid).  hid's gradient w (x) dhbar is rank one per
+    ray: the backward parks (w, dhbar) in the pass for hid's producer instead of materialising a 7 GB tensor."""
 
     @staticmethod
-    def forward(ctx, qa, qb, hid2, dims, gs: GradScale, hid_parts=None, qb_last=None):
+    def forward(ctx, qa, qb, hid2, dims, bp: BackwardPass, qb_last=None):
         """qb_last: None = qb is this node's own; False / True = qb (coords_embed) is shared by two nodes and this is the one
         whose backward runs first / last (round 2 / round 1: round 1's gradient depends on round 2's backward).  The first
-        parks its dqb in hid_parts and returns none, the last adds it inside the kernel (an autograd accumulation of two
+        parks its dqb in the pass and returns none, the last adds it inside the kernel (an autograd accumulation of two
         0.5 GB tensors otherwise)."""
         B, V, R, S = dims
         nrays = B * R
@@ -313,7 +328,7 @@ class AttendHiddenFn(Function):
         call("cpn_attend_hidden", qa.data_ptr(), qb.data_ptr(), 0, hid2.data_ptr(), B, V, R, S, 0, nrays, hbar.data_ptr(),
              w.data_ptr(), _stream())
         ctx.save_for_backward(qa, qb, hid2, w)
-        ctx.dims, ctx.gs, ctx.hid_parts, ctx.qb_last = dims, gs, hid_parts, qb_last
+        ctx.dims, ctx.bp, ctx.qb_last = dims, bp, qb_last
         return hbar, w
 
     @staticmethod
@@ -321,32 +336,28 @@ class AttendHiddenFn(Function):
         qa, qb, hid2, w = ctx.saved_tensors
         B, V, R, S = ctx.dims
         nrays = B * R
-        gs = ctx.gs
+        bp = ctx.bp
         # the kernel is linear in (dhbar, dw): feed both in the scaled representation, get scaled fp16 gradients back.
         # dhbar (fp16) already carries the scale its producer fixed; if only the softmax weights received a gradient
         # (dhbar is the materialised zero tensor) the scale is fixed here from dw
-        if gs.s is None:
-            gs.ensure(dw)
+        if bp.s is None:
+            bp.ensure(dw)
         dh = dhbar.float().contiguous()
-        dwc = None if dw is None else (dw.float() * gs.s).contiguous()
+        dwc = None if dw is None else (dw.float() * bp.s).contiguous()
         dqa, dqb = torch.empty_like(qa), torch.empty_like(qb)
-        park = ctx.hid_parts is not None
-        dhid = None if park else torch.empty_like(hid2)
-        hp = ctx.hid_parts
-        share = SHARE_QB_GRAD and hp is not None and ctx.qb_last is not None
-        acc = hp.dqb if (share and ctx.qb_last) else None
+        share = SHARE_QB_GRAD and ctx.qb_last is not None
+        acc = bp.dqb if (share and ctx.qb_last) else None
         call("cpn_attend_hidden_bwd", qa.data_ptr(), qb.data_ptr(), hid2.data_ptr(), w.data_ptr(), dh.data_ptr(),
-             0 if dwc is None else dwc.data_ptr(), B, V, R, S, 0, nrays, dqa.data_ptr(), dqb.data_ptr(),
-             0 if park else dhid.data_ptr(), 0 if acc is None else acc.data_ptr(), _stream())
-        if park:                            # dhid = w (x) dhbar is formed by the producer of hid (cpn_hid_grad_combine)
-            hp.parts.append((w, dh))
+             0 if dwc is None else dwc.data_ptr(), B, V, R, S, 0, nrays, dqa.data_ptr(), dqb.data_ptr(), 0,
+             0 if acc is None else acc.data_ptr(), _stream())
+        bp.parts.append((w, dh))            # dhid = w (x) dhbar is formed by the producer of hid (cpn_hid_grad_combine)
         if share:
             if ctx.qb_last:
-                hp.dqb, hp.dqb_done = None, True
-            elif not hp.dqb_done:           # (had the other round already run, nobody would pick the parked tensor up)
-                hp.dqb = dqb
+                bp.dqb, bp.dqb_done = None, True
+            elif not bp.dqb_done:           # (had the other round already run, nobody would pick the parked tensor up)
+                bp.dqb = dqb
                 dqb = None
-        return dqa, dqb, dhid, None, None, None, None
+        return dqa, dqb, None, None, None, None
 
 
 class EncodeFn(Function):
@@ -355,7 +366,7 @@ class EncodeFn(Function):
     The backward differentiates the layer in its table form (csrc/encode_bwd.hip, _backward_tables)."""
 
     @staticmethod
-    def forward(ctx, z0, z1, z2, z3, W, b, pixel_val, sec_grid, pe6, dims, HW, gs: GradScale, hid_parts, key=None):
+    def forward(ctx, z0, z1, z2, z3, W, b, pixel_val, sec_grid, pe6, dims, HW, bp: BackwardPass, key: KeyForward):
         B, V, R, S = dims
         H, Wd = HW
         s = _stream()
@@ -382,8 +393,6 @@ class EncodeFn(Function):
              _hip.TAB_LD, 768, 0, 0, s)
         nrays = B * R
         hid = torch.empty(nrays * V * S * 2, 832, dtype=torch.float16, device=dev)
-        if key is None:                      # a caller that only wants hid: a zero key layer rides along
-            key = KeyForward(torch.zeros(128, 1664, device=dev), torch.zeros(128, device=dev))
         from .render import pack_key_ring
         Wk = key.W.detach().contiguous().float()
         key.W16 = torch.empty(128, 1664, dtype=torch.float16, device=dev)
@@ -398,7 +407,7 @@ class EncodeFn(Function):
         call("cpn_pack_weight_f16", Wc.data_ptr(), 832, Wc.shape[1], W16.data_ptr(), 896, s)
         del tab, maps[0], maps[0], maps[0]                               # maps is now [level 3]
         ctx.save_for_backward(maps[0], pixel_val, sec_grid, pe6, W16, hid, feat, wtab)
-        ctx.dims, ctx.HW, ctx.gs, ctx.hid_parts, ctx.K = dims, HW, gs, hid_parts, Wc.shape[1]
+        ctx.dims, ctx.HW, ctx.bp, ctx.K = dims, HW, bp, Wc.shape[1]
         ctx.shapes = [tuple(t.shape) for t in (z0, z1, z2, z3)]
         return hid
 
@@ -416,7 +425,7 @@ class EncodeFn(Function):
         lib = _hip.lib()
         nimg = B * V
         nodes = nimg * int(lib.cpn_encode_table_nodes(H, Wd))
-        gs = ctx.gs.s
+        gs = ctx.bp.s
         # ---- table gradient (fp32, carries the pass's scale gs)
         dT = torch.zeros(nodes, _hip.TAB_LD, dtype=torch.float32, device=dev)
         boxes = torch.empty(int(lib.cpn_scatter_tables_scratch(H, Wd, B, V, R, S)), dtype=torch.int32, device=dev)
@@ -452,8 +461,6 @@ class EncodeFn(Function):
             # handed on as the NHWC buffer it is (an NCHW view with channels-last strides): its only consumer is conv_map's
             # backward, a library convolution that takes that layout; the .contiguous() here was a 134 MB transpose
             g[3] = dm3.mul_(1.0 / gs).permute(0, 3, 1, 2)
-            if os.environ.get("COPONERF_NCHW_LEVEL3_GRAD") == "1":
-                g[3] = g[3].contiguous()
         dW = db = None
         if ctx.needs_input_grad[4] or ctx.needs_input_grad[5]:
             xt = torch.empty(d16.shape[0], 128, dtype=torch.float16, device=dev)
@@ -464,29 +471,21 @@ class EncodeFn(Function):
                 dW = torch.cat((dWtab, dWt[:, :ctx.K - 768]), dim=1)
             if ctx.needs_input_grad[5]:
                 db = dWt[:, ctx.K - 768].contiguous()
-        return g[0], g[1], g[2], g[3], dW, db, None, None, None, None, None, None, None, None
+        return g[0], g[1], g[2], g[3], dW, db, None, None, None, None, None, None, None
 
     @staticmethod
     def backward(ctx, dC):
         hid = ctx.saved_tensors[5]
         B, V, R, S = ctx.dims
-        H, Wd = ctx.HW
         s = _stream()
-        d = ctx.gs.scaled16(dC.contiguous()).to(torch.float16)
-        if ctx.hid_parts is not None and ctx.hid_parts.combined and not ctx.hid_parts.parts:
-            # the key path's data-gradient GEMM already added the parked parts and applied the mask (cpn_gemm_f16_combine)
-            ctx.hid_parts.combined = False
+        bp = ctx.bp
+        d = bp.scaled16(dC.contiguous()).to(torch.float16)
+        if not bp.parts and bp.take("combined", dC):
+            # the key layer's data-gradient GEMM already added the parked parts and applied the mask (cpn_gemm_f16_combine)
             d16 = d.view(hid.shape)
         else:                                                # (parts parked after a fused combine are still added here)
-            parts = ctx.hid_parts.parts if ctx.hid_parts is not None else []
-            (w1, dh1) = parts[0] if len(parts) > 0 else (None, None)
-            (w2, dh2) = parts[1] if len(parts) > 1 else (None, None)
-            d16 = torch.empty_like(hid)                      # relu mask (.) (key-path gradient + parked rank-one parts)
-            call("cpn_hid_grad_combine", d.data_ptr(), hid.data_ptr(), 0 if w1 is None else w1.data_ptr(),
-                 0 if dh1 is None else dh1.data_ptr(), 0 if w2 is None else w2.data_ptr(), 0 if dh2 is None else dh2.data_ptr(),
-                 B, V, R, S, 0, B * R, d16.data_ptr(), s)
-            if ctx.hid_parts is not None:
-                ctx.hid_parts.parts = []
-                ctx.hid_parts.combined = False
+            d16 = torch.empty_like(hid)                      # relu mask (.) (incoming gradient + parked rank-one parts)
+            call("cpn_hid_grad_combine", d.data_ptr(), hid.data_ptr(), *bp.part_ptrs(), B, V, R, S, 0, B * R, d16.data_ptr(), s)
+            bp.parts = []
         del d
         return EncodeFn._backward_tables(ctx, d16)

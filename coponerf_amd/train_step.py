@@ -64,7 +64,7 @@ class TrainStep:
         self.timing: Optional[Dict[str, list]] = None                    # set to {} to collect HIP-event timings
         # reorder every step's query rays by image tile (_rays_by_tile); COPONERF_SORT_RAYS=0: as given
         self.sort_rays = os.environ.get("COPONERF_SORT_RAYS", "1") != "0"
-        # fp16 activation gradients carry a static per-pass scale (train_fns.GradScale).  If they overflow the guard
+        # fp16 activation gradients carry a static per-pass scale (train_fns.BackwardPass).  If they overflow the guard
         # skips the step and the next pass would pick the same scale: back the target off (x 1/4 per skipped step, down
         # to 1) and restore it (x 2 every `growth_interval` good steps) like an AMP GradScaler does.  Where the guard runs on
         # the device the outcome of a step reaches this adaptation one or two steps LATE (its 4-byte copy is not waited for):
@@ -204,8 +204,9 @@ class TrainStep:
 
     def _adapt_grad_scale(self, stepped: bool) -> None:
         eng = getattr(self.model, "_engine", None)
-        from . import getz as _getz
-        _getz.trunk_bwd_target_backoff(stepped)
+        trunk = getattr(getattr(self.model, "encoder", None), "trunk_bwd", None)     # the trunk's fp16 backward (getz)
+        if trunk is not None:
+            trunk.after_step(stepped)
         if stepped:
             self.skipped_in_a_row = 0
             self._good += 1

@@ -94,18 +94,17 @@ def test_step_gradients_match_reference_at_4096_rays(tag, model, dev):
     assert not bad, sc.report(bad, 40)
 
 
-def test_trunk_fp16_backward_against_fp32_backward(model, dev):
+def test_trunk_fp16_backward_against_fp32_backward_on_model_state(model, dev):
     """The trunk's convolution backward on fp16 operands (getz._ConvF16BwdFn) against the library's fp32 backward of the same
     step, with the run-to-run spread of the fp32 backward itself beside it (the render backward accumulates with atomics, so
     two fp32 passes already differ upstream of z), and the fp16 results dx / dw two decades below fp16's largest number."""
-    from coponerf_amd import getz
     inp, gt = sc.inputs(4096)
     inp, gt = to_device(inp, dev), gt.to(dev)
-    getz._TRUNK_BWD_TARGET[0] = 4.0            # (process-wide; tests that force skipped steps back it off)
+    trunk = model.encoder.trunk_bwd
 
     def trunk_grads(f16: bool):
-        old = getz.F16_TRUNK_BACKWARD
-        getz.F16_TRUNK_BACKWARD = f16
+        old = trunk.enabled
+        trunk.enabled = f16
         try:
             model.zero_grad(set_to_none=True)
             out = model(inp, val=False)
@@ -116,7 +115,7 @@ def test_trunk_fp16_backward_against_fp32_backward(model, dev):
             return {n: p.grad.detach().clone() for n, p in model.named_parameters()
                     if n.startswith("encoder.") and p.grad is not None and p.dim() == 4}
         finally:
-            getz.F16_TRUNK_BACKWARD = old
+            trunk.enabled = old
 
     def apart(a, b):
         rows = sorted((((a[n] - g).norm() / g.norm().clamp_min(1e-30)).item(), n) for n, g in b.items())
@@ -124,12 +123,12 @@ def test_trunk_fp16_backward_against_fp32_backward(model, dev):
 
     ref = trunk_grads(False)
     again = trunk_grads(False)
-    getz.F16_BWD_TRACE = []
+    trunk.trace = []
     try:
         half = trunk_grads(True)
-        trace = getz.F16_BWD_TRACE
+        trace = trunk.trace
     finally:
-        getz.F16_BWD_TRACE = None
+        trunk.trace = None
     assert len(trace) >= 30                                   # the 3x3 / 1x1 layers of the trunk took the fp16 path
     top = max(float(t) for _, dx, dw in trace for t in (dx, dw) if t is not None)
     spread, worst = apart(again, ref), apart(half, ref)

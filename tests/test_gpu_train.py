@@ -293,7 +293,7 @@ def test_conv_weight_gradient_kernels(dev):
 def test_mean_loss_gradients_survive_fp16(dev):
     """the reference's loss is an L1 `.mean()` over B*R*3 ~ 5e4 values, so dL/drgb ~ 2e-5 and the
     per-sample activation gradients (~1e-8) underflow plain fp16.  With the per-pass power-of-two scale of
-    train_fns.GradScale every gradient must match fp32 autograd through the oracle at THAT magnitude (the loss below
+    train_fns.BackwardPass every gradient must match fp32 autograd through the oracle at THAT magnitude (the loss below
     is the small case's L1 sum divided by 4*4096*3, i.e. the configs[2] normalisation)."""
     from coponerf_amd import CoPoNeRF
     from oracle import render_ref as orc
@@ -866,6 +866,66 @@ def test_backward_fusions_leave_the_gradients_alone(dev, monkeypatch):
     for k in res[0]:                                         # the shared gradient is summed in fp32 before ONE fp16 rounding
         rel_err = float((res[0][k] - res[1][k]).norm() / (res[1][k].norm() + 1e-30))
         assert rel_err <= 2e-3, (k, rel_err)
+
+
+def test_backward_hand_offs_take_their_shortcuts(dev, monkeypatch):
+    """In a default render_train backward key_map_2's node hands the key layer its gradient already masked by kh > 0, and
+    the key layer hands EncodeFn hid's gradient already combined and masked: each receiver recognises the tensor it gets."""
+    from coponerf_amd import CoPoNeRF, train_fns
+    passes = []
+
+    class Recorded(train_fns.BackwardPass):
+        def __init__(self, *args):
+            super().__init__(*args)
+            passes.append(self)
+
+    monkeypatch.setattr(train_fns, "BackwardPass", Recorded)
+    monkeypatch.setattr(train_fns, "FUSE_COMBINE", True)
+    monkeypatch.setattr(train_fns, "MASKED_DGRAD", True)
+    B, H, R, S = 2, 64, 40, 32
+    weights = syn.make_render_weights(seed=31)
+    inp = to_device(syn.make_inputs(B, H, H, R, seed=65), dev)
+    z, rel, flow = syn.make_latents(B, H, H, seed=66)
+    model = CoPoNeRF.CoPoNeRF(n_view=2, npoints=S)
+    model.load_state_dict(weights, strict=False)
+    model = model.to(dev).train()
+    zz = [t.to(dev).requires_grad_(True) for t in z]
+    out = model(inp, z=zz, rel_pose=rel.to(dev), val=False, flow=to_device(flow, dev))
+    (out["rgb"] * syn.normal((B, 1, R, 3), seed=67).to(dev)).sum().backward()
+    assert len(passes) == 1
+    bp = passes[0]
+    assert bp.taken == ["masked", "combined"] and not bp.handed and not bp.parts
+    assert all(t.grad is not None for t in zz)
+
+
+def test_key_layer_masks_a_gradient_it_was_not_handed(dev):
+    """The key layer / key_map_2 pair built directly, with a second consumer of kh: the gradient reaching the key layer is
+    the sum of key_map_2's masked one and the other consumer's, so the key layer applies the ReLU mask itself.  Its data
+    gradient against float64 on the same operands."""
+    from coponerf_amd.train_fns import BackwardPass, GemmFn, KeyForward, KeyLayerFn
+    B, V, R, S = 2, 2, 40, 32
+    rows = B * R * V * S
+    hid2 = torch.relu(syn.normal((rows, 1664), seed=91)).half().to(dev).requires_grad_(True)
+    W = (syn.normal((128, 1664), seed=92) * 0.05).to(dev).requires_grad_(True)
+    b = (syn.normal((128,), seed=93) * 0.1).to(dev).requires_grad_(True)
+    W2 = (syn.normal((128, 128), seed=94) * 0.1).to(dev).requires_grad_(True)
+    b2 = syn.normal((128,), seed=95).to(dev).requires_grad_(True)
+    c1 = syn.normal((rows, 128), seed=96).to(dev)
+    c2 = syn.normal((rows, 128), seed=97).to(dev)
+    kf = KeyForward(W, b)
+    kf.W16 = W.detach().half()
+    kf.kh = torch.relu(hid2.detach().float() @ W.detach().t() + b.detach()).half()
+    assert 0.2 < float((kf.kh > 0).float().mean()) < 0.8
+    bp = BackwardPass()
+    bp.s = torch.tensor(1.0, device=dev)                     # the gradients below are fp16 already: scale 1
+    kh = KeyLayerFn.apply(hid2, W, b, kf, (B, V, R, S), bp)
+    key2 = GemmFn.apply(kh, W2, b2, False, False, bp, True)
+    ((key2.float() * c1).sum() + (kh.float() * c2).sum()).backward()
+    assert bp.taken == [] and not bp.handed
+    dkh = c1.half().double() @ W2.detach().half().double() + c2.half().double()
+    ref = torch.where(kh.detach() > 0, dkh, torch.zeros_like(dkh)) @ W.detach().half().double()
+    got = hid2.grad.double()
+    assert float((got - ref).abs().max()) <= 2e-2 * max(1.0, float(ref.abs().max()))
 
 
 def test_local_hidden_backward_kernel(dev):

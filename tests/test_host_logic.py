@@ -50,6 +50,18 @@ def test_forward_requires_hip_device():
         m(inp, z=z, rel_pose=rel, val=True, flow=flow)
 
 
+def test_trunk_backward_target_backs_off_per_model():
+    """A step skipped by the finite-gradient guard quarters the fp16 trunk backward's target of the model its TrainStep
+    drives, and of no other model in the process."""
+    from coponerf_amd import CoPoNeRF
+    from coponerf_amd.train_step import TrainStep
+    first, second = CoPoNeRF.CoPoNeRF(n_view=2), CoPoNeRF.CoPoNeRF(n_view=2)
+    assert first.encoder.trunk_bwd.target == 4.0 and second.encoder.trunk_bwd.target == 4.0
+    TrainStep(first)._adapt_grad_scale(False)
+    assert first.encoder.trunk_bwd.target == 1.0
+    assert second.encoder.trunk_bwd.target == 4.0
+
+
 def test_pending_host_tensor_waits_at_first_use_of_values():
     """render.PendingHostTensor: `.cpu()` / metadata do not wait for the copy event, the first value access does, once."""
     from coponerf_amd.render import PendingHostTensor

@@ -1,6 +1,6 @@
 import torch, sys
 sys.path.insert(0, '/root/repo')
-from coponerf_amd import synthetic as syn, getz
+from coponerf_amd import synthetic as syn
 from tests import step_case as sc
 from tests.helpers import to_device
 from coponerf_amd import CoPoNeRF
@@ -13,7 +13,7 @@ fx = sc.fixture("step_r4096.npz")
 inp, gt = sc.inputs(4096)
 inp, gt = to_device(inp, dev), gt.to(dev)
 for mode in (True, False):
-    getz.F16_TRUNK_BACKWARD = mode
+    m.encoder.trunk_bwd.enabled = mode
     for it in range(5):
         m.zero_grad(set_to_none=True)
         out = m(inp, val=False)

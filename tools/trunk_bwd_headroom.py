@@ -1,5 +1,5 @@
 import torch, json
-from coponerf_amd import CoPoNeRF, synthetic as syn, getz
+from coponerf_amd import CoPoNeRF, synthetic as syn
 from coponerf_amd.train_step import TrainStep
 dev = torch.device("cuda:0")
 model = CoPoNeRF.CoPoNeRF(n_view=2)
@@ -12,10 +12,10 @@ inp = mv(inp)
 step = TrainStep(model, lr=1e-4)
 gt = inp["query"]["rgb"]
 for it in range(6):
-    getz.F16_BWD_TRACE = []
+    model.encoder.trunk_bwd.trace = []
     step(inp, gt)
     torch.cuda.synchronize()
-    tr = getz.F16_BWD_TRACE
+    tr = model.encoder.trunk_bwd.trace
     mx = max(float(t[1]) for t in tr if t[1] is not None), max(float(t[2]) for t in tr if t[2] is not None)
     print(it, len(tr), "max dx16 %.1f max dw16 %.1f" % mx)
 for t in tr:
