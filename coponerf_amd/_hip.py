@@ -37,6 +37,10 @@ SIGNATURES: Dict[str, List] = {
     "cpn_node_features_f32": [_P, _P, _P, _I, _I, _I, _P, _P],
     "cpn_encode_hidden_f32": [_P, _P, _I, _I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P],
     "cpn_attend_hidden_f32": [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P],
+    "cpn_logit_guard": [_P, _I, _I, _I, _I, _I, _I, _P, _I, _P],
+    "cpn_select_rays": [_P, _I, _F, _P, _P, _P],
+    "cpn_encode_hidden_f32_rays": [_P, _P, _I, _I, _P, _P, _P, _P, _I, _I, _I, _I, _P, _I, _I, _P, _P],
+    "cpn_attend_hidden_f32_rays": [_P, _P, _P, _I, _I, _I, _I, _P, _I, _I, _P, _P, _P],
     "cpn_linear_f32": [_P, _I, _P, _I, _P, _P, _I, _P, _I, _I, _I, _I, _I, _I, _P],
     "cpn_lightfield_decode": [_P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P],
     "cpn_ray_outputs": [_P, _P, _P, ctypes.c_longlong, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P],
@@ -95,7 +99,7 @@ CAM_TQ, CAM_M, CAM_AOWN, CAM_AOTH, CAM_KQ, CAM_KC, CAM_KO, CAM_KN = 0, 16, 32, 4
 TAB_LD = 832
 RAYC_STRIDE = 64
 LIGHTFIELD_PACK_FLOATS = 128 * 32 + 128 + 3 * (128 * 416 + 128 + 2 * (128 * 128 + 128)) + 16 * 128 + 16
-ABI_VERSION = 10
+ABI_VERSION = 11
 ADAM_SEG_BYTES = 48
 
 

@@ -22,6 +22,7 @@ UNITS = [
     ("encode.hip", []),
     ("encode_fused.hip", []),
     ("encode_f32.hip", []),
+    ("guard.hip", []),
     ("local_units.hip", []),
     ("encode_bwd.hip", []),
     ("gemm_f16.hip", []),

@@ -103,9 +103,13 @@ struct BatchLds {
 // run as  commit(n + 1), resolve(n + 2), fetch(n + 3)  while the owners multiply batch n: no request is waited for in the
 // trip that made it.  (One batch at a time, coordinates -> taps -> texels was a chain of two memory latencies per batch, and
 // with the contraction on the MFMA the producer, not the owners, set the pace: 6.5 us per batch.)
+// LIST: local ray t of the launch is rays[ray0 + t] (precision = "auto": the flagged rays only), else ray0 + t; a listed ray
+// outside [0, nraytot) resolves to dead rows.
+template <bool LIST>
 struct Producer {
     const float* __restrict__ map3; const float* __restrict__ pixel_val; const float* __restrict__ sec_grid; const float* __restrict__ pe6;
     int H, W, V, R, S, ray0; long long nrows2; NodeGrid ng; unsigned npi; int l;
+    const int* __restrict__ rays; long long nraytot;
     // fetched
     f32x2 gc; float p0, p1, p2; long long frow; int fimg; bool fown, flive;
     // resolved
@@ -121,7 +125,11 @@ struct Producer {
             const int T = V * S;
             const int t = (int)(row / T);
             const int rem = (int)(row - (long long)t * T), vv = rem / S, s = rem - vv * S;
-            const long long ray = (long long)ray0 + t;
+            long long ray = (long long)ray0 + t;
+            if constexpr (LIST) {
+                ray = rays[ray0 + t];
+                if (ray < 0 || ray >= nraytot) { flive = false; ray = 0; }
+            }
             const int bb = (int)(ray / R), r = (int)(ray - (long long)bb * R);
             const size_t sidx = (((size_t)(bb * V + vv)) * R + r) * S + s;
             fown = j == 0;
@@ -183,10 +191,11 @@ constexpr int ETILES = ECH / 16;         // 26
 constexpr int WLD = 432;                 // LDS row stride of the weight block in floats (= 16 mod 32: the four k groups of an
                                          // A-operand read fall on disjoint bank halves)
 constexpr int EF32_LDS = KX * WLD * 4 + 2 * (int)sizeof(BatchLds);
+template <bool LIST>
 __global__ __launch_bounds__(64 * EWAVES, 1) void encode_hidden_f32_kernel(
     const float* __restrict__ tab, const float* __restrict__ map3, int H, int W, const float* __restrict__ pixel_val,
     const float* __restrict__ sec_grid, const float* __restrict__ pe6, const float* __restrict__ w80t, int V, int R, int S,
-    int ray0, long long nrows2, long long nbatches, __half* __restrict__ hs) {
+    int ray0, long long nrows2, long long nbatches, __half* __restrict__ hs, const int* __restrict__ rays, long long nraytot) {
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     float* const wl = reinterpret_cast<float*>(smem_raw);               // [k][WLD]: this workgroup's half of the K = 68 block
     BatchLds* const lds = reinterpret_cast<BatchLds*>(smem_raw + KX * WLD * 4);
@@ -204,7 +213,7 @@ __global__ __launch_bounds__(64 * EWAVES, 1) void encode_hidden_f32_kernel(
         wl[k * WLD + c] = w80t[(size_t)k * 832 + half * ECH + c];
     }
     if (b_lo >= b_hi) return;
-    Producer P{map3, pixel_val, sec_grid, pe6, H, W, V, R, S, ray0, nrows2, ng, npi, lane};
+    Producer<LIST> P{map3, pixel_val, sec_grid, pe6, H, W, V, R, S, ray0, nrows2, ng, npi, lane, rays, nraytot};
     if (producer) {
         P.fetch(b_lo);
         P.resolve();
@@ -299,10 +308,13 @@ __device__ __forceinline__ float wave_sum_f2(float v) {
     return v;
 }
 
-// one workgroup per ray: logits from (rows,128) fp32 operands, softmax over the V*S rows, hbar = sum_rows w (hi + lo)
+// one workgroup per ray: logits from (rows,128) fp32 operands, softmax over the V*S rows, hbar = sum_rows w (hi + lo);
+// LIST: the workgroup's ray is rays[ray0 + blockIdx.x] (its at_wt rows are skipped if that lies outside [0, nraytot))
+template <bool LIST>
 __global__ __launch_bounds__(256) void attend_hidden_f32_kernel(const float* __restrict__ qa, const float* __restrict__ qb,
                                                                 const __half* __restrict__ hs, int V, int R, int S, int ray0,
-                                                                float* __restrict__ hbar, float* __restrict__ at_wt) {
+                                                                float* __restrict__ hbar, float* __restrict__ at_wt,
+                                                                const int* __restrict__ rays, long long nraytot) {
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     float* wts = reinterpret_cast<float*>(smem_raw);
     float* red = wts + V * S;
@@ -343,7 +355,12 @@ __global__ __launch_bounds__(256) void attend_hidden_f32_kernel(const float* __r
         const float w = wts[row] * inv;
         wts[row] = w;
         if (at_wt) {
-            const unsigned ray = (unsigned)ray0 + (unsigned)lray;
+            unsigned ray = (unsigned)ray0 + (unsigned)lray;
+            if constexpr (LIST) {
+                const int lr = rays[ray0 + lray];
+                if (lr < 0 || lr >= nraytot) continue;
+                ray = (unsigned)lr;
+            }
             const int b = (int)(ray / (unsigned)R), r = (int)(ray % (unsigned)R);
             const int v = row / S, s = row - v * S;
             at_wt[(((size_t)(b * V + v)) * R + r) * S + s] = w;
@@ -384,13 +401,17 @@ extern "C" int cpn_node_features_f32(const float* map0, const float* map1, const
     return 0;
 }
 
-extern "C" int cpn_encode_hidden_f32(const float* tab, const float* map3, int H, int W, const float* pixel_val, const float* sec_grid,
-                                     const float* pe6, const float* w80t, int B, int V, int R, int S, int ray0, int nrays,
-                                     uint16_t* hs, void* stream) {
-    CPN_REQUIRE(tab && map3 && pixel_val && sec_grid && pe6 && w80t && hs, CPN_E_ARG, "cpn_encode_hidden_f32: null pointer");
+namespace {
+
+template <bool LIST>
+int encode_hidden_f32(const float* tab, const float* map3, int H, int W, const float* pixel_val, const float* sec_grid,
+                      const float* pe6, const float* w80t, int B, int V, int R, int S, const int* rays, int ray0, int nrays,
+                      uint16_t* hs, void* stream) {
+    CPN_REQUIRE(tab && map3 && pixel_val && sec_grid && pe6 && w80t && hs && (!LIST || rays), CPN_E_ARG,
+                "cpn_encode_hidden_f32: null pointer");
     CPN_REQUIRE(B > 0 && V == 2 && R > 0 && S > 0 && H >= 16 && W >= 16 && (H % 16) == 0 && (W % 16) == 0, CPN_E_SHAPE,
                 "cpn_encode_hidden_f32: need V==2 and H,W multiples of 16 (got H=%d W=%d V=%d)", H, W, V);
-    CPN_REQUIRE(ray0 >= 0 && nrays > 0 && (long long)ray0 + nrays <= (long long)B * R, CPN_E_ARG,
+    CPN_REQUIRE(ray0 >= 0 && nrays > 0 && (LIST || (long long)ray0 + nrays <= (long long)B * R), CPN_E_ARG,
                 "cpn_encode_hidden_f32: ray range [%d,%d) outside B*R=%lld", ray0, ray0 + nrays, (long long)B * R);
     const NodeGrid ng{W >> 1, H >> 1};
     CPN_REQUIRE((long long)B * V * ng.nodes_per_image() * TABF * 4 < (1LL << 32) && (long long)B * V * H * W * 64 < (1LL << 32), CPN_E_SHAPE,
@@ -401,7 +422,7 @@ extern "C" int cpn_encode_hidden_f32(const float* tab, const float* map3, int H,
     const long long nbatches = (nrows2 + EB - 1) / EB;
     static bool attr_set = false;
     if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute((const void*)encode_hidden_f32_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, EF32_LDS);
+        hipError_t e = hipFuncSetAttribute((const void*)encode_hidden_f32_kernel<LIST>, hipFuncAttributeMaxDynamicSharedMemorySize, EF32_LDS);
         if (e != hipSuccess) {
             cpn_set_error("cpn_encode_hidden_f32: cannot reserve %d B of LDS: %s", EF32_LDS, hipGetErrorString(e));
             return (int)e;
@@ -411,23 +432,48 @@ extern "C" int cpn_encode_hidden_f32(const float* tab, const float* map3, int H,
     const int num_cu = cpn_stream_cus(stream);
     // workgroups 2p, 2p + 1 = the two channel halves of batch range p
     const unsigned grid = 2u * (unsigned)std::min<long long>(std::max(1, num_cu / 2), nbatches);
-    hipLaunchKernelGGL(encode_hidden_f32_kernel, dim3(grid), dim3(64 * EWAVES), EF32_LDS, (hipStream_t)stream, tab, map3, H, W, pixel_val,
-                       sec_grid, pe6, w80t, V, R, S, ray0, nrows2, nbatches, (__half*)hs);
+    hipLaunchKernelGGL(encode_hidden_f32_kernel<LIST>, dim3(grid), dim3(64 * EWAVES), EF32_LDS, (hipStream_t)stream, tab, map3, H, W,
+                       pixel_val, sec_grid, pe6, w80t, V, R, S, ray0, nrows2, nbatches, (__half*)hs, rays, (long long)B * R);
     CPN_LAUNCH_CHECK("cpn_encode_hidden_f32");
     return 0;
 }
 
-extern "C" int cpn_attend_hidden_f32(const float* qa, const float* qb, const uint16_t* hs, int B, int V, int R, int S, int ray0,
-                                     int nrays, float* hbar, float* at_wt, void* stream) {
-    CPN_REQUIRE(qa && qb && hs && hbar, CPN_E_ARG, "cpn_attend_hidden_f32: null pointer");
+template <bool LIST>
+int attend_hidden_f32(const float* qa, const float* qb, const uint16_t* hs, int B, int V, int R, int S, const int* rays, int ray0,
+                      int nrays, float* hbar, float* at_wt, void* stream) {
+    CPN_REQUIRE(qa && qb && hs && hbar && (!LIST || rays), CPN_E_ARG, "cpn_attend_hidden_f32: null pointer");
     CPN_REQUIRE(B > 0 && V == 2 && R > 0 && S > 0 && V * S <= 4096, CPN_E_SHAPE, "cpn_attend_hidden_f32: bad shape");
-    CPN_REQUIRE(ray0 >= 0 && nrays > 0 && (long long)ray0 + nrays <= (long long)B * R, CPN_E_ARG,
+    CPN_REQUIRE(ray0 >= 0 && nrays > 0 && (LIST || (long long)ray0 + nrays <= (long long)B * R), CPN_E_ARG,
                 "cpn_attend_hidden_f32: ray range outside B*R");
     CPN_REQUIRE(((uintptr_t)qa % 16) == 0 && ((uintptr_t)qb % 16) == 0 && ((uintptr_t)hs % 16) == 0 && ((uintptr_t)hbar % 16) == 0,
                 CPN_E_ARG, "cpn_attend_hidden_f32: operands must be 16-byte aligned");
     const size_t lds = (size_t)(V * S + 8) * sizeof(float);
-    hipLaunchKernelGGL(attend_hidden_f32_kernel, dim3(nrays), dim3(256), lds, (hipStream_t)stream, qa, qb, (const __half*)hs, V, R, S,
-                       ray0, hbar, at_wt);
+    hipLaunchKernelGGL(attend_hidden_f32_kernel<LIST>, dim3(nrays), dim3(256), lds, (hipStream_t)stream, qa, qb, (const __half*)hs, V,
+                       R, S, ray0, hbar, at_wt, rays, (long long)B * R);
     CPN_LAUNCH_CHECK("cpn_attend_hidden_f32");
     return 0;
+}
+
+}  // namespace
+
+extern "C" int cpn_encode_hidden_f32(const float* tab, const float* map3, int H, int W, const float* pixel_val, const float* sec_grid,
+                                     const float* pe6, const float* w80t, int B, int V, int R, int S, int ray0, int nrays,
+                                     uint16_t* hs, void* stream) {
+    return encode_hidden_f32<false>(tab, map3, H, W, pixel_val, sec_grid, pe6, w80t, B, V, R, S, nullptr, ray0, nrays, hs, stream);
+}
+
+extern "C" int cpn_encode_hidden_f32_rays(const float* tab, const float* map3, int H, int W, const float* pixel_val,
+                                          const float* sec_grid, const float* pe6, const float* w80t, int B, int V, int R, int S,
+                                          const int* rays, int ray0, int nrays, uint16_t* hs, void* stream) {
+    return encode_hidden_f32<true>(tab, map3, H, W, pixel_val, sec_grid, pe6, w80t, B, V, R, S, rays, ray0, nrays, hs, stream);
+}
+
+extern "C" int cpn_attend_hidden_f32(const float* qa, const float* qb, const uint16_t* hs, int B, int V, int R, int S, int ray0,
+                                     int nrays, float* hbar, float* at_wt, void* stream) {
+    return attend_hidden_f32<false>(qa, qb, hs, B, V, R, S, nullptr, ray0, nrays, hbar, at_wt, stream);
+}
+
+extern "C" int cpn_attend_hidden_f32_rays(const float* qa, const float* qb, const uint16_t* hs, int B, int V, int R, int S,
+                                          const int* rays, int ray0, int nrays, float* hbar, float* at_wt, void* stream) {
+    return attend_hidden_f32<true>(qa, qb, hs, B, V, R, S, rays, ray0, nrays, hbar, at_wt, stream);
 }

@@ -373,6 +373,10 @@ class RenderEngine:
     FREE_SHARE = 0.5                # ... and at most this share of the memory that is free when the workspace is sized
     MAX_AUTO_CHUNK = 65536
     FEW_ROWS = 4096                 # per-ray GEMMs of at most this many rows take the few-row kernel (cpn_gemm_f16_fewrows: 17 vs 35 us at 3 641)
+    # precision="auto": default guard threshold on the score sum_i w_i (1 - w_i) |l_i|: half the smallest score of a ray whose
+    # fp16 rgb was off by > 5e-4 or a weight by > 1e-3 in the calibration sweep (tools/auto_calibrate.py)
+    AUTO_THRESHOLD = 0.5062
+    PRECISIONS = ("f16", "f32", "auto")
 
     def __init__(self, chunk_rays: int = 0, lanes: int = 1):
         # ONE per-sample formulation (round 6; rounds 2-5 kept their predecessors as switchable modes - gather + GEMM first layer,
@@ -398,6 +402,13 @@ class RenderEngine:
         # test suite bounds |rgb_f16 - rgb_f32| with it and bench.py reports it as `rays_per_s_f32` beside the headline.
         self.precision = os.environ.get("COPONERF_PRECISION", "f16")
         self.f32_chunk_rays = 16384
+        # precision="auto" (COPONERF_PRECISION=auto; inference only, like "f32"): the fp16 default plus a per-ray logit guard
+        # (csrc/guard.hip) - rays whose score sum_i w_i (1 - w_i) |l_i| exceeds auto_threshold are rendered again in the reference's
+        # arithmetic and merged in before the decoder (_render_body).  inf: no ray; negative: every ray.  One host wait per call
+        # (the flagged count).  last_exact_rays = (flagged, total) of the last auto call.
+        self.auto_threshold = self.AUTO_THRESHOLD
+        self.last_exact_rays: Optional[Tuple[int, int]] = None
+        self._guard_host: Optional[torch.Tensor] = None
         self._w32key = None
         self._w32: Dict[str, torch.Tensor] = {}
         self._t32 = None
@@ -495,12 +506,22 @@ class RenderEngine:
         loc16 = torch.cat((l8[..., 0:3], torch.zeros_like(l8[..., 0:3]), c9[..., 0:3], l8[..., 3:7], c9[..., 6:9]), dim=-1)
         return loc16.reshape(B * R * V * S, 16).contiguous()
 
-    def _per_sample_f32(self, pz, B, R, S, H, W, pixel_val, sec_grid, pe6, loc8, coords9, zl, at_wt, s) -> None:
+    def _loc16_rays(self, loc8, coords9, B, R, S, rays):
+        # _loc16's rows of the listed rays only (rays: int64 device indices b * R + r), in list order
+        l8 = loc8.view(B, V, R, S, 8).permute(0, 2, 1, 3, 4).reshape(B * R, V, S, 8)[rays]             # (n,V,S,8)
+        c9 = coords9.view(B, V, R, 9).permute(0, 2, 1, 3).reshape(B * R, V, 1, 9)[rays].expand(-1, V, S, 9)
+        loc16 = torch.cat((l8[..., 0:3], torch.zeros_like(l8[..., 0:3]), c9[..., 0:3], l8[..., 3:7], c9[..., 6:9]), dim=-1)
+        return loc16.reshape(-1, 16).contiguous()
+
+    def _per_sample_f32(self, pz, B, R, S, H, W, pixel_val, sec_grid, pe6, loc8, coords9, zl, at_wt, s,
+                        rays: Optional[torch.Tensor] = None, nsel: int = 0) -> None:
         """zl, at_wt of a call in the reference's arithmetic, in the formulation of the fp16 default (csrc/encode_f32.hip, round 6;
         round 5 ran this mode layer by layer in the reference's order at 78 k rays/s - tools/experiments/r6_pruned/):
         fp32 node tables, the first layer as 4 fp32 table taps + an fp32 K = 68 block, hid as fp16 (hi, lo) pairs, the folded key
         layer on cpn_gemm_f16 against (hi, lo) weights (exact products, fp32 accumulation), both attention rounds on the
-        hidden activations, the folded value projection per ray in exact fp32."""
+        hidden activations, the folded value projection per ray in exact fp32.
+        rays (int32 device list, precision="auto"), nsel: only the first nsel listed rays - the per-sample kernels take their
+        _rays forms, the per-ray rows are compact in list order and land in zl by one index_copy_; at_wt is written in place."""
         params, z = pz
         w = self._weights_f32(params)
         dev = zl.device
@@ -516,10 +537,36 @@ class RenderEngine:
             self._lin_f32(s, feat, 768, w["tab.w"], None, tab, _hip.TAB_LD, nodes, _hip.TAB_LD, 768, False)
             del feat
             self._t32 = (mk, tuple(z), tab, maps[3])
+            if rays is not None:
+                # a later auto call on another call lane reads the tables: it waits for this build (below)
+                self._t32_ready = torch.cuda.Event()
+                self._t32_ready.record(torch.cuda.current_stream(dev))
         tab, map3 = self._t32[2], self._t32[3]
         T = V * S
-        nray = B * R
-        loc16 = self._loc16(loc8, coords9, B, R, S)
+        if rays is None:
+            nray = B * R
+            loc16 = self._loc16(loc8, coords9, B, R, S)
+            enc = lambda ray0, n, hs: call(
+                "cpn_encode_hidden_f32", tab.data_ptr(), map3.data_ptr(), H, W, pixel_val.data_ptr(), sec_grid.data_ptr(),
+                pe6.data_ptr(), w["k80t"].data_ptr(), B, V, R, S, ray0, n, hs.data_ptr(), s)
+            att = lambda qa, ray0, n, hbar, wt: call(
+                "cpn_attend_hidden_f32", qa.data_ptr(), ce.data_ptr(), hs.data_ptr(), B, V, R, S, ray0, n, hbar.data_ptr(), wt, s)
+        else:
+            ev = self.__dict__.get("_t32_ready")
+            cur = torch.cuda.current_stream(dev)
+            if ev is not None:
+                cur.wait_event(ev)
+            tab.record_stream(cur)
+            map3.record_stream(cur)
+            nray = nsel
+            loc16 = self._loc16_rays(loc8, coords9, B, R, S, rays[:nsel].long())
+            zc = self._buf("f32t.zc", (nsel, 416), f32, dev)
+            enc = lambda ray0, n, hs: call(
+                "cpn_encode_hidden_f32_rays", tab.data_ptr(), map3.data_ptr(), H, W, pixel_val.data_ptr(), sec_grid.data_ptr(),
+                pe6.data_ptr(), w["k80t"].data_ptr(), B, V, R, S, rays.data_ptr(), ray0, n, hs.data_ptr(), s)
+            att = lambda qa, ray0, n, hbar, wt: call(
+                "cpn_attend_hidden_f32_rays", qa.data_ptr(), ce.data_ptr(), hs.data_ptr(), B, V, R, S, rays.data_ptr(), ray0, n,
+                hbar.data_ptr(), wt, s)
         C = min(self.f32_chunk_rays, nray)
         lin = lambda *a, **k: self._lin_f32(s, *a, **k)
         t = lambda name, shape, dt=f32: self._buf("f32t." + name, shape, dt, dev)
@@ -527,8 +574,7 @@ class RenderEngine:
             n = min(C, nray - ray0)
             rows = n * T
             hs = t("hs", (rows, 3328), f16)
-            call("cpn_encode_hidden_f32", tab.data_ptr(), map3.data_ptr(), H, W, pixel_val.data_ptr(), sec_grid.data_ptr(),
-                 pe6.data_ptr(), w["k80t"].data_ptr(), B, V, R, S, ray0, n, hs.data_ptr(), s)
+            enc(ray0, n, hs)
             kh, key2 = t("kh", (rows, 128)), t("key2", (rows, 128))
             call("cpn_gemm_f16", hs.data_ptr(), 3328, w["keyf.w1"].data_ptr(), 3328, w["keyf.b"].data_ptr(), kh.data_ptr(), 128,
                  rows, 128, 3328, 0, 1, s)
@@ -540,8 +586,7 @@ class RenderEngine:
             lin(lc, 16, w["qe.w"], w["qe.b"], hq, 128, rows, 128, 16, True)
             lin(hq, 128, w["qe2.w"], w["qe2.b"], ce, 128, rows, 128, 128, False)
             hbar, z1, ze, aq = t("hbar", (n, 1664)), t("z1", (n, 416)), t("ze", (n, 128)), t("aq", (n, 128))
-            call("cpn_attend_hidden_f32", key2.data_ptr(), ce.data_ptr(), hs.data_ptr(), B, V, R, S, ray0, n, hbar.data_ptr(),
-                 at_wt.data_ptr(), s)
+            att(key2, ray0, n, hbar, at_wt.data_ptr())
             lin(hbar, 1664, w["valf.w"], w["valf.b"], z1, 416, n, 416, 1664, False)
             lin(z1, 416, w["el.w"], w["el.b"], ze, 128, n, 128, 416, False)
             lin(ze, 128, w["qr.w_z"], None, aq, 128, n, 128, 128, False)
@@ -549,11 +594,13 @@ class RenderEngine:
             q2 = key2                                                                        # (the key is spent)
             lin(lc, 16, w["qr.w_l"], w["qr.b"], hq, 128, rows, 128, 16, True, res=aq_rows)
             lin(hq, 128, w["qr2.w"], w["qr2.b"], q2, 128, rows, 128, 128, False)
-            call("cpn_attend_hidden_f32", q2.data_ptr(), ce.data_ptr(), hs.data_ptr(), B, V, R, S, ray0, n, hbar.data_ptr(), 0, s)
+            att(q2, ray0, n, hbar, 0)
             zs = t("zs", (n, 416))
             lin(hbar, 1664, w["valf.w"], w["valf.b"], zs, 416, n, 416, 1664, False)
             # the round-1 vector sits in both view slots when the views are summed (CoPoNeRF.py:481-485): + V * z1
-            torch.add(zs[:n], z1[:n], alpha=float(V), out=zl[ray0:ray0 + n])
+            torch.add(zs[:n], z1[:n], alpha=float(V), out=(zl if rays is None else zc)[ray0:ray0 + n])
+        if rays is not None:
+            zl.index_copy_(0, rays[:nsel].long(), zc)
 
     def invalidate(self) -> None:
         """Drop the packed-weight / feature-map caches.  The caches are keyed on tensor identity and `_version`;
@@ -575,7 +622,7 @@ class RenderEngine:
         # caches, streams and workspace are derived state: a copied model gets a fresh engine with the same settings
         new = RenderEngine(self.chunk_rays, self.lanes)
         new.grad_scale_target, new.call_lanes, new.lazy_pixel_val = self.grad_scale_target, self.call_lanes, self.lazy_pixel_val
-        new.precision, new.f32_chunk_rays = self.precision, self.f32_chunk_rays
+        new.precision, new.f32_chunk_rays, new.auto_threshold = self.precision, self.f32_chunk_rays, self.auto_threshold
         return new
 
     @staticmethod
@@ -920,7 +967,8 @@ class RenderEngine:
     def render_train(self, params: Dict[str, torch.Tensor], ctx_c2w, ctx_K, qry_c2w, qry_K, uv,
                      z: Sequence[torch.Tensor], rel_pose, val: bool, S: int, H: int, W: int) -> Dict[str, torch.Tensor]:
         """Same forward kernels as render(), wrapped in autograd Functions (coponerf_amd/train_fns.py); all rays of
-        the call form one chunk (training uses <= 4096 rays per pair, /root/reference train.py:87)."""
+        the call form one chunk (training uses <= 4096 rays per pair, /root/reference train.py:87).  `precision` is not
+        consulted: "f32" and "auto" are inference-only modes, training always runs the fp16 formulation."""
         from .train_fns import (AttendHiddenFn, BackwardPass, EncodeFn, GemmFn, KeyForward, KeyLayerFn, LinearF32Fn,
                                 LocalHiddenFn)
         dev = uv.device
@@ -1042,7 +1090,8 @@ class RenderEngine:
         rgb (B,1,R,3), valid_mask (B,R,1), pixel_val (N,R,S,2), pt (N,R,S,3), at_wt (N,R,S),
         coords (N,R,9), z_local (B*R,416), Tq (B,V,4,4) (device copy of the host pose algebra); `pixel_val_cpu` is the
         pinned CPU copy (a PendingHostTensor while the copy stream may still be writing it); with `inp` and `flow` given,
-        `aux` = the per-ray auxiliary outputs (aux_outputs.ray_outputs).  debug=True adds sec_grid / rgb_raw.
+        `aux` = the per-ray auxiliary outputs (aux_outputs.ray_outputs).  debug=True adds sec_grid / rgb_raw (and, with
+        precision="auto", guard_score (B,R) fp32: each ray's logit-guard score).
 
         Consecutive calls are independent (a full-image render is 18 of them in the reference's callers, test.py:176-190),
         so they alternate over `call_lanes` HIP streams: the small per-ray kernels and the tails of the persistent
@@ -1059,8 +1108,8 @@ class RenderEngine:
         B, _, R, _ = uv.shape
         if z[0].shape[0] != B * V or len(z) != 4:
             raise ValueError("expected 4 latent maps with a leading dimension of B*2")
-        if self.precision not in ("f16", "f32"):
-            raise ValueError(f"RenderEngine.precision must be 'f16' or 'f32' (got {self.precision!r})")
+        if self.precision not in self.PRECISIONS:
+            raise ValueError(f"RenderEngine.precision must be 'f16', 'f32' or 'auto' (got {self.precision!r})")
         main = torch.cuda.current_stream()
         miss0 = self._misses
         w = self._weights(params)
@@ -1145,6 +1194,9 @@ class RenderEngine:
 
         nray_total = B * R
         zl = torch.empty(nray_total, 416, dtype=f32, device=dev)
+        auto = self.precision == "auto"
+        # precision="auto": every ray's guard score, written by the two cpn_logit_guard launches of its chunk
+        score = self._buf("guard.score", (nray_total,), f32, dev) if auto else None
         C = min(self.chunk_rays if self.chunk_rays > 0 else self._auto_chunk(S, dev, nray_total), nray_total)
         T = V * S                       # rows per ray for the attention stage
         GW = dict(self.GEMM_WEIGHTS, key_fold=(128, 1664, 1664), value_fold=(416, 1664, 1664))
@@ -1203,6 +1255,9 @@ class RenderEngine:
                 w["query_embed.b"].data_ptr(), 0, w["query_embed_2.w16"].data_ptr(), 128, w["query_embed_2.b"].data_ptr(),
                 w["key_map_2.w16"].data_ptr(), 128, w["key_map_2.b"].data_ptr(), 0, 0, 0, bf["khf"].data_ptr(), B, V, R, S,
                 ray0, n, 0, lvu.data_ptr(), bf["lg"].data_ptr(), s))
+            if auto:                    # guard score of round 1 (before round 2 overwrites lg)
+                timed("logit_guard:round1", 0.0, lambda: call(
+                    "cpn_logit_guard", bf["lg"].data_ptr(), B, V, R, S, ray0, n, score.data_ptr(), 0, s))
             # A1: joint softmax over the 2 x S samples of a ray + the weighted hidden sum, round 1  [:450-461]
             timed("attend_hidden:round1", 2.0 * n * T * 1664, lambda: call(
                 "cpn_attend_hidden", 0, 0, bf["lg"].data_ptr(), bf["hid"].data_ptr(), B, V, R, S, ray0, n,
@@ -1221,6 +1276,9 @@ class RenderEngine:
                 w["query_repeat_embed_2.b"].data_ptr(), w["query_embed_2.w16"].data_ptr(), 128, w["query_embed_2.b"].data_ptr(),
                 w["query_embed.w"].data_ptr(), 16, w["query_embed.b"].data_ptr(), 0, B, V, R, S, ray0, n, 0,
                 lvu.data_ptr(), bf["lg"].data_ptr(), s))
+            if auto:                    # ... max'ed with round 2's
+                timed("logit_guard:round2", 0.0, lambda: call(
+                    "cpn_logit_guard", bf["lg"].data_ptr(), B, V, R, S, ray0, n, score.data_ptr(), 1, s))
             # A2: round 2 of the attention  [:475-485]
             timed("attend_hidden:round2", 2.0 * n * T * 1664, lambda: call(
                 "cpn_attend_hidden", 0, 0, bf["lg"].data_ptr(), bf["hid"].data_ptr(), B, V, R, S, ray0, n,
@@ -1250,6 +1308,8 @@ class RenderEngine:
                 done = torch.cuda.Event()
                 done.record(self._lane_streams[lane])
                 main.wait_event(done)
+        if auto:
+            self._exact_rays(pre[8], score, B, R, S, H, W, pixel_val, sec_grid, pe6, loc8, coords9, zl, at_wt, s)
 
         # ---- light-field decoder phi over all rays (lightfield.py:131-167) + white background, exact fp32, one launch
         rgb = torch.empty(B, 1, R, 3, dtype=f32, device=dev)
@@ -1268,4 +1328,27 @@ class RenderEngine:
             out["aux"] = ray_outputs(inp, fp, at_wt, pt, up["rayc"], (uvc, uvs))
         if debug:
             out["sec_grid"], out["rgb_raw"] = sec_grid.clone(), rgb_raw
+            if auto:
+                out["guard_score"] = score.view(B, R).clone()
         return out
+
+    def _exact_rays(self, pz, score, B, R, S, H, W, pixel_val, sec_grid, pe6, loc8, coords9, zl, at_wt, s) -> None:
+        """precision="auto", after the fp16 chunks have joined: list the rays whose guard score exceeds auto_threshold
+        (cpn_select_rays), read their count on the host - the mode's ONE host wait per call - and render those rays again in
+        the reference's arithmetic (_per_sample_f32 over the list), overwriting their zl rows and at_wt entries before the
+        decoder runs.  The fp32 tables are built by the first call that flags a ray."""
+        nray = B * R
+        dev = zl.device
+        lst = self._buf("guard.list", (nray,), torch.int32, dev)
+        cnt = self._buf("guard.count", (1,), torch.int32, dev)
+        call("cpn_select_rays", score.data_ptr(), nray, float(self.auto_threshold), lst.data_ptr(), cnt.data_ptr(), s)
+        if self._guard_host is None:
+            self._guard_host = torch.empty(1, dtype=torch.int32, pin_memory=True)
+        self._guard_host.copy_(cnt, non_blocking=True)
+        copied = torch.cuda.Event()
+        copied.record()
+        copied.synchronize()
+        k = int(self._guard_host[0])
+        self.last_exact_rays = (k, nray)
+        if k > 0:
+            self._per_sample_f32(pz, B, R, S, H, W, pixel_val, sec_grid, pe6, loc8, coords9, zl, at_wt, s, rays=lst, nsel=k)

@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define CPN_ABI_VERSION 10
+#define CPN_ABI_VERSION 11
 
 #define CPN_E_ARG   (-1)   /* bad argument (null pointer, size, alignment) */
 #define CPN_E_SHAPE (-2)   /* shape not supported by the compiled tiles    */
@@ -254,6 +254,33 @@ int cpn_encode_hidden_f32(const float* tab, const float* map3, int H, int W, con
  * hidden activations hs (hi, lo pairs) -> hbar (nrays, 1664) fp32, at_wt (N,R,S) fp32 or NULL   (CoPoNeRF.py:450-461, 475-485) */
 int cpn_attend_hidden_f32(const float* qa, const float* qb, const uint16_t* hs, int B, int V, int R, int S, int ray0, int nrays,
                           float* hbar, float* at_wt, void* stream);
+
+/* ==== precision = "auto": a per-ray logit guard picks the rays the reference-arithmetic path re-renders (csrc/guard.hip) ====
+ * The fp16 default forms the attention logits from fp16 operands (relative error ~3e-4); a softmax weight is then off by
+ * ~w (1 - w) |l| 3e-4, which flat rays average away and sharp rays do not (CoPoNeRF.py:450-461, 475-485).  Under
+ * |dl_i| <= eps |l_i| both sum_i |dw_i| and max_i |dw_i| are bounded by 2 eps sum_i w_i (1 - w_i) |l_i|: that sum is the
+ * ray's score.                                                                                                              */
+
+/* score of every ray of a chunk from the logits cpn_local_units stored (the layout cpn_attend_hidden reads): l_i = lg_i / 11.31,
+ * w = softmax(l) formed exactly as cpn_attend_hidden forms it, score[b*R + r] = sum_i w_i (1 - w_i) |l_i| for the rays
+ * [ray0, ray0 + nrays);
+ * accumulate = 1: score = max(score, that) (round 2 after round 1)
+ *   logits (nrays*V*S) fp32   score (B*R) fp32                                                                          */
+int cpn_logit_guard(const float* logits, int B, int V, int R, int S, int ray0, int nrays, float* score, int accumulate,
+                    void* stream);
+
+/* indices of the rays with score > tau in ascending order (a deterministic scan, no atomics) and their count
+ *   score (nray) fp32   list (nray) int32: entries [0, count) written   count (1) int32                                */
+int cpn_select_rays(const float* score, int nray, float tau, int* list, int* count, void* stream);
+
+/* cpn_encode_hidden_f32 / cpn_attend_hidden_f32 over a LIST of rays: local ray t of the launch is rays[ray0 + t] instead of
+ * ray0 + t (rays (>= ray0 + nrays) int32, each in [0, B*R); entries outside are skipped).  hs and hbar rows are compact
+ * (local ray order); at_wt is written at the listed ray's own (n, r, s) position.  Same arithmetic, bit for bit.      */
+int cpn_encode_hidden_f32_rays(const float* tab, const float* map3, int H, int W, const float* pixel_val, const float* sec_grid,
+                               const float* pe6, const float* w80t, int B, int V, int R, int S, const int* rays, int ray0,
+                               int nrays, uint16_t* hs, void* stream);
+int cpn_attend_hidden_f32_rays(const float* qa, const float* qb, const uint16_t* hs, int B, int V, int R, int S,
+                               const int* rays, int ray0, int nrays, float* hbar, float* at_wt, void* stream);
 
 /* ==== training: backward of the two non-GEMM stages (plain GEMM gradients use hipBLASLt via torch.matmul) ==== */
 
