@@ -14,7 +14,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 
 import torch
 
-from . import _hip
+from . import _hip, render_f32
 from ._hip import call
 
 V = 2  # context views; the kernels are specialised for stereo pairs like the reference's released model
@@ -377,6 +377,9 @@ class RenderEngine:
     # fp16 rgb was off by > 5e-4 or a weight by > 1e-3 in the calibration sweep (tools/auto_calibrate.py)
     AUTO_THRESHOLD = 0.5062
     PRECISIONS = ("f16", "f32", "auto")
+    # what a copied engine keeps (__deepcopy__); caches, streams and workspace are derived state
+    SETTINGS = ("chunk_rays", "lanes", "grad_scale_target", "call_lanes", "lazy_pixel_val", "precision", "f32_chunk_rays",
+                "auto_threshold")
 
     def __init__(self, chunk_rays: int = 0, lanes: int = 1):
         # ONE per-sample formulation (round 6; rounds 2-5 kept their predecessors as switchable modes - gather + GEMM first layer,
@@ -397,7 +400,7 @@ class RenderEngine:
         self._lane_streams: List[torch.cuda.Stream] = []
         # precision="f32" (COPONERF_PRECISION=f32): the reference's arithmetic on this device in the SAME formulation - fp32 node
         # tables, fp32 blends, the first layer's K = 68 block and the 128-wide layers on the exact fp32 MFMA, hid as fp16 (hi, lo)
-        # pairs with exact products in the folded key layer (csrc/encode_f32.hip, _per_sample_f32).  ~5 x slower than the fp16
+        # pairs with exact products in the folded key layer (csrc/encode_f32.hip, render_f32.py).  ~5 x slower than the fp16
         # default; the path for models whose attention is sharp enough to leave the fp16 envelope (tests/test_gpu_range.py); the
         # test suite bounds |rgb_f16 - rgb_f32| with it and bench.py reports it as `rays_per_s_f32` beside the headline.
         self.precision = os.environ.get("COPONERF_PRECISION", "f16")
@@ -409,9 +412,8 @@ class RenderEngine:
         self.auto_threshold = self.AUTO_THRESHOLD
         self.last_exact_rays: Optional[Tuple[int, int]] = None
         self._guard_host: Optional[torch.Tensor] = None
-        self._w32key = None
-        self._w32: Dict[str, torch.Tensor] = {}
-        self._t32 = None
+        self._t32: Optional[Tuple[torch.Tensor, torch.Tensor]] = None     # the f32 path's node tables (_f32_inputs)
+        self._t32_ready: Optional[torch.cuda.Event] = None                 # ... recorded after their build
         self._wkey = None
         self._w: Dict[str, torch.Tensor] = {}
         self._mkey = None
@@ -427,6 +429,7 @@ class RenderEngine:
         self._prep_stream: Optional[torch.cuda.Stream] = None
         self._ws: Dict[str, torch.Tensor] = {}
         self._interval: Dict[Tuple[int, str], torch.Tensor] = {}
+        self._auto_chunk_memo: Optional[Tuple[Tuple, int]] = None     # (key, chunk) of the last _auto_chunk decision
         # optional per-kernel timing (bench.py): name -> list of (start_event, end_event, algorithmic_flops)
         self.profile: Optional[Dict[str, list]] = None
         self._copy_stream: Optional[torch.cuda.Stream] = None
@@ -437,6 +440,7 @@ class RenderEngine:
         # consecutive render() calls alternate over this many HIP streams (render() docstring); 1 = the caller's stream
         self.call_lanes = int(os.environ.get("COPONERF_CALL_LANES", "2"))
         self._call_streams: List[torch.cuda.Stream] = []
+        self._call_streams_given = False    # set_call_streams() installed the caller's streams
         self._call_idx = 0
         self._ws_prefix = ""            # workspace of the call lane in flight
         self._misses = 0                # cache rebuilds so far (a call that rebuilt something must wait for the caller's stream)
@@ -452,156 +456,6 @@ class RenderEngine:
             self._ws[name] = t
         return t[:n].view(*shape)
 
-    # ---- the reference-arithmetic mode (precision="f32") ---------------------------------------------------------
-    def _weights_f32(self, params: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
-        key = tuple((id(p), p.data_ptr(), p._version) for p in params.values())
-        if key == self._w32key:
-            return self._w32
-        f = lambda n, rows: params[n + ".weight"].detach().reshape(rows, -1).float().contiguous()
-        b = lambda n: params[n + ".bias"].detach().float().contiguous()
-        w = {}
-        w1 = f("query_encode_latent", 832)                                   # (832, 835)
-        w["qel.b"] = b("query_encode_latent")
-        for short, name, rows in (("qel2", "query_encode_latent_2", 416), ("val", "latent_value", 416), ("key", "key_map", 128),
-                                  ("key2", "key_map_2", 128), ("qe", "query_embed", 128), ("qe2", "query_embed_2", 128),
-                                  ("qr2", "query_repeat_embed_2", 128)):
-            w[short + ".w"], w[short + ".b"] = f(name, rows), b(name)
-        wr = f("query_repeat_embed", 128)                                    # (128, 144) = [encode_latent(z) 128 | local_coords 16]
-        w["qr.w_z"], w["qr.w_l"], w["qr.b"] = wr[:, :128].contiguous(), wr[:, 128:].contiguous(), b("query_repeat_embed")
-        w["el.w"], w["el.b"] = f("encode_latent", 128), b("encode_latent")
-        # ---- restructured form (csrc/encode_f32.hip): table projection, K = 68 block (k-major, bias as its last row), the folded
-        #      key / value matrices (products in float64, one rounding to fp32) and the key matrix as an fp16 (hi, lo) pair
-        w["tab.w"] = w1[:, :768].contiguous()                                                # (832, 768)
-        w["k80t"] = torch.cat((w1[:, 768:835].t(), w["qel.b"][None]), 0).contiguous()        # (68, 832)
-        W2d, b2d = w["qel2.w"].double(), w["qel2.b"].double()
-
-        def fold(short, n_out):
-            Wx = w[short + ".w"].double()
-            Wf = torch.cat((Wx[:, :416] @ W2d, Wx[:, 416:] @ W2d), dim=1)
-            cf = Wx[:, :416] @ b2d + Wx[:, 416:] @ b2d + w[short + ".b"].double()
-            return Wf.float().contiguous(), cf.float().contiguous()
-
-        wk, w["keyf.b"] = fold("key", 128)
-        w["valf.w"], w["valf.b"] = fold("val", 416)
-        hi = wk.half()
-        lo = (wk - hi.float()).half()
-        w["keyf.w1"] = torch.cat((hi, hi), 1).contiguous()                                   # against [hid_hi | hid_lo]
-        w["keyf.w2"] = lo.contiguous()                                                       # against hid_hi
-        w["zero128"] = torch.zeros(128, dtype=torch.float32, device=wk.device)
-        self._w32, self._w32key = w, key
-        return w
-
-    def _lin_f32(self, s, x, ldx, wt, bias, y, ldy, m, n, k, relu, res=None):
-        for n0 in range(0, n, 128):
-            nb = min(128, n - n0)
-            call("cpn_linear_f32", x.data_ptr(), ldx, wt.data_ptr() + n0 * wt.shape[1] * 4, wt.shape[1],
-                 0 if bias is None else bias.data_ptr() + n0 * 4, 0 if res is None else res.data_ptr() + n0 * 4,
-                 0 if res is None else res.shape[1], y.data_ptr() + n0 * 4, ldy, m, nb, k, 0, int(relu), s)
-
-    def _loc16(self, loc8, coords9, B, R, S):
-        # local_coords (16 channels, CoPoNeRF.py:411-445) of every sample in row order: [ctx ray dir 3 | 0 0 0 | query dir 3 |
-        # tanh(depth x {1, .1, .01, .001}) 4 | query origin 3] from the per-sample / per-ray pieces cpn_sample_geometry wrote
-        l8 = loc8.view(B, V, R, S, 8).permute(0, 2, 1, 3, 4)                  # (B,R,V,S,8)
-        c9 = coords9.view(B, V, R, 1, 9).permute(0, 2, 1, 3, 4).expand(B, R, V, S, 9)
-        loc16 = torch.cat((l8[..., 0:3], torch.zeros_like(l8[..., 0:3]), c9[..., 0:3], l8[..., 3:7], c9[..., 6:9]), dim=-1)
-        return loc16.reshape(B * R * V * S, 16).contiguous()
-
-    def _loc16_rays(self, loc8, coords9, B, R, S, rays):
-        # _loc16's rows of the listed rays only (rays: int64 device indices b * R + r), in list order
-        l8 = loc8.view(B, V, R, S, 8).permute(0, 2, 1, 3, 4).reshape(B * R, V, S, 8)[rays]             # (n,V,S,8)
-        c9 = coords9.view(B, V, R, 9).permute(0, 2, 1, 3).reshape(B * R, V, 1, 9)[rays].expand(-1, V, S, 9)
-        loc16 = torch.cat((l8[..., 0:3], torch.zeros_like(l8[..., 0:3]), c9[..., 0:3], l8[..., 3:7], c9[..., 6:9]), dim=-1)
-        return loc16.reshape(-1, 16).contiguous()
-
-    def _per_sample_f32(self, pz, B, R, S, H, W, pixel_val, sec_grid, pe6, loc8, coords9, zl, at_wt, s,
-                        rays: Optional[torch.Tensor] = None, nsel: int = 0) -> None:
-        """zl, at_wt of a call in the reference's arithmetic, in the formulation of the fp16 default (csrc/encode_f32.hip, round 6;
-        round 5 ran this mode layer by layer in the reference's order at 78 k rays/s - tools/experiments/r6_pruned/):
-        fp32 node tables, the first layer as 4 fp32 table taps + an fp32 K = 68 block, hid as fp16 (hi, lo) pairs, the folded key
-        layer on cpn_gemm_f16 against (hi, lo) weights (exact products, fp32 accumulation), both attention rounds on the
-        hidden activations, the folded value projection per ray in exact fp32.
-        rays (int32 device list, precision="auto"), nsel: only the first nsel listed rays - the per-sample kernels take their
-        _rays forms, the per-ray rows are compact in list order and land in zl by one index_copy_; at_wt is written in place."""
-        params, z = pz
-        w = self._weights_f32(params)
-        dev = zl.device
-        f32, f16 = torch.float32, torch.float16
-        mk = tuple((id(t), t._version) for t in z) + (self._w32key,)
-        if self._t32 is None or self._t32[0] != mk or any(a is not b for a, b in zip(self._t32[1], z)):
-            maps = [t.detach().float().permute(0, 2, 3, 1).contiguous() for t in z]                          # NHWC fp32
-            nimg = maps[0].shape[0]
-            nodes = nimg * int(_hip.lib().cpn_encode_table_nodes(H, W))
-            feat = torch.empty(nodes, 768, dtype=f32, device=dev)
-            call("cpn_node_features_f32", maps[0].data_ptr(), maps[1].data_ptr(), maps[2].data_ptr(), H, W, nimg, feat.data_ptr(), s)
-            tab = torch.empty(nodes, _hip.TAB_LD, dtype=f32, device=dev)
-            self._lin_f32(s, feat, 768, w["tab.w"], None, tab, _hip.TAB_LD, nodes, _hip.TAB_LD, 768, False)
-            del feat
-            self._t32 = (mk, tuple(z), tab, maps[3])
-            if rays is not None:
-                # a later auto call on another call lane reads the tables: it waits for this build (below)
-                self._t32_ready = torch.cuda.Event()
-                self._t32_ready.record(torch.cuda.current_stream(dev))
-        tab, map3 = self._t32[2], self._t32[3]
-        T = V * S
-        if rays is None:
-            nray = B * R
-            loc16 = self._loc16(loc8, coords9, B, R, S)
-            enc = lambda ray0, n, hs: call(
-                "cpn_encode_hidden_f32", tab.data_ptr(), map3.data_ptr(), H, W, pixel_val.data_ptr(), sec_grid.data_ptr(),
-                pe6.data_ptr(), w["k80t"].data_ptr(), B, V, R, S, ray0, n, hs.data_ptr(), s)
-            att = lambda qa, ray0, n, hbar, wt: call(
-                "cpn_attend_hidden_f32", qa.data_ptr(), ce.data_ptr(), hs.data_ptr(), B, V, R, S, ray0, n, hbar.data_ptr(), wt, s)
-        else:
-            ev = self.__dict__.get("_t32_ready")
-            cur = torch.cuda.current_stream(dev)
-            if ev is not None:
-                cur.wait_event(ev)
-            tab.record_stream(cur)
-            map3.record_stream(cur)
-            nray = nsel
-            loc16 = self._loc16_rays(loc8, coords9, B, R, S, rays[:nsel].long())
-            zc = self._buf("f32t.zc", (nsel, 416), f32, dev)
-            enc = lambda ray0, n, hs: call(
-                "cpn_encode_hidden_f32_rays", tab.data_ptr(), map3.data_ptr(), H, W, pixel_val.data_ptr(), sec_grid.data_ptr(),
-                pe6.data_ptr(), w["k80t"].data_ptr(), B, V, R, S, rays.data_ptr(), ray0, n, hs.data_ptr(), s)
-            att = lambda qa, ray0, n, hbar, wt: call(
-                "cpn_attend_hidden_f32_rays", qa.data_ptr(), ce.data_ptr(), hs.data_ptr(), B, V, R, S, rays.data_ptr(), ray0, n,
-                hbar.data_ptr(), wt, s)
-        C = min(self.f32_chunk_rays, nray)
-        lin = lambda *a, **k: self._lin_f32(s, *a, **k)
-        t = lambda name, shape, dt=f32: self._buf("f32t." + name, shape, dt, dev)
-        for ray0 in range(0, nray, C):
-            n = min(C, nray - ray0)
-            rows = n * T
-            hs = t("hs", (rows, 3328), f16)
-            enc(ray0, n, hs)
-            kh, key2 = t("kh", (rows, 128)), t("key2", (rows, 128))
-            call("cpn_gemm_f16", hs.data_ptr(), 3328, w["keyf.w1"].data_ptr(), 3328, w["keyf.b"].data_ptr(), kh.data_ptr(), 128,
-                 rows, 128, 3328, 0, 1, s)
-            call("cpn_gemm_f16", hs.data_ptr(), 3328, w["keyf.w2"].data_ptr(), 1664, w["zero128"].data_ptr(), kh.data_ptr(), 128,
-                 rows, 128, 1664, 1, 2, s)
-            lin(kh, 128, w["key2.w"], w["key2.b"], key2, 128, rows, 128, 128, False)
-            lc = loc16[ray0 * T:(ray0 + n) * T]
-            hq, ce = t("hq", (rows, 128)), t("ce", (rows, 128))
-            lin(lc, 16, w["qe.w"], w["qe.b"], hq, 128, rows, 128, 16, True)
-            lin(hq, 128, w["qe2.w"], w["qe2.b"], ce, 128, rows, 128, 128, False)
-            hbar, z1, ze, aq = t("hbar", (n, 1664)), t("z1", (n, 416)), t("ze", (n, 128)), t("aq", (n, 128))
-            att(key2, ray0, n, hbar, at_wt.data_ptr())
-            lin(hbar, 1664, w["valf.w"], w["valf.b"], z1, 416, n, 416, 1664, False)
-            lin(z1, 416, w["el.w"], w["el.b"], ze, 128, n, 128, 416, False)
-            lin(ze, 128, w["qr.w_z"], None, aq, 128, n, 128, 128, False)
-            aq_rows = aq[:n].repeat_interleave(T, dim=0)                                     # the ray's vector on each of its samples
-            q2 = key2                                                                        # (the key is spent)
-            lin(lc, 16, w["qr.w_l"], w["qr.b"], hq, 128, rows, 128, 16, True, res=aq_rows)
-            lin(hq, 128, w["qr2.w"], w["qr2.b"], q2, 128, rows, 128, 128, False)
-            att(q2, ray0, n, hbar, 0)
-            zs = t("zs", (n, 416))
-            lin(hbar, 1664, w["valf.w"], w["valf.b"], zs, 416, n, 416, 1664, False)
-            # the round-1 vector sits in both view slots when the views are summed (CoPoNeRF.py:481-485): + V * z1
-            torch.add(zs[:n], z1[:n], alpha=float(V), out=(zl if rays is None else zc)[ray0:ray0 + n])
-        if rays is not None:
-            zl.index_copy_(0, rays[:nsel].long(), zc)
-
     def invalidate(self) -> None:
         """Drop the packed-weight / feature-map caches.  The caches are keyed on tensor identity and `_version`;
         writes that bypass the version counter (`p.data.copy_`, `dist.broadcast(p.data)`: /root/reference
@@ -615,14 +469,13 @@ class RenderEngine:
         self._camc = None
         self._next = []
         self._early = None
-        self._w32key, self._t32 = None, None
+        self._t32 = None
         self.epoch += 1
 
     def __deepcopy__(self, memo):
-        # caches, streams and workspace are derived state: a copied model gets a fresh engine with the same settings
-        new = RenderEngine(self.chunk_rays, self.lanes)
-        new.grad_scale_target, new.call_lanes, new.lazy_pixel_val = self.grad_scale_target, self.call_lanes, self.lazy_pixel_val
-        new.precision, new.f32_chunk_rays, new.auto_threshold = self.precision, self.f32_chunk_rays, self.auto_threshold
+        new = RenderEngine()
+        for name in self.SETTINGS:
+            setattr(new, name, getattr(self, name))
         return new
 
     @staticmethod
@@ -744,7 +597,8 @@ class RenderEngine:
         w["query_encode_latent.b"] = f32("query_encode_latent.bias")
         # ---- folding: query_encode_latent_2 is linear and feeds only linear layers, so
         #      key_map and latent_value act directly on the 2 x 832 hidden activations [h_own ; h_other]:
-        #      W' = [W_a . W2 | W_b . W2],  c' = W_a b2 + W_b b2 + b   (products in float64, then one rounding)
+        #      W' = [W_a . W2 | W_b . W2],  c' = W_a b2 + W_b b2 + b   (products in float64, then one rounding); the fp32 W'
+        #      stays in the entry for the reference-arithmetic path (render_f32.weights)
         W2 = f32("query_encode_latent_2.weight").reshape(416, 832).double()
         b2 = f32("query_encode_latent_2.bias").double()
 
@@ -755,13 +609,13 @@ class RenderEngine:
             dst = torch.empty(n_out, 1664, dtype=torch.float16, device=dev)
             src = Wf.float().contiguous()
             call("cpn_pack_weight_f16", src.data_ptr(), n_out, 1664, dst.data_ptr(), 1664, s)
-            return dst, cf.float().contiguous()
+            return src, dst, cf.float().contiguous()
 
-        w["key_fold.w16"], w["key_fold.b"] = fold("key_map.weight", "key_map.bias", 128)
+        w["key_fold.w"], w["key_fold.w16"], w["key_fold.b"] = fold("key_map.weight", "key_map.bias", 128)
         # the same matrix in the order cpn_encode_key streams it through its LDS ring: [image j][slice n][tile t][k][lane =
         # row + 16 * 8-column group][8] - every 1 KiB DMA piece contiguous
         w["key_fold.wpk"] = pack_key_ring(w["key_fold.w16"])
-        w["value_fold.w16"], w["value_fold.b"] = fold("latent_value.weight", "latent_value.bias", 416)
+        w["value_fold.w"], w["value_fold.w16"], w["value_fold.b"] = fold("latent_value.weight", "latent_value.bias", 416)
         # the same matrix in MFMA fragment order for the few-row form of the per-ray value projection (cpn_gemm_f16_fewrows)
         w["value_fold.wpk"] = torch.empty(416 * 1664, dtype=torch.float16, device=dev)
         call("cpn_pack_gemm_frags", w["value_fold.w16"].data_ptr(), 1664, 416, 1664, w["value_fold.wpk"].data_ptr(), s)
@@ -814,11 +668,10 @@ class RenderEngine:
         strong references to the z tensors and compares identity, so a freed-and-reallocated tensor at the same
         address can never hit it."""
         key = self._maps_key(z)
-        if key == self._mkey and len(self._mrefs) == len(z) and all(a is b for a, b in zip(self._mrefs, z)):
+        if self._same_maps(self._mkey, self._mrefs, key, z):
             return self._maps, self._tabs
         self._misses += 1
-        nx = next((e for e in self._next if e["mkey"] == key and len(e["z"]) == len(z) and
-                   all(a is b for a, b in zip(e["z"], z))), None)
+        nx = next((e for e in self._next if self._same_maps(e["mkey"], e["z"], key, z)), None)
         if nx is not None:
             # built by prepare_next() on its own stream while the previous pair rendered
             # Their blocks belong to the preparation stream's pool: record the adopting stream on them so that a block is
@@ -834,10 +687,16 @@ class RenderEngine:
         else:
             maps, tabs = self._build_maps(z, w)
         self._maps, self._tabs, self._mkey, self._mrefs = maps, tabs, key, tuple(z)
+        self._t32 = None                # the f32 path's tables belong to the entry replaced
         return maps, tabs
 
     def _maps_key(self, z: Sequence[torch.Tensor]):
         return tuple((t._version, tuple(t.shape)) for t in z) + (self._wgen,)
+
+    @staticmethod
+    def _same_maps(held_key, held_z, key, z) -> bool:
+        """A feature-map entry (its _maps_key and z tensors) is the one of `z`: same key and the same tensors by identity."""
+        return held_key == key and len(held_z) == len(z) and all(a is b for a, b in zip(held_z, z))
 
     def _build_maps(self, z: Sequence[torch.Tensor], w: Dict[str, torch.Tensor]):
         """The launches behind _feature_maps, on the current stream."""
@@ -864,6 +723,22 @@ class RenderEngine:
              tab.data_ptr(), _hip.TAB_LD, nodes, _hip.TAB_LD, 768, 0, 0, s)
         tabs.append(tab)
         return maps, tabs
+
+    def _f32_inputs(self, pz, w: Dict[str, torch.Tensor], H: int, W: int):
+        """(w, (tab, map3)): the weight entry with its f32 section and the fp32 node tables of the current pair (_t32, dropped
+        with the _feature_maps entry and by invalidate()), built on the stream of the first call that needs them.  Every reader,
+        on any call lane, waits for that build and is recorded on the tables (their blocks are the building stream's)."""
+        params, z = pz
+        cur = torch.cuda.current_stream(z[0].device)
+        if self._t32 is None:
+            render_f32.weights(w, params)
+            self._t32 = render_f32.node_tables(z, w, H, W, _stream())
+            self._t32_ready = torch.cuda.Event()
+            self._t32_ready.record(cur)
+        cur.wait_event(self._t32_ready)
+        for t in self._t32:
+            t.record_stream(cur)
+        return w, self._t32
 
     @torch.no_grad()
     def prepare_next(self, params: Dict[str, torch.Tensor], ctx_c2w, ctx_K, qry_c2w, qry_K, z: Sequence[torch.Tensor],
@@ -895,7 +770,7 @@ class RenderEngine:
         nx["z"] = tuple(z)
         with torch.cuda.stream(side):
             key = self._maps_key(z)
-            if key == self._mkey and len(self._mrefs) == len(z) and all(a is b for a, b in zip(self._mrefs, z)):
+            if self._same_maps(self._mkey, self._mrefs, key, z):
                 nx["mkey"], nx["maps"], nx["tabs"], nx["built"] = None, None, None, None
             else:
                 nx["maps"], nx["tabs"] = self._build_maps(z, w)
@@ -913,26 +788,36 @@ class RenderEngine:
     def _geometry(self, ctx_c2w, ctx_K, qry_c2w, qry_K, uv, rel_pose, val, S, H, W):
         dev = uv.device
         B, _, R, _ = uv.shape
-        N = B * V
-        s = _stream()
         up = self._camera(ctx_c2w, ctx_K, qry_c2w, qry_K, rel_pose, val, H, dev)
-        cam = up["cam"]
+        uvc, uvs = _uv_rows(uv, B, R)
+        new = lambda name, shape, dt: torch.empty(shape, dtype=dt, device=dev)
+        g = self._launch_geometry(new, up["cam"], uvc, uvs, self._sample_interval(S, dev), B, R, S, H, W)
+        g["Tq"], g["host"] = up["Tq"], up
+        return g
+
+    def _sample_interval(self, S: int, dev) -> torch.Tensor:
+        """linspace(0, 1, S) on the device (a CPU linspace, as the oracle's), made once per (S, device): a build is a miss."""
         ikey = (S, str(dev))
         if ikey not in self._interval:
             self._interval[ikey] = torch.linspace(0, 1, S).to(dev)
-        interval = self._interval[ikey]
-        uvc, uvs = _uv_rows(uv, B, R)
-        f32 = torch.float32
-        g = {"coords9": torch.empty(N, R, 9, dtype=f32, device=dev), "seg": torch.empty(N, R, 4, dtype=f32, device=dev),
-             "overlaps": torch.empty(N, R, dtype=torch.uint8, device=dev),
-             "pixel_val": torch.empty(N, R, S, 2, dtype=f32, device=dev), "pt": torch.empty(N, R, S, 3, dtype=f32, device=dev),
-             "sec_grid": torch.empty(N, R, S, 2, dtype=f32, device=dev), "pe6": torch.empty(N, R, S, 6, dtype=f32, device=dev),
-             "loc8": torch.empty(N, R, S, 8, dtype=f32, device=dev), "Tq": up["Tq"], "host": up}
+            self._misses += 1
+        return self._interval[ikey]
+
+    @staticmethod
+    def _launch_geometry(new, cam, uvc, uvs, interval, B, R, S, H, W, lvu=None) -> Dict[str, torch.Tensor]:
+        """The geometry launches of render() and render_train(), on the current stream, into tensors from new(name, shape,
+        dtype): per ray and view coords9, seg, overlaps (cpn_project_rays); per sample pixel_val, pt, sec_grid, pe6, loc8 and,
+        given `lvu`, the unit-order inputs of cpn_local_units (cpn_sample_geometry)."""
+        N = B * V
+        shapes = {"coords9": (N, R, 9), "seg": (N, R, 4), "overlaps": (N, R), "pixel_val": (N, R, S, 2), "pt": (N, R, S, 3),
+                  "sec_grid": (N, R, S, 2), "pe6": (N, R, S, 6), "loc8": (N, R, S, 8)}
+        g = {k: new(k, shape, torch.uint8 if k == "overlaps" else torch.float32) for k, shape in shapes.items()}
+        s = _stream()
         call("cpn_project_rays", cam.data_ptr(), uvc.data_ptr(), uvs, B, V, R, g["coords9"].data_ptr(), g["seg"].data_ptr(),
              g["overlaps"].data_ptr(), s)
         call("cpn_sample_geometry", cam.data_ptr(), g["coords9"].data_ptr(), g["seg"].data_ptr(), interval.data_ptr(),
              B, V, R, S, H, W, g["pixel_val"].data_ptr(), g["pt"].data_ptr(), g["sec_grid"].data_ptr(),
-             g["pe6"].data_ptr(), g["loc8"].data_ptr(), 0, s)
+             g["pe6"].data_ptr(), g["loc8"].data_ptr(), _ptr(lvu), s)
         return g
 
     def _start_host_copy(self, t):
@@ -1039,7 +924,7 @@ class RenderEngine:
         memory.  The decision is kept per (S, device, settings) for as long as the workspace of the current call lane already
         holds a chunk of `nrays` rays at that size (nothing would be allocated); otherwise free memory is consulted again."""
         key = (S, str(dev), self.lanes, self.call_lanes)
-        hit = self.__dict__.get("_auto_chunk_memo")
+        hit = self._auto_chunk_memo
         if hit is not None and hit[0] == key:
             have = self._ws.get(self._ws_prefix + "hid.0")
             if have is not None and have.device == dev and have.numel() >= min(hit[1], max(1, nrays)) * V * S * 2 * 832:
@@ -1057,7 +942,7 @@ class RenderEngine:
             pass
         fit = budget // per_ray
         C = int(max(1024, min(self.MAX_AUTO_CHUNK, fit // 1024 * 1024)))
-        self.__dict__["_auto_chunk_memo"] = (key, C)
+        self._auto_chunk_memo = (key, C)
         return C
 
     # ---- the render pass -------------------------------------------------------------------------
@@ -1073,7 +958,7 @@ class RenderEngine:
     def _call_stream(self, dev) -> Optional[torch.cuda.Stream]:
         if self.call_lanes <= 1:
             return None
-        if self.__dict__.get("_call_streams_given"):
+        if self._call_streams_given:
             if len(self._call_streams) != self.call_lanes or self._call_streams[0].device != dev:
                 raise RuntimeError("set_call_streams: need call_lanes streams on the render device")
         elif len(self._call_streams) != self.call_lanes or self._call_streams[0].device != dev:
@@ -1123,10 +1008,7 @@ class RenderEngine:
             fp, hit = flow_products(flow, inp["context"]["rgb"].shape[-2])
             self._misses += 0 if hit else 1
         up = self._camera(ctx_c2w, ctx_K, qry_c2w, qry_K, rel_pose, val, H, dev)
-        ikey = (S, str(dev))
-        if ikey not in self._interval:
-            self._interval[ikey] = torch.linspace(0, 1, S).to(dev)       # CPU linspace, as the oracle's
-            self._misses += 1
+        interval = self._sample_interval(S, dev)
         uvc, uvs = _uv_rows(uv, B, R)
         base = uv._base if uv._base is not None else uv
         side = self._call_stream(dev)            # may install new lane streams, which resets _uv_seen (-> fresh)
@@ -1134,7 +1016,7 @@ class RenderEngine:
         fresh = self._misses != miss0 or seen is None or seen[0] is not base or seen[1] != base._version or \
             uvc.untyped_storage().data_ptr() != uv.untyped_storage().data_ptr()
         self._uv_seen = (base, base._version)
-        pre = (w, maps, tabs, up, self._interval[ikey], uvc, uvs, fp, (params, z))
+        pre = (w, maps, tabs, up, interval, uvc, uvs, fp, (params, z))
         if side is None:
             self._ws_prefix = ""
             return self._render_body(pre, B, R, S, H, W, dev, debug, inp)
@@ -1159,18 +1041,11 @@ class RenderEngine:
         w, maps, tabs, up, interval, uvc, uvs, fp = pre[:8]
         N = B * V
         s = _stream()
-        cam = up["cam"]
 
         f32, f16 = torch.float32, torch.float16
-        coords9 = torch.empty(N, R, 9, dtype=f32, device=dev)
-        seg = self._buf("seg", (N, R, 4), f32, dev)
-        overlaps = self._buf("overlaps", (N, R), torch.uint8, dev)
-        pixel_val = torch.empty(N, R, S, 2, dtype=f32, device=dev)
-        pt = torch.empty(N, R, S, 3, dtype=f32, device=dev)
-        at_wt = torch.empty(N, R, S, dtype=f32, device=dev)
-        sec_grid = self._buf("sec_grid", (N, R, S, 2), f32, dev)
-        pe6 = self._buf("pe6", (N, R, S, 6), f32, dev)
-        loc8 = self._buf("loc8", (N, R, S, 8), f32, dev)
+        # the geometry the call hands out is fresh memory, the rest of it workspace
+        new = lambda name, shape, dt: torch.empty(shape, dtype=dt, device=dev) if name in ("coords9", "pixel_val", "pt") \
+            else self._buf(name, shape, dt, dev)
         # the per-sample inputs of the two query MLPs once more in the UNIT order cpn_local_units multiplies in (one coalesced
         # line per unit instead of scattered reads of loc8 / coords9; include/coponerf_hip.h, cpn_sample_geometry)
         lvu = None
@@ -1182,11 +1057,10 @@ class RenderEngine:
                 # they hold feed MFMA columns of their own whose results are dropped - fresh memory is cleared once so that
                 # nothing there is a NaN pattern either (a fill per call cost the callers' 18-call loop a launch per call)
                 self._ws[self._ws_prefix + "lvu"].zero_()
-        call("cpn_project_rays", cam.data_ptr(), uvc.data_ptr(), uvs, B, V, R, coords9.data_ptr(), seg.data_ptr(),
-             overlaps.data_ptr(), s)
-        call("cpn_sample_geometry", cam.data_ptr(), coords9.data_ptr(), seg.data_ptr(), interval.data_ptr(),
-             B, V, R, S, H, W, pixel_val.data_ptr(), pt.data_ptr(), sec_grid.data_ptr(), pe6.data_ptr(),
-             loc8.data_ptr(), lvu.data_ptr() if lvu is not None else 0, s)
+        g = self._launch_geometry(new, up["cam"], uvc, uvs, interval, B, R, S, H, W, lvu)
+        coords9, overlaps, pixel_val, pt = g["coords9"], g["overlaps"], g["pixel_val"], g["pt"]
+        sec_grid, pe6, loc8 = g["sec_grid"], g["pe6"], g["loc8"]
+        at_wt = torch.empty(N, R, S, dtype=f32, device=dev)
 
         # the caller contract wants pixel_val on the CPU (CoPoNeRF.py:490): start the 8*N*R*S-byte device->host copy
         # now, into pinned memory on a side stream, so it overlaps the GEMMs instead of stalling the step's tail
@@ -1199,7 +1073,6 @@ class RenderEngine:
         score = self._buf("guard.score", (nray_total,), f32, dev) if auto else None
         C = min(self.chunk_rays if self.chunk_rays > 0 else self._auto_chunk(S, dev, nray_total), nray_total)
         T = V * S                       # rows per ray for the attention stage
-        GW = dict(self.GEMM_WEIGHTS, key_fold=(128, 1664, 1664), value_fold=(416, 1664, 1664))
         nchunks = (nray_total + C - 1) // C
         nlanes = min(self.lanes, nchunks)
         if nlanes > 1 and (len(self._lane_streams) < nlanes or self._lane_streams[0].device != dev):
@@ -1288,8 +1161,10 @@ class RenderEngine:
             value_fold(s, bf["hbar"], bf["zs"], n)
             torch.add(bf["zs"][:n], z1[:n], alpha=float(V), out=zl[ray0:ray0 + n])
 
+        dims = (B, R, S, H, W)
+        f32_inputs = lambda: self._f32_inputs(pre[8], w, H, W)
         if self.precision == "f32":
-            self._per_sample_f32(pre[8], B, R, S, H, W, pixel_val, sec_grid, pe6, loc8, coords9, zl, at_wt, s)
+            render_f32.per_sample(*f32_inputs(), g, zl, at_wt, dims, self.f32_chunk_rays, self._buf, s)
         elif nlanes == 1:
             bf = lane_buffers(0)
             for ray0 in range(0, nray_total, C):
@@ -1309,7 +1184,21 @@ class RenderEngine:
                 done.record(self._lane_streams[lane])
                 main.wait_event(done)
         if auto:
-            self._exact_rays(pre[8], score, B, R, S, H, W, pixel_val, sec_grid, pe6, loc8, coords9, zl, at_wt, s)
+            # list the rays whose guard score exceeds auto_threshold (cpn_select_rays), read their count - the mode's ONE host
+            # wait per call - and render those rays again in the reference's arithmetic before the decoder runs
+            lst = self._buf("guard.list", (nray_total,), torch.int32, dev)
+            cnt = self._buf("guard.count", (1,), torch.int32, dev)
+            call("cpn_select_rays", score.data_ptr(), nray_total, float(self.auto_threshold), lst.data_ptr(), cnt.data_ptr(), s)
+            if self._guard_host is None:
+                self._guard_host = torch.empty(1, dtype=torch.int32, pin_memory=True)
+            self._guard_host.copy_(cnt, non_blocking=True)
+            copied = torch.cuda.Event()
+            copied.record()
+            copied.synchronize()
+            k = int(self._guard_host[0])
+            self.last_exact_rays = (k, nray_total)
+            if k > 0:
+                render_f32.per_sample(*f32_inputs(), g, zl, at_wt, dims, self.f32_chunk_rays, self._buf, s, rays=lst, nsel=k)
 
         # ---- light-field decoder phi over all rays (lightfield.py:131-167) + white background, exact fp32, one launch
         rgb = torch.empty(B, 1, R, 3, dtype=f32, device=dev)
@@ -1331,24 +1220,3 @@ class RenderEngine:
             if auto:
                 out["guard_score"] = score.view(B, R).clone()
         return out
-
-    def _exact_rays(self, pz, score, B, R, S, H, W, pixel_val, sec_grid, pe6, loc8, coords9, zl, at_wt, s) -> None:
-        """precision="auto", after the fp16 chunks have joined: list the rays whose guard score exceeds auto_threshold
-        (cpn_select_rays), read their count on the host - the mode's ONE host wait per call - and render those rays again in
-        the reference's arithmetic (_per_sample_f32 over the list), overwriting their zl rows and at_wt entries before the
-        decoder runs.  The fp32 tables are built by the first call that flags a ray."""
-        nray = B * R
-        dev = zl.device
-        lst = self._buf("guard.list", (nray,), torch.int32, dev)
-        cnt = self._buf("guard.count", (1,), torch.int32, dev)
-        call("cpn_select_rays", score.data_ptr(), nray, float(self.auto_threshold), lst.data_ptr(), cnt.data_ptr(), s)
-        if self._guard_host is None:
-            self._guard_host = torch.empty(1, dtype=torch.int32, pin_memory=True)
-        self._guard_host.copy_(cnt, non_blocking=True)
-        copied = torch.cuda.Event()
-        copied.record()
-        copied.synchronize()
-        k = int(self._guard_host[0])
-        self.last_exact_rays = (k, nray)
-        if k > 0:
-            self._per_sample_f32(pz, B, R, S, H, W, pixel_val, sec_grid, pe6, loc8, coords9, zl, at_wt, s, rays=lst, nsel=k)

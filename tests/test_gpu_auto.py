@@ -201,6 +201,9 @@ def test_threshold_limits(dev):
     for k in ("rgb", "at_wt"):
         assert _same(oa[k], o32[k]), k
     assert _same(oa["_core"]["z_local"], o32["_core"]["z_local"])
+    assert m._engine._t32 is not None
+    _run(m, dev, _sweep_case(63, 64), "auto", auto_threshold=math.inf)      # a new pair that flags nothing
+    assert m._engine._t32 is None                              # the old pair's fp32 tables are not kept
     with pytest.raises(ValueError, match="auto"):
         _run(m, dev, case, "fp8")
 
@@ -290,11 +293,11 @@ def test_held_out_sharpness_sweep(dev):
 
 
 # ---- 7. the callers' loop ------------------------------------------------------------------------------------------------------
-def test_callers_loop_equals_one_call(dev):
+def _callers_loop_equals_one_call(dev, precision):
     from coponerf_amd.evalloop import render_in_chunks
     B, H = 2, 64
     m = _model(dev, syn.peaked_weights(syn.make_render_weights(seed=19), 48.0), 32)
-    m._engine.precision = "auto"
+    m._engine.precision = precision
     m._engine.call_lanes = 2
     inp = to_device(syn.make_inputs(B, H, H, 0, seed=71, full_image=True), dev)
     z, rel, flow = syn.make_latents(B, H, H, seed=72)
@@ -302,8 +305,9 @@ def test_callers_loop_equals_one_call(dev):
     rel, flow = rel.to(dev), to_device(flow, dev)
     with torch.no_grad():
         full = m(inp, z=z, rel_pose=rel, val=True, flow=flow)
-    k, n = m._engine.last_exact_rays
-    assert 0 < k < n
+    if precision == "auto":
+        k, n = m._engine.last_exact_rays
+        assert 0 < k < n
     joined = render_in_chunks(m, inp, 18, latents=(z, rel, flow))
     assert torch.equal(joined["pixel_val"], full["pixel_val"])
     assert torch.equal(joined["at_wt_max"], full["at_wt_max"])
@@ -312,9 +316,19 @@ def test_callers_loop_equals_one_call(dev):
         assert _same(joined[key], full[key]), key
 
 
+def test_callers_loop_equals_one_call(dev):
+    _callers_loop_equals_one_call(dev, "auto")
+
+
+def test_callers_loop_equals_one_call_in_f32_mode(dev):
+    """the f32 mode's tables are built by the loop's first call on one call lane and read by the next call on the other"""
+    _callers_loop_equals_one_call(dev, "f32")
+
+
 # ---- 8. the default and the f32 mode run none of the new entries ---------------------------------------------------------------
 def test_f16_and_f32_modes_do_not_launch_the_guard(dev, monkeypatch):
     import coponerf_amd.render as render_mod
+    import coponerf_amd.render_f32 as render_f32_mod
     seen = []
     inner = render_mod.call
 
@@ -322,7 +336,8 @@ def test_f16_and_f32_modes_do_not_launch_the_guard(dev, monkeypatch):
         seen.append(name)
         return inner(name, *args)
 
-    monkeypatch.setattr(render_mod, "call", counting)
+    for mod in (render_mod, render_f32_mod):
+        monkeypatch.setattr(mod, "call", counting)
     case = _sweep_case(61, 62)
     m = _model(dev, syn.peaked_weights(syn.make_render_weights(seed=19), 48.0), 32)
     for precision in ("f16", "f32"):

@@ -107,6 +107,25 @@ def test_uv_rows_reads_ray_chunks_in_place():
     assert u2.is_contiguous() and s2 == 20 and torch.equal(u2, full[:, 0])
 
 
+def test_loc16_of_all_rays_and_of_listed_rays():
+    """render_f32.loc16: the 16 local_coords channels per sample in row order ((ray * V + v) * S + s) from cpn_sample_geometry's
+    loc8 / coords9; with a ray list, the rows of the listed rays only, in list order."""
+    from coponerf_amd.render_f32 import loc16
+    B, V, R, S = 2, 2, 5, 3
+    g = torch.Generator().manual_seed(3)
+    loc8, coords9 = torch.randn(B * V, R, S, 8, generator=g), torch.randn(B * V, R, 9, generator=g)
+    full = loc16(loc8, coords9, B, R, S)
+    assert full.shape == (B * R * V * S, 16) and full.is_contiguous()
+    rows = full.view(B, R, V, S, 16)
+    l8 = loc8.view(B, V, R, S, 8).permute(0, 2, 1, 3, 4)
+    c9 = coords9.view(B, V, R, 1, 9).permute(0, 2, 1, 3, 4).expand(B, R, V, S, 9)
+    assert torch.equal(rows[..., 0:3], l8[..., 0:3]) and not rows[..., 3:6].any()
+    assert torch.equal(rows[..., 6:9], c9[..., 0:3]) and torch.equal(rows[..., 9:13], l8[..., 3:7])
+    assert torch.equal(rows[..., 13:16], c9[..., 6:9])
+    rays = torch.tensor([7, 0, 9, 4])                     # rays of both pairs, in any order
+    assert torch.equal(loc16(loc8, coords9, B, R, S, rays), full.view(B * R, V * S, 16)[rays].reshape(-1, 16))
+
+
 def test_guard_on_device_matches_the_host_guard():
     """dist.guard_on_device (flag and clip coefficient as tensors, no host read) against dist.guard_and_clip: same flag, the
     coefficient it would have applied; a NaN makes the flag 0 and leaves the coefficient finite; no gradients at all -> flag 1."""

@@ -28,6 +28,17 @@ def test_auto_threshold_default_and_deepcopy():
     assert copy.deepcopy(eng).auto_threshold == math.inf
 
 
+def test_deepcopy_keeps_every_setting():
+    eng = RenderEngine(chunk_rays=1300, lanes=3)
+    eng.grad_scale_target, eng.call_lanes, eng.lazy_pixel_val = 64.0, 3, False
+    eng.precision, eng.f32_chunk_rays, eng.auto_threshold = "f32", 1000, 0.25
+    new = copy.deepcopy(eng)
+    for name in ("chunk_rays", "lanes", "grad_scale_target", "call_lanes", "lazy_pixel_val", "precision", "f32_chunk_rays",
+                 "auto_threshold"):
+        assert getattr(new, name) == getattr(eng, name), name
+    assert new._t32 is None and not new._ws and not new._w                 # caches are not copied
+
+
 def test_guard_entries_are_bound():
     for name in ("cpn_logit_guard", "cpn_select_rays", "cpn_encode_hidden_f32_rays", "cpn_attend_hidden_f32_rays"):
         assert name in _hip.SIGNATURES and name in _hip.declared_symbols()
