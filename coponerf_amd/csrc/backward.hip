@@ -5,6 +5,7 @@
 //
 //   cpn_attend_hidden_bwd  gradient of the joint softmax + attention-weighted hidden sum (cpn_attend_hidden),
 //                          i.e. of /root/reference models/CoPoNeRF.py:450-461 / 475-485 in the folded form
+//   cpn_attend_hidden_bwd_f32  the same for cpn_attend_hidden_f32 (fp32 operands, hidden activations as (hi, lo) pairs)
 //   cpn_gather_rows_bwd    gradient of the bilinear multi-scale gather w.r.t. the feature maps (scatter-add),
 //                          i.e. of F.grid_sample at models/CoPoNeRF.py:312 / 370 (no coordinate gradient: all sample
 //                          coordinates derive from poses only and `pt` is detached, CoPoNeRF.py:380-381, 433)
@@ -385,6 +386,101 @@ __global__ __launch_bounds__(256) void attend_hidden_bwd_kernel(
     }
 }
 
+// The same gradient for the reference-arithmetic training forward (RenderEngine.train_precision = "f32"): fp32 qa / qb /
+// dqa / dqb / dqb_acc and the hidden activations as the (hi, lo) fp16 pairs cpn_encode_hidden_f32 stored, hs row =
+// [hi_own | hi_other | lo_own | lo_other] (3328 halves).  Everything is fp32 from the loads on:
+//   dw[row] = <hi[row] + lo[row], dhbar> + dw_ext[row],  dl[row] = w[row] * (dw[row] - sum_r w[r] dw[r]) / 11.31,
+//   dqa[row] = dl[row] * qb[row],  dqb[row] = dl[row] * qa[row] (+ dqb_acc[row])
+// HBM-bound: the 6.5 KB hs row is read once (one wave per row, the hi and lo chunks of a lane side by side).
+__global__ __launch_bounds__(256) void attend_hidden_bwd_f32_kernel(
+    const float* __restrict__ qa, const float* __restrict__ qb, const __half* __restrict__ hs,
+    const float* __restrict__ at_wt, const float* __restrict__ dhbar, const float* __restrict__ dw_ext, int V, int R,
+    int S, int ray0, float* __restrict__ dqa, float* __restrict__ dqb, const float* __restrict__ dqb_acc) {
+    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+    float* dh = reinterpret_cast<float*>(smem_raw);          // HC floats: dhbar of this ray
+    float* wts = dh + HC;                                    // T
+    float* dl = wts + V * S;                                 // T
+    float* red = dl + V * S;                                 // 4
+    const int T = V * S;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const unsigned lray = blockIdx.x;
+    const size_t row0 = (size_t)lray * T;
+    const unsigned ray = (unsigned)ray0 + lray;
+    const int b = (int)(ray / (unsigned)R), r = (int)(ray % (unsigned)R);
+
+    for (int c = tid; c < HC; c += 256) dh[c] = dhbar[(size_t)lray * HC + c];
+    for (int row = tid; row < T; row += 256) {
+        const int v = row / S, s = row - v * S;
+        wts[row] = at_wt[(((size_t)(b * V + v)) * R + r) * S + s];
+    }
+    __syncthreads();
+    constexpr int NCH = HC / 8;                              // 208 chunks per half row
+    constexpr int HS_LD = 2 * HC;                            // hs row stride (halves)
+    float dreg[4][8];
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+#pragma unroll
+        for (int e = 0; e < 8; ++e) dreg[k][e] = (lane + 64 * k < NCH) ? dh[(lane + 64 * k) * 8 + e] : 0.0f;
+    auto load_row = [&](int row, half8 (&h)[4], half8 (&l)[4]) {
+        const __half* hp = hs + (row0 + min(row, T - 1)) * HS_LD;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {                        // chunk 208.. of the last group: re-read chunk lane (weight 0)
+            const int ch = (lane + 64 * k < NCH) ? lane + 64 * k : lane;
+            h[k] = __builtin_nontemporal_load(reinterpret_cast<const half8*>(hp + ch * 8));
+            l[k] = __builtin_nontemporal_load(reinterpret_cast<const half8*>(hp + HC + ch * 8));
+        }
+    };
+    auto row_dot = [&](const half8 (&h)[4], const half8 (&l)[4]) {
+        float acc = 0.f;
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+#pragma unroll
+            for (int e = 0; e < 8; ++e) acc += ((float)h[k][e] + (float)l[k][e]) * dreg[k][e];
+        return wave_sum_f(acc);
+    };
+    float part = 0.f;
+    auto finish = [&](int row, float acc) {
+        if (lane == 0 && row < T) {
+            float dwv = acc;
+            if (dw_ext) {
+                const int v = row / S, s = row - v * S;
+                dwv += dw_ext[(((size_t)(b * V + v)) * R + r) * S + s];
+            }
+            dl[row] = dwv;
+            part += wts[row] * dwv;
+        }
+    };
+    for (int row = wave; row < T; row += 8) {
+        half8 ha[4], la[4], hb[4], lb[4];
+        load_row(row, ha, la);
+        load_row(row + 4, hb, lb);
+        finish(row, row_dot(ha, la));
+        finish(row + 4, row_dot(hb, lb));
+    }
+    if (lane == 0) red[wave] = part;
+    __syncthreads();
+    const float dot = (red[0] + red[1]) + (red[2] + red[3]);
+    for (int row = tid; row < T; row += 256) dl[row] = wts[row] * (dl[row] - dot) / 11.31f;
+    __syncthreads();
+    // dqa / dqb: thread = (row, 4-channel group)
+    for (int i = tid; i < T * 32; i += 256) {
+        const int row = i >> 5, g = i & 31;
+        const size_t off = (row0 + row) * 128 + g * 4;
+        const f32x4 a = *reinterpret_cast<const f32x4*>(qa + off);
+        const f32x4 bq = *reinterpret_cast<const f32x4*>(qb + off);
+        const f32x4 pq = dqb_acc ? *reinterpret_cast<const f32x4*>(dqb_acc + off) : f32x4{0.f, 0.f, 0.f, 0.f};
+        const float d = dl[row];
+        f32x4 oa, ob;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            oa[e] = d * bq[e];
+            ob[e] = pq[e] + d * a[e];
+        }
+        *reinterpret_cast<f32x4*>(dqa + off) = oa;
+        *reinterpret_cast<f32x4*>(dqb + off) = ob;
+    }
+}
+
 // d(pre-activation of the first encoder layer) from ALL consumers of `hid` in one pass:
 //     out[row, c] = hid[row, c] > 0 ? dkey[row, c] + w1[row] * dh1[ray, j*832 + c] + w2[row] * dh2[ray, j*832 + c] : 0
 // hid feeds the key path (a GEMM, gradient dkey) and the two attention-weighted hidden sums (gradients w_i (x) dhbar_i,
@@ -703,6 +799,23 @@ extern "C" int cpn_attend_hidden_bwd(const uint16_t* qa, const uint16_t* qb, con
                        (const __half*)qa, (const __half*)qb, (const __half*)hid, at_wt, dhbar, dw_ext, V, R, S, ray0,
                        (__half*)dqa, (__half*)dqb, (__half*)dhid, (const __half*)dqb_acc);
     CPN_LAUNCH_CHECK("cpn_attend_hidden_bwd");
+    return 0;
+}
+
+extern "C" int cpn_attend_hidden_bwd_f32(const float* qa, const float* qb, const uint16_t* hs, const float* at_wt,
+                                         const float* dhbar, const float* dw_ext, int B, int V, int R, int S, int ray0,
+                                         int nrays, float* dqa, float* dqb, const float* dqb_acc, void* stream) {
+    CPN_REQUIRE(qa && qb && hs && at_wt && dhbar && dqa && dqb, CPN_E_ARG, "cpn_attend_hidden_bwd_f32: null pointer");
+    CPN_REQUIRE(B > 0 && V == 2 && R > 0 && S > 0 && V * S <= 2048, CPN_E_SHAPE, "cpn_attend_hidden_bwd_f32: bad shape");
+    CPN_REQUIRE(ray0 >= 0 && nrays > 0 && (long long)ray0 + nrays <= (long long)B * R, CPN_E_ARG,
+                "cpn_attend_hidden_bwd_f32: ray range outside B*R");
+    CPN_REQUIRE(((uintptr_t)qa % 16) == 0 && ((uintptr_t)qb % 16) == 0 && ((uintptr_t)hs % 16) == 0 && ((uintptr_t)dqa % 16) == 0 &&
+                    ((uintptr_t)dqb % 16) == 0 && ((uintptr_t)dqb_acc % 16) == 0, CPN_E_ARG,
+                "cpn_attend_hidden_bwd_f32: operands must be 16-byte aligned");
+    const size_t lds = (size_t)(HC + 2 * V * S + 4) * sizeof(float);
+    hipLaunchKernelGGL(attend_hidden_bwd_f32_kernel, dim3(nrays), dim3(256), lds, (hipStream_t)stream, qa, qb, (const __half*)hs,
+                       at_wt, dhbar, dw_ext, V, R, S, ray0, dqa, dqb, dqb_acc);
+    CPN_LAUNCH_CHECK("cpn_attend_hidden_bwd_f32");
     return 0;
 }
 

@@ -726,24 +726,44 @@ extern "C" int cpn_gemm_f16(const uint16_t* A, int lda, const uint16_t* W, int l
     return CPN_E_SHAPE;
 }
 
+namespace {
+
+// the two combine entries: the mask is read from rows of LDH halves (hid (rows, 1664), or the hi half of hs (rows, 3328))
+template <int LDH>
+int gemm_f16_combine(const char* name, const uint16_t* dkh, int lda, const uint16_t* Wt, int ldw, const uint16_t* hid,
+                     const float* w1, const float* dh1, const float* w2, const float* dh2, int B, int V, int R, int S, int ray0,
+                     int nrays, int K, uint16_t* out, void* stream) {
+    CPN_REQUIRE(dkh && Wt && hid && out && (!w1 || dh1) && (!w2 || dh2), CPN_E_ARG, "%s: null pointer", name);
+    CPN_REQUIRE(B > 0 && V == 2 && R > 0 && S > 0 && (S % 16) == 0, CPN_E_SHAPE, "%s: need V == 2, S %% 16 == 0", name);
+    CPN_REQUIRE(ray0 >= 0 && nrays > 0 && (long long)ray0 + nrays <= (long long)B * R, CPN_E_SHAPE,
+                "%s: ray range outside B*R", name);
+    CPN_REQUIRE(K > 0 && (K % 32) == 0 && lda >= K && ldw >= K && (lda % 8) == 0 && (ldw % 8) == 0, CPN_E_SHAPE,
+                "%s: bad K / leading dimension", name);
+    const long long M = (long long)nrays * V * S;
+    CPN_REQUIRE(M < (1LL << 31) && (long long)256 * lda * 2 < (1LL << 31) && (long long)1664 * ldw * 2 < (1LL << 31), CPN_E_SHAPE,
+                "%s: problem exceeds the 32-bit index range", name);
+    CPN_REQUIRE(((uintptr_t)dkh % 16) == 0 && ((uintptr_t)Wt % 16) == 0 && ((uintptr_t)hid % 16) == 0 && ((uintptr_t)out % 16) == 0 &&
+                    ((uintptr_t)dh1 % 16) == 0 && ((uintptr_t)dh2 % 16) == 0, CPN_E_ARG,
+                "%s: pointers must be 16-byte aligned", name);
+    CombineArgs ca{w1, dh1, w2, dh2, V, R, S, ray0, 0};
+    return launch_combine<13>((const __half*)dkh, lda, (const __half*)Wt, ldw, (const __half*)hid, LDH, ca, (__half*)out, 1664,
+                              (int)M, 1664, K / 32, (hipStream_t)stream);
+}
+
+}  // namespace
+
 extern "C" int cpn_gemm_f16_combine(const uint16_t* dkh, int lda, const uint16_t* Wt, int ldw, const uint16_t* hid, const float* w1,
                                     const float* dh1, const float* w2, const float* dh2, int B, int V, int R, int S, int ray0,
                                     int nrays, int K, uint16_t* out, void* stream) {
-    CPN_REQUIRE(dkh && Wt && hid && out && (!w1 || dh1) && (!w2 || dh2), CPN_E_ARG, "cpn_gemm_f16_combine: null pointer");
-    CPN_REQUIRE(B > 0 && V == 2 && R > 0 && S > 0 && (S % 16) == 0, CPN_E_SHAPE, "cpn_gemm_f16_combine: need V == 2, S %% 16 == 0");
-    CPN_REQUIRE(ray0 >= 0 && nrays > 0 && (long long)ray0 + nrays <= (long long)B * R, CPN_E_SHAPE,
-                "cpn_gemm_f16_combine: ray range outside B*R");
-    CPN_REQUIRE(K > 0 && (K % 32) == 0 && lda >= K && ldw >= K && (lda % 8) == 0 && (ldw % 8) == 0, CPN_E_SHAPE,
-                "cpn_gemm_f16_combine: bad K / leading dimension");
-    const long long M = (long long)nrays * V * S;
-    CPN_REQUIRE(M < (1LL << 31) && (long long)256 * lda * 2 < (1LL << 31) && (long long)1664 * ldw * 2 < (1LL << 31), CPN_E_SHAPE,
-                "cpn_gemm_f16_combine: problem exceeds the 32-bit index range");
-    CPN_REQUIRE(((uintptr_t)dkh % 16) == 0 && ((uintptr_t)Wt % 16) == 0 && ((uintptr_t)hid % 16) == 0 && ((uintptr_t)out % 16) == 0 &&
-                    ((uintptr_t)dh1 % 16) == 0 && ((uintptr_t)dh2 % 16) == 0, CPN_E_ARG,
-                "cpn_gemm_f16_combine: pointers must be 16-byte aligned");
-    CombineArgs ca{w1, dh1, w2, dh2, V, R, S, ray0, 0};
-    return launch_combine<13>((const __half*)dkh, lda, (const __half*)Wt, ldw, (const __half*)hid, 1664, ca, (__half*)out, 1664,
-                              (int)M, 1664, K / 32, (hipStream_t)stream);
+    return gemm_f16_combine<1664>("cpn_gemm_f16_combine", dkh, lda, Wt, ldw, hid, w1, dh1, w2, dh2, B, V, R, S, ray0, nrays, K, out,
+                                  stream);
+}
+
+extern "C" int cpn_gemm_f16_combine_hs(const uint16_t* dkh, int lda, const uint16_t* Wt, int ldw, const uint16_t* hs, const float* w1,
+                                       const float* dh1, const float* w2, const float* dh2, int B, int V, int R, int S, int ray0,
+                                       int nrays, int K, uint16_t* out, void* stream) {
+    return gemm_f16_combine<3328>("cpn_gemm_f16_combine_hs", dkh, lda, Wt, ldw, hs, w1, dh1, w2, dh2, B, V, R, S, ray0, nrays, K,
+                                  out, stream);
 }
 
 extern "C" int cpn_gemm_f16_masked(const uint16_t* A, int lda, const uint16_t* Wt, int ldw, const uint16_t* mask, int ldm,

@@ -377,9 +377,10 @@ class RenderEngine:
     # fp16 rgb was off by > 5e-4 or a weight by > 1e-3 in the calibration sweep (tools/auto_calibrate.py)
     AUTO_THRESHOLD = 0.5062
     PRECISIONS = ("f16", "f32", "auto")
+    TRAIN_PRECISIONS = ("f16", "f32")
     # what a copied engine keeps (__deepcopy__); caches, streams and workspace are derived state
     SETTINGS = ("chunk_rays", "lanes", "grad_scale_target", "call_lanes", "lazy_pixel_val", "precision", "f32_chunk_rays",
-                "auto_threshold")
+                "auto_threshold", "train_precision")
 
     def __init__(self, chunk_rays: int = 0, lanes: int = 1):
         # ONE per-sample formulation (round 6; rounds 2-5 kept their predecessors as switchable modes - gather + GEMM first layer,
@@ -410,6 +411,11 @@ class RenderEngine:
         # arithmetic and merged in before the decoder (_render_body).  inf: no ray; negative: every ray.  One host wait per call
         # (the flagged count).  last_exact_rays = (flagged, total) of the last auto call.
         self.auto_threshold = self.AUTO_THRESHOLD
+        # train_precision="f32" (COPONERF_TRAIN_PRECISION=f32): render_train's per-sample stages in the f32 mode's arithmetic, as
+        # autograd nodes (train_f32.py); the gradients of the attention sums and of every fp32 layer are fp32, hs's gradient and
+        # the first layer's table-form backward keep fp16 operands.  "f16" (default): the fp16 formulation (train_fns.py).
+        # `precision` governs render() only.
+        self.train_precision = os.environ.get("COPONERF_TRAIN_PRECISION", "f16")
         self.last_exact_rays: Optional[Tuple[int, int]] = None
         self._guard_host: Optional[torch.Tensor] = None
         self._t32: Optional[Tuple[torch.Tensor, torch.Tensor]] = None     # the f32 path's node tables (_f32_inputs)
@@ -851,9 +857,12 @@ class RenderEngine:
     # ---- the differentiable render pass (training; gradients to the render weights and to z) ------------
     def render_train(self, params: Dict[str, torch.Tensor], ctx_c2w, ctx_K, qry_c2w, qry_K, uv,
                      z: Sequence[torch.Tensor], rel_pose, val: bool, S: int, H: int, W: int) -> Dict[str, torch.Tensor]:
-        """Same forward kernels as render(), wrapped in autograd Functions (coponerf_amd/train_fns.py); all rays of
-        the call form one chunk (training uses <= 4096 rays per pair, /root/reference train.py:87).  `precision` is not
-        consulted: "f32" and "auto" are inference-only modes, training always runs the fp16 formulation."""
+        """Same forward kernels as render(), wrapped in autograd Functions; all rays of the call form one chunk (training uses
+        <= 4096 rays per pair, /root/reference train.py:87).  `train_precision` picks the per-sample stages: "f16" the fp16
+        formulation (coponerf_amd/train_fns.py), "f32" the f32 mode's arithmetic (coponerf_amd/train_f32.py).  `precision`
+        is not consulted: it governs render() only ("auto" has no training form)."""
+        if self.train_precision not in self.TRAIN_PRECISIONS:
+            raise ValueError(f"RenderEngine.train_precision must be 'f16' or 'f32' (got {self.train_precision!r})")
         from .train_fns import (AttendHiddenFn, BackwardPass, EncodeFn, GemmFn, KeyForward, KeyLayerFn, LinearF32Fn,
                                 LocalHiddenFn)
         dev = uv.device
@@ -873,10 +882,18 @@ class RenderEngine:
 
         def fold(name, n_out):                                   # differentiable fp32 fold
             Wa, Wb = mat(name, n_out).chunk(2, 1)                # one split node, not four slices (each a fill + copy + add backward)
+            if self.train_precision == "f32":                    # its products in float64, as _weights folds for render()
+                W2d, Wa, Wb = W2.double(), Wa.double(), Wb.double()
+                return (torch.cat((Wa @ W2d, Wb @ W2d), dim=1).float(),
+                        ((Wa + Wb) @ b2.double() + bias(name).double()).float())
             return torch.cat((Wa @ W2, Wb @ W2), dim=1), (Wa + Wb) @ b2 + bias(name)
 
         Wkf, ckf = fold("key_map", 128)
         Wvf, cvf = fold("latent_value", 416)
+        if self.train_precision == "f32":
+            from .train_f32 import render_samples
+            zl, w1 = render_samples(P, mat, bias, z, g, (Wkf, ckf), (Wvf, cvf), dims, (H, W), bp)
+            return self._train_outputs(P, g, zl, w1, B, R, pixel_val_cpu, copy_done)
         kf = KeyForward(Wkf, ckf)                   # the folded key layer's forward rides in the first layer's kernel
         # the first layer on the node tables with the key layer behind it, as in inference: no gathered input in the forward pass
         hid = EncodeFn.apply(z[0], z[1], z[2], z[3], mat("query_encode_latent", 832), bias("query_encode_latent"),
@@ -898,6 +915,14 @@ class RenderEngine:
         hbar2, _ = AttendHiddenFn.apply(q2, ce, hid2, dims, bp, False)
         zs = GemmFn.apply(hbar2, Wvf, cvf, False, True, bp)
         zl = zs + float(V) * z1                                  # CoPoNeRF.py:481-485
+        return self._train_outputs(P, g, zl, w1, B, R, pixel_val_cpu, copy_done)
+
+    @staticmethod
+    def _train_outputs(P, g, zl, w1, B, R, pixel_val_cpu, copy_done) -> Dict[str, torch.Tensor]:
+        """render_train's tail for either train_precision: the decoder on z_local (fp32, LinearF32Fn), the white background
+        and the outputs; w1 = the round-1 softmax weights (at_wt)."""
+        from .train_fns import LinearF32Fn
+        dev = zl.device
         nray = B * R
         c18 = torch.zeros(nray, 32, dtype=torch.float32, device=dev)
         c18[:, :18] = g["coords9"].view(B, V, R, 9).permute(0, 2, 1, 3).reshape(nray, 18)

@@ -53,9 +53,10 @@ def weights(w: Dict[str, torch.Tensor], params: Dict[str, torch.Tensor]) -> Dict
     return w
 
 
-def node_tables(z, w: Dict[str, torch.Tensor], H: int, W: int, s) -> Tuple[torch.Tensor, torch.Tensor]:
+def node_tables(z, w: Dict[str, torch.Tensor], H: int, W: int, s, keep_feat: bool = False) -> Tuple[torch.Tensor, ...]:
     """(tab, map3): the three coarse levels sampled at every node of the common grid in fp32 and projected through the first
-    layer's column blocks, and the full-resolution level as NHWC fp32"""
+    layer's column blocks, and the full-resolution level as NHWC fp32; keep_feat: (tab, map3, feat), feat = the sampled
+    (nodes, 768) fp32 rows the projection read (train_precision="f32" keeps them for the weight gradient)"""
     maps = [t.detach().float().permute(0, 2, 3, 1).contiguous() for t in z]                          # NHWC fp32
     nimg = maps[0].shape[0]
     nodes = nimg * int(_hip.lib().cpn_encode_table_nodes(H, W))
@@ -63,7 +64,7 @@ def node_tables(z, w: Dict[str, torch.Tensor], H: int, W: int, s) -> Tuple[torch
     call("cpn_node_features_f32", maps[0].data_ptr(), maps[1].data_ptr(), maps[2].data_ptr(), H, W, nimg, feat.data_ptr(), s)
     tab = torch.empty(nodes, _hip.TAB_LD, dtype=torch.float32, device=feat.device)
     linear_f32(s, feat, 768, w["tab.w"], None, tab, _hip.TAB_LD, nodes, _hip.TAB_LD, 768, False)
-    return tab, maps[3]
+    return (tab, maps[3], feat) if keep_feat else (tab, maps[3])
 
 
 def per_sample(w, tables, g, zl, at_wt, dims, chunk: int, buf, s, rays: Optional[torch.Tensor] = None, nsel: int = 0) -> None:

@@ -249,7 +249,8 @@ class KeyLayerFn(Function):
 
 
 class LinearF32Fn(Function):
-    """Y = act_out(act_in(X) . W^T + b + res) through cpn_linear_f32 (exact fp32).  K % 16 == 0, N <= 128."""
+    """Y = act_out(act_in(X) . W^T + b + res) through cpn_linear_f32 (exact fp32).  K % 16 == 0; one launch per 128 output
+    columns (N <= 128: one launch)."""
 
     @staticmethod
     def forward(ctx, X, W, b, res, relu_in: bool, relu_out: bool):
@@ -259,8 +260,10 @@ class LinearF32Fn(Function):
         bc = None if b is None else b.detach().contiguous().float()
         rc = None if res is None else res.detach().contiguous().float()
         Y = torch.empty(M, N, dtype=torch.float32, device=X.device)
-        call("cpn_linear_f32", Xc.data_ptr(), K, Wc.data_ptr(), K, 0 if bc is None else bc.data_ptr(),
-             0 if rc is None else rc.data_ptr(), N, Y.data_ptr(), N, M, N, K, int(relu_in), int(relu_out), _stream())
+        for n0 in range(0, N, 128):
+            call("cpn_linear_f32", Xc.data_ptr(), K, Wc.data_ptr() + n0 * K * 4, K, 0 if bc is None else bc.data_ptr() + n0 * 4,
+                 0 if rc is None else rc.data_ptr() + n0 * 4, N, Y.data_ptr() + n0 * 4, N, M, min(128, N - n0), K, int(relu_in),
+                 int(relu_out), _stream())
         ctx.save_for_backward(Xc, Wc, Y if relu_out else None)
         ctx.relu_in, ctx.relu_out = relu_in, relu_out
         ctx.has_b, ctx.has_res = b is not None, res is not None

@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define CPN_ABI_VERSION 11
+#define CPN_ABI_VERSION 12
 
 #define CPN_E_ARG   (-1)   /* bad argument (null pointer, size, alignment) */
 #define CPN_E_SHAPE (-2)   /* shape not supported by the compiled tiles    */
@@ -293,6 +293,18 @@ int cpn_attend_hidden_bwd(const uint16_t* qa, const uint16_t* qb, const uint16_t
                           const float* dhbar, const float* dw_ext, int B, int V, int R, int S, int ray0, int nrays,
                           uint16_t* dqa, uint16_t* dqb, uint16_t* dhid, const uint16_t* dqb_acc, void* stream);
 
+/* gradient of cpn_attend_hidden_f32 (train_precision = "f32"): autograd's backward of the joint softmax over the 2 S samples
+ * of a ray and of the attention-weighted sum, models/CoPoNeRF.py:450-461 (round 1) and 475-485 (round 2) under
+ * wrapper.py:138, evaluated on the hidden activations as cpn_attend_hidden_f32 evaluates the forward.
+ * qa, qb (rays*V*S,128) fp32, hs (rays*V*S,3328) fp16 = [hi_own | hi_other | lo_own | lo_other] (cpn_encode_hidden_f32),
+ * at_wt (N,R,S) the forward weights, dhbar (rays,1664) fp32, dw_ext (N,R,S) fp32 or NULL -> dqa, dqb (rays*V*S,128) fp32,
+ * all in fp32: dw = <hi + lo, dhbar> + dw_ext, dl = w (dw - sum w dw) / 11.31, dqa = dl qb, dqb = dl qa (+ dqb_acc).
+ * dqb_acc (rays*V*S,128) fp32 or NULL: the other round's gradient of the shared qb (coords_embed), summed in.  hs's own
+ * gradient w (x) dhbar is left to cpn_gemm_f16_combine_hs.  Operands 16-byte aligned.                                   */
+int cpn_attend_hidden_bwd_f32(const float* qa, const float* qb, const uint16_t* hs, const float* at_wt, const float* dhbar,
+                              const float* dw_ext, int B, int V, int R, int S, int ray0, int nrays, float* dqa, float* dqb,
+                              const float* dqb_acc, void* stream);
+
 /* gradient w.r.t. the pre-activation of the first encoder layer from ALL consumers of hid, in one pass:
  *   out[row,c] = hid[row,c] > 0 ? dkey[row,c] + w1[n,r,s]*dh1[ray, j*832+c] + w2[n,r,s]*dh2[ray, j*832+c] : 0
  * dkey (rows, 832) fp16 or NULL = gradient through the key path; (w_i (N,R,S) fp32, dh_i (rays,1664) fp32) or NULL =
@@ -309,6 +321,15 @@ int cpn_hid_grad_combine(const uint16_t* dkey, const uint16_t* hid, const float*
 int cpn_gemm_f16_combine(const uint16_t* dkh, int lda, const uint16_t* Wt, int ldw, const uint16_t* hid, const float* w1,
                          const float* dh1, const float* w2, const float* dh2, int B, int V, int R, int S, int ray0,
                          int nrays, int K, uint16_t* out, void* stream);
+
+/* cpn_gemm_f16_combine with the mask read from the hi half of hs (rows, 3328) of cpn_encode_hidden_f32 (train_precision =
+ * "f32"): the data gradient of the folded key layer (models/CoPoNeRF.py:404-408 under wrapper.py:138, kh = ReLU(W' (hi + lo)
+ * + c')) plus the parked parts of the two attention sums (:450-461, 475-485), masked by hi > 0.  For a ReLU output hi > 0
+ * <=> hi + lo > 0 except below fp16's smallest subnormal.  out (rows, 1664) fp16, the layout of cpn_gemm_f16_combine;
+ * bit-identical to it run on a contiguous copy of the hi half.                                                             */
+int cpn_gemm_f16_combine_hs(const uint16_t* dkh, int lda, const uint16_t* Wt, int ldw, const uint16_t* hs, const float* w1,
+                            const float* dh1, const float* w2, const float* dh2, int B, int V, int R, int S, int ray0,
+                            int nrays, int K, uint16_t* out, void* stream);
 
 /* data gradient THROUGH a ReLU in one kernel:  out (M,N) fp16 = mask (M,N) > 0 ? A (M,K) . Wt (N,K)^T : 0  — grad_input of a
  * 1x1 Conv2d whose input `mask` is a ReLU output (key_map -> ReLU -> key_map_2, models/CoPoNeRF.py:404-408: autograd's

@@ -20,6 +20,9 @@ def main():
     ap.add_argument("--sort-rays", choices=("none", "rowmajor", "tiles"), default="none",
                     help="order of the query pixels inside each pair (the dataset draws them at random): locality experiment")
     ap.add_argument("--cudnn-benchmark", action="store_true", help="let the convolution library time its algorithms (MIOpen find)")
+    ap.add_argument("--train-precision", choices=("f16", "f32"), default="f16",
+                    help="RenderEngine.train_precision of the render path (f32: the reference's arithmetic, train_f32.py)")
+    ap.add_argument("--trunk-f32", action="store_true", help="the trunk's fp32 backward (encoder.trunk_bwd.enabled = False)")
     a = ap.parse_args()
     torch.backends.cudnn.benchmark = a.cudnn_benchmark
     dev = torch.device("cuda:0")
@@ -27,6 +30,8 @@ def main():
     shapes = {k: tuple(v.shape) for k, v in model.state_dict().items()}
     model.load_state_dict(syn.make_full_weights(shapes), strict=True)
     model = model.to(dev).train()
+    model._engine.train_precision = a.train_precision
+    model.encoder.trunk_bwd.enabled = not a.trunk_f32
     inp = syn.make_inputs(a.batch, 256, 256, a.rays, seed=61)
     mv = lambda o: {k: mv(v) for k, v in o.items()} if isinstance(o, dict) else (o.to(dev) if torch.is_tensor(o) else o)
     if a.sort_rays != "none":
@@ -64,7 +69,7 @@ def main():
         ph["host_enqueue_ms"] = min(host)
         print(json.dumps({"train_ms_per_step": dt * 1e3, "rays_per_s": a.batch * a.rays / dt, **{k: round(v, 3) for k, v in ph.items()},
                           "peak_mem_GB": torch.cuda.max_memory_allocated() / 2**30, "batch": a.batch, "rays_per_pair": a.rays,
-                          "stepped": bool(res["stepped"]), "loss": float(res["loss"])}))
+                          "train_precision": a.train_precision, "trunk_f32": a.trunk_f32, "stepped": bool(res["stepped"]), "loss": float(res["loss"])}))
         return
     opt = torch.optim.Adam(model.parameters(), lr=1e-5)
     ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
