@@ -11,6 +11,7 @@
 #include <algorithm>
 
 #include "common.h"
+#include "hid_sum.h"
 
 namespace {
 
@@ -126,17 +127,12 @@ __device__ __forceinline__ void attend_hidden_ray(const unsigned lray, float* __
 #pragma unroll
             for (int u = 0; u < U; ++u) h[u] = ld(row + u);
 #pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const float w = wts[row + u];
-#pragma unroll
-                for (int e = 0; e < 8; ++e) acc[e] += w * (float)h[u][e];
-            }
+            for (int u = 0; u < U; ++u) hid_row_acc<U % HID_BLOCK_ROWS == 0>(acc, wts[row + u], h[u]);      // (rounding: hid_sum.h)
         }
         for (; row < T; ++row) {
             const half8 h = ld(row);
-            const float w = wts[row];
-#pragma unroll
-            for (int e = 0; e < 8; ++e) acc[e] += w * (float)h[e];
+            if (U != HID_BLOCK_ROWS && row < T - T % HID_BLOCK_ROWS) hid_row_acc<true>(acc, wts[row], h);
+            else hid_row_acc<false>(acc, wts[row], h);
         }
         half8 o;
 #pragma unroll

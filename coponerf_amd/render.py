@@ -372,6 +372,7 @@ class RenderEngine:
     WORKSPACE_SHARE = 0.25
     FREE_SHARE = 0.5                # ... and at most this share of the memory that is free when the workspace is sized
     MAX_AUTO_CHUNK = 65536
+    ATTEND_UNITS_MAX_T = 1684       # (160 KiB of LDS - 81 KiB of round-2 weights) / (3 x 4 rays x 4 bytes), csrc/attend_units.hip
     FEW_ROWS = 4096                 # per-ray GEMMs of at most this many rows take the few-row kernel (cpn_gemm_f16_fewrows: 17 vs 35 us at 3 641)
     # precision="auto": default guard threshold on the score sum_i w_i (1 - w_i) |l_i|: half the smallest score of a ray whose
     # fp16 rgb was off by > 5e-4 or a weight by > 1e-3 in the calibration sweep (tools/auto_calibrate.py)
@@ -386,8 +387,8 @@ class RenderEngine:
         # ONE per-sample formulation (round 6; rounds 2-5 kept their predecessors as switchable modes - gather + GEMM first layer,
         # un-fused key layer, row-order tails, stored coords_embed, layer-by-layer values, "project before you store": they are
         # in tools/experiments/r6_pruned/ with the measurements that retired them in HISTORY.md): node tables + K = 80 MFMA first
-        # layer with the folded key layer behind it (cpn_encode_key), the query / key tails in unit order (cpn_local_units), both
-        # attention rounds on the hidden activations with the folded value projection per ray (cpn_attend_hidden + cpn_gemm_f16).
+        # layer with the folded key layer behind it (cpn_encode_key), the query / key tails in unit order and both attention
+        # rounds on the hidden activations, one launch per round (cpn_attend_units), the folded value projection per ray (cpn_gemm_f16).
         # rays per chunk of the per-sample stages; 0 = automatic (`_auto_chunk`): one 65 536-ray image is ONE chunk on a
         # 288 GB MI355X (28 GB of `hid` at 64 samples) — 4 launches of each per-sample kernel instead of 16 shave the
         # ramp / tail of the persistent grids: 26.6 -> 24.7 ms per image against chunks of 16 384
@@ -1098,6 +1099,10 @@ class RenderEngine:
         score = self._buf("guard.score", (nray_total,), f32, dev) if auto else None
         C = min(self.chunk_rays if self.chunk_rays > 0 else self._auto_chunk(S, dev, nray_total), nray_total)
         T = V * S                       # rows per ray for the attention stage
+        # one launch per attention round (cpn_attend_units) as far as a ray group's logits and weights fit the CU's LDS beside the
+        # layer-2 weights; more samples per ray than that (S > 842) take the two kernels the launch is made of, which hand the
+        # logits over through memory: same results, the only shapes cpn_attend_units rejects
+        fused = T <= self.ATTEND_UNITS_MAX_T
         nchunks = (nray_total + C - 1) // C
         nlanes = min(self.lanes, nchunks)
         if nlanes > 1 and (len(self._lane_streams) < nlanes or self._lane_streams[0].device != dev):
@@ -1109,7 +1114,9 @@ class RenderEngine:
             # kh in unit order: 16 rows per unit incl. the dead rows of partial units (at most one ray group more per batch
             # element and chunk edge)
             rows128 = ((C + 3) // 4 + B + 1) * V * ((S + 3) // 4) * 16
-            return {"lg": t("lg", (C * T,), f32),
+            # (lg: the raw logits in row order - the guard's input with precision = "auto", the hand-over of the two-kernel pair
+            #  beyond what cpn_attend_units holds in LDS; otherwise the logits never leave the CU)
+            return {"lg": t("lg", (C * T,), f32) if (auto or not fused) else None,
                     "z1": t("z1", (C, 416), f32), "ze": t("ze", (C, 128), f32), "addq": t("addq", (C, 128), f32),
                     "hbar": t("hbar", (C, 1664), f16), "zs": t("zs", (C, 416), f32),
                     "hid": t("hid", (C * T * 2, 832), f16), "khf": t("khf", (rows128, 128), f16)}
@@ -1146,41 +1153,51 @@ class RenderEngine:
                 "cpn_encode_key", tabs[0].data_ptr(), maps[3].data_ptr(), H, W, pixel_val.data_ptr(), sec_grid.data_ptr(),
                 pe6.data_ptr(), w["enc.frag"].data_ptr(), w["query_encode_latent.b"].data_ptr(), w["key_fold.wpk"].data_ptr(),
                 w["key_fold.b"].data_ptr(), B, V, R, S, ray0, n, bf["hid"].data_ptr(), bf["khf"].data_ptr(), 1, s))
-            # G: coords_embed (both query_embed layers), key_map_2 on kh and <key, coords_embed>; nothing but the logit is stored
-            #    [:408, :446, :450]
-            timed("local_units:query_embed+key_map_2", 2.0 * n * T * 128 * (128 + 128 + 16), lambda: call(
-                "cpn_local_units", 0, loc8.data_ptr(), coords9.data_ptr(), w["query_embed.w"].data_ptr(), 16,
-                w["query_embed.b"].data_ptr(), 0, w["query_embed_2.w16"].data_ptr(), 128, w["query_embed_2.b"].data_ptr(),
-                w["key_map_2.w16"].data_ptr(), 128, w["key_map_2.b"].data_ptr(), 0, 0, 0, bf["khf"].data_ptr(), B, V, R, S,
-                ray0, n, 0, lvu.data_ptr(), bf["lg"].data_ptr(), s))
+            # G A1: coords_embed (both query_embed layers), key_map_2 on kh, <key, coords_embed>, and behind them - in the SAME launch,
+            #    for other rays of the chunk - the joint softmax over the 2 x S samples of a ray + the weighted hidden sum, round 1
+            #    (cpn_attend_units; the logits reach the sum through LDS)  [:408, :446, :450-461]
+            lg = bf["lg"].data_ptr() if (auto or not fused) else 0
+            r1 = (0, loc8.data_ptr(), coords9.data_ptr(), w["query_embed.w"].data_ptr(), 16,
+                  w["query_embed.b"].data_ptr(), 0, w["query_embed_2.w16"].data_ptr(), 128, w["query_embed_2.b"].data_ptr(),
+                  w["key_map_2.w16"].data_ptr(), 128, w["key_map_2.b"].data_ptr(), 0, 0, 0, bf["khf"].data_ptr())
+            if fused:
+                timed("attend_units:round1", 2.0 * n * T * (128 * (128 + 128 + 16) + 1664), lambda: call(
+                    "cpn_attend_units", *r1, bf["hid"].data_ptr(), B, V, R, S, ray0, n, lvu.data_ptr(),
+                    bf["hbar"].data_ptr(), at_wt.data_ptr(), lg, s))
+            else:
+                timed("local_units:query_embed+key_map_2", 2.0 * n * T * 128 * (128 + 128 + 16), lambda: call(
+                    "cpn_local_units", *r1, B, V, R, S, ray0, n, 0, lvu.data_ptr(), lg, s))
+                timed("attend_hidden:round1", 2.0 * n * T * 1664, lambda: call(
+                    "cpn_attend_hidden", 0, 0, lg, bf["hid"].data_ptr(), B, V, R, S, ray0, n,
+                    bf["hbar"].data_ptr(), at_wt.data_ptr(), s))
             if auto:                    # guard score of round 1 (before round 2 overwrites lg)
                 timed("logit_guard:round1", 0.0, lambda: call(
-                    "cpn_logit_guard", bf["lg"].data_ptr(), B, V, R, S, ray0, n, score.data_ptr(), 0, s))
-            # A1: joint softmax over the 2 x S samples of a ray + the weighted hidden sum, round 1  [:450-461]
-            timed("attend_hidden:round1", 2.0 * n * T * 1664, lambda: call(
-                "cpn_attend_hidden", 0, 0, bf["lg"].data_ptr(), bf["hid"].data_ptr(), B, V, R, S, ray0, n,
-                bf["hbar"].data_ptr(), at_wt.data_ptr(), s))
-            # V1 L M2: value projection of the round-1 sum, encode_latent, the second query and its logits (coords_embed formed
-            #    again from the local coordinates: cpn_local_units mode 2)  [:467-475]
+                    "cpn_logit_guard", lg, B, V, R, S, ray0, n, score.data_ptr(), 0, s))
+            # V1 L M2 A2: value projection of the round-1 sum, encode_latent, the second query, its logits (coords_embed formed
+            #    again from the local coordinates: mode 2) and round 2 of the attention  [:467-485]
             z1, ze, addq = bf["z1"], bf["ze"], bf["addq"]
             value_fold(s, bf["hbar"], z1, n)
             call("cpn_linear_f32", z1.data_ptr(), 416, w["encode_latent.w"].data_ptr(), 416,
                  w["encode_latent.b"].data_ptr(), 0, 0, ze.data_ptr(), 128, n, 128, 416, 0, 0, s)
             call("cpn_linear_f32", ze.data_ptr(), 128, w["query_repeat_embed.w_z"].data_ptr(), 128, 0, 0, 0,
                  addq.data_ptr(), 128, n, 128, 128, 0, 0, s)
-            timed("local_units:round2+query_embed", 2.0 * n * T * 128 * (2 * 128 + 2 * 16), lambda: call(
-                "cpn_local_units", 2, loc8.data_ptr(), coords9.data_ptr(), w["query_repeat_embed.w_l"].data_ptr(), 16,
-                w["query_repeat_embed.b"].data_ptr(), addq.data_ptr(), w["query_repeat_embed_2.w16"].data_ptr(), 128,
-                w["query_repeat_embed_2.b"].data_ptr(), w["query_embed_2.w16"].data_ptr(), 128, w["query_embed_2.b"].data_ptr(),
-                w["query_embed.w"].data_ptr(), 16, w["query_embed.b"].data_ptr(), 0, B, V, R, S, ray0, n, 0,
-                lvu.data_ptr(), bf["lg"].data_ptr(), s))
+            r2 = (2, loc8.data_ptr(), coords9.data_ptr(), w["query_repeat_embed.w_l"].data_ptr(), 16,
+                  w["query_repeat_embed.b"].data_ptr(), addq.data_ptr(), w["query_repeat_embed_2.w16"].data_ptr(), 128,
+                  w["query_repeat_embed_2.b"].data_ptr(), w["query_embed_2.w16"].data_ptr(), 128, w["query_embed_2.b"].data_ptr(),
+                  w["query_embed.w"].data_ptr(), 16, w["query_embed.b"].data_ptr(), 0)
+            if fused:
+                timed("attend_units:round2", 2.0 * n * T * (128 * (2 * 128 + 2 * 16) + 1664), lambda: call(
+                    "cpn_attend_units", *r2, bf["hid"].data_ptr(), B, V, R, S, ray0, n, lvu.data_ptr(),
+                    bf["hbar"].data_ptr(), 0, lg, s))
+            else:
+                timed("local_units:round2+query_embed", 2.0 * n * T * 128 * (2 * 128 + 2 * 16), lambda: call(
+                    "cpn_local_units", *r2, B, V, R, S, ray0, n, 0, lvu.data_ptr(), lg, s))
+                timed("attend_hidden:round2", 2.0 * n * T * 1664, lambda: call(
+                    "cpn_attend_hidden", 0, 0, lg, bf["hid"].data_ptr(), B, V, R, S, ray0, n,
+                    bf["hbar"].data_ptr(), 0, s))
             if auto:                    # ... max'ed with round 2's
                 timed("logit_guard:round2", 0.0, lambda: call(
-                    "cpn_logit_guard", bf["lg"].data_ptr(), B, V, R, S, ray0, n, score.data_ptr(), 1, s))
-            # A2: round 2 of the attention  [:475-485]
-            timed("attend_hidden:round2", 2.0 * n * T * 1664, lambda: call(
-                "cpn_attend_hidden", 0, 0, bf["lg"].data_ptr(), bf["hid"].data_ptr(), B, V, R, S, ray0, n,
-                bf["hbar"].data_ptr(), 0, s))
+                    "cpn_logit_guard", lg, B, V, R, S, ray0, n, score.data_ptr(), 1, s))
             # V2: value projection of the round-2 sum; the round-1 vector sits in both view slots when the views are summed
             #    (CoPoNeRF.py:481-485)
             value_fold(s, bf["hbar"], bf["zs"], n)

@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define CPN_ABI_VERSION 12
+#define CPN_ABI_VERSION 12   /* cpn_attend_units (round 7) is additive - one more symbol, none altered: the version stays */
 
 #define CPN_E_ARG   (-1)   /* bad argument (null pointer, size, alignment) */
 #define CPN_E_SHAPE (-2)   /* shape not supported by the compiled tiles    */
@@ -190,6 +190,21 @@ int cpn_gemm_f16_fewrows(const uint16_t* A, int lda, const uint16_t* Wp, const f
  *   formed them (cpn_local_units); then qa, qb may be NULL                                                     */
 int cpn_attend_hidden(const uint16_t* qa, const uint16_t* qb, const float* logits, const uint16_t* hid, int B, int V,
                       int R, int S, int ray0, int nrays, uint16_t* hbar, float* at_wt, void* stream);
+
+/* ---- one attention round in ONE launch (round 7, csrc/attend_units.hip): cpn_local_units(mode) followed by
+ * cpn_attend_hidden(logits = ...) for the rays [ray0, ray0 + nrays), bit for bit, with the logit arithmetic of one ray group (4
+ * adjacent rays) running under the hid stream of another (wave-specialised persistent workgroups, hand-over through LDS).
+ * Replaces CoPoNeRF.py:408, 446, 450-461 (mode 0, round 1) and :472-485 (mode 2, round 2).
+ *   mode, loc8 .. kh_u, lv_u: as cpn_local_units (no ce_u: mode 0 stores no coords_embed).  hid, hbar, at_wt (or NULL): as
+ *   cpn_attend_hidden.  logits (nrays*V*S) fp32 or NULL: when given, the raw row dot products cpn_local_units would have stored
+ *   (before the / 11.31; what cpn_logit_guard reads) are stored as well.
+ *   V*S is bounded by the CU's LDS: the layer-2 weights (73 / 81 KiB) + 3 x 4 rays x V*S floats must fit 160 KiB
+ *   (V*S <= 1 856 in mode 0, <= 1 684 in mode 2; CPN_E_SHAPE beyond).                                                       */
+int cpn_attend_units(int mode, const float* loc8, const float* coords9, const float* w1, int ldw1, const float* b1,
+                     const float* add, const uint16_t* w2, int ldw2, const float* b2, const uint16_t* wk2, int ldwk2,
+                     const float* bk2, const float* w1b, int ldw1b, const float* b1b, const uint16_t* kh_u, const uint16_t* hid,
+                     int B, int V, int R, int S, int ray0, int nrays, const float* lv_u, uint16_t* hbar, float* at_wt,
+                     float* logits, void* stream);
 
 /* ---- K5: exact-fp32 per-ray linear layer (MFMA 16x16x4 f32)  Y = act_out( act_in(X) . W^T + bias + res ) --
  * replaces nn.Conv1d encode_latent (CoPoNeRF.py:468) and lightfield.ResnetFC (models/lightfield.py:131-167).
