@@ -272,7 +272,7 @@ def test_encode_hidden_against_torch(dev):
     fill the 4-ray x 4-sample units."""
     from coponerf_amd import _hip
     from coponerf_amd._hip import call
-    from oracle.render_ref import gather_levels
+    from tests.encode_bwd_ref import encode_input_ref
     torch.manual_seed(5)
     B, V, R, S, H = 1, 2, 9, 20, 64                       # 9*2*20*2 = 720 rows = 5.6 tiles
     N = B * V
@@ -317,12 +317,8 @@ def test_encode_hidden_against_torch(dev):
     _encode_first_layer(dev, (tab.data_ptr(), maps[3].data_ptr(), H, H, pvd.data_ptr(), sgd.data_ptr(), ped.data_ptr()), frag, b1d,
                         B, V, R, S, 0, B * R, hid)
     # ---- fp32 reference: grid_sample on the fp16-rounded maps, then the layer in float64
-    prim = gather_levels(z, pv, "border").view(B, V, R, S, 832)
-    z_swapped = [t.view(B, V, *t.shape[1:]).flip(1).reshape(t.shape) for t in z]
-    sec = gather_levels(z_swapped, sg, "zeros").view(B, V, R, S, 832)
-    pe5 = pe.view(B, V, R, S, 6)
-    x = torch.stack((torch.cat((prim, pe5[..., 0:3]), -1), torch.cat((sec, pe5[..., 3:6]), -1)), dim=4)   # (B,V,R,S,2,835)
-    x = x.permute(0, 2, 1, 3, 4, 5).reshape(rows, 835)                                                     # row order
+    x = encode_input_ref(z, pv, sg, pe, B, V, R, S, torch.float32)                                         # (rows, 835), row order
+    assert x.shape == (rows, 835)
     want = torch.relu(x.double() @ W1.double().t() + b1.double()).float()
     got = hid.float().cpu()
     assert torch.isfinite(got).all()
@@ -347,7 +343,7 @@ def test_encode_hidden_ragged_ranges(B, R, S, ray0, nrays, dev):
     grid_sample + the layer in float64 on the same fp16-rounded maps, rows outside it are not written at all."""
     from coponerf_amd import _hip
     from coponerf_amd._hip import call
-    from oracle.render_ref import gather_levels
+    from tests.encode_bwd_ref import encode_input_ref, chunk_rows
     g = torch.Generator().manual_seed(1000 * B + 10 * R + S)
     V, H = 2, 32
     N = B * V
@@ -385,12 +381,8 @@ def test_encode_hidden_ragged_ranges(B, R, S, ray0, nrays, dev):
     _encode_first_layer(dev, (tab.data_ptr(), maps[3].data_ptr(), H, H, pvd.data_ptr(), sgd.data_ptr(), ped.data_ptr()), frag, b1d,
                         B, V, R, S, ray0, nrays, hid)
     torch.cuda.synchronize()
-    prim = gather_levels(z, pv, "border").view(B, V, R, S, 832)
-    z_swapped = [t.view(B, V, *t.shape[1:]).flip(1).reshape(t.shape) for t in z]
-    sec = gather_levels(z_swapped, sg, "zeros").view(B, V, R, S, 832)
-    pe5 = pe.view(B, V, R, S, 6)
-    x = torch.stack((torch.cat((prim, pe5[..., 0:3]), -1), torch.cat((sec, pe5[..., 3:6]), -1)), dim=4)   # (B,V,R,S,2,835)
-    x = x.permute(0, 2, 1, 3, 4, 5).reshape(B * R, V * S * 2, 835)[ray0:ray0 + nrays].reshape(rows, 835)    # the chunk's rows
+    x = chunk_rows(encode_input_ref(z, pv, sg, pe, B, V, R, S, torch.float32), B, V, R, S, ray0, nrays)    # the chunk's rows
+    assert x.shape == (rows, 835)
     ref = torch.relu(x.double() @ W1.double().t() + b1.double()).float()
     got = hid[:rows].float().cpu()
     assert torch.isfinite(got).all(), "rows of the chunk left unwritten"
