@@ -4,7 +4,8 @@
     python coponerf_amd/csrc/build.py [--force]
 
 geometry.hip is compiled with -ffp-contract=off: its arithmetic must reproduce the oracle's
-IEEE operation sequence bit for bit (sample coordinates / tap indices).
+IEEE operation sequence bit for bit (sample coordinates / tap indices); ssim_warp.hip likewise, for the
+sampling coordinates of the flow warp (its window sums name their FMAs).
 """
 import os
 import subprocess
@@ -41,6 +42,7 @@ UNITS = [
     ("adam.hip", []),
     ("trunk_conv.hip", []),
     ("pose.hip", []),
+    ("ssim_warp.hip", ["-ffp-contract=off"]),
 ]
 
 

@@ -1,7 +1,8 @@
 """One data-parallel training step of the drop-in model, as the reference's loop performs it.
 
-Mirrors /root/reference wrapper.py:104-151 for the default loss configuration (image loss only,
-models/loss_function.py:65-71, 105-108): forward with `val=False` (get_z inside), `|gt - rgb|.mean()`, backward,
+Mirrors /root/reference wrapper.py:104-151 with the reference's loss, every flag (models/loss_function.py:89-137; `loss`, a
+losses.LossConfig, holds the `--cycle --pose --ssim` switches; the default is the image loss alone,
+loss_function.py:65-71, 105-108): forward with `val=False` (get_z inside), the loss terms summed, backward,
 invalid-gradient guard, `clip_grad_norm_(max_norm=1)` BEFORE the exchange (wrapper.py:142-148), gradient averaging,
 Adam step.  The exchange and the guard are the RCCL-friendly forms of coponerf_amd/dist.py: one MIN-all-reduced finite
 flag (every rank takes the same branch: no deadlock) and a few flat buckets instead of <= 636 blocking per-parameter
@@ -16,6 +17,7 @@ from typing import Dict, Optional
 import torch
 
 from . import dist as cdist
+from .losses import LossConfig, loss_terms
 
 
 class _LazyFlag:
@@ -40,10 +42,13 @@ class _LazyFlag:
 
 class TrainStep:
     def __init__(self, model: torch.nn.Module, lr: float = 5e-5 * 4, clip_grad: float = 1.0,
-                 bucket_bytes: int = 64 << 20, group=None, force_collectives: bool = False, exchange: bool = True):
-        """exchange=False: never exchange gradients, even inside an initialised process group (every rank for itself: the
+                 bucket_bytes: int = 64 << 20, group=None, force_collectives: bool = False, exchange: bool = True,
+                 loss: LossConfig = LossConfig()):
+        """loss: which terms join the image loss (losses.LossConfig: the reference's --cycle / --pose / --ssim).
+        exchange=False: never exchange gradients, even inside an initialised process group (every rank for itself: the
         single-GPU step measured beside the N-rank one, bench.py `ms_per_step_without_exchange`)."""
         self.model = model
+        self.loss_cfg = loss
         self.exchange_enabled = bool(exchange)
         self.params = [p for p in model.parameters()]
         # train.py:102-105 (both groups share lr); where the parameters live on the GPU the update of all 636 tensors is ONE
@@ -135,8 +140,11 @@ class TrainStep:
                 self._adapt_grad_scale(bool(self._pending.popleft()))
         e0 = self._ev() if timed else None
         out = self.model(model_input, val=False)
-        zero = lambda t: torch.where(torch.isnan(t), torch.zeros_like(t), t)      # loss_function.py:66-69
-        loss = (zero(gt_rgb) - zero(out["rgb"])).abs().mean()
+        terms = loss_terms(self.loss_cfg, model_input, out, gt_rgb)
+        loss = terms["img_loss"]
+        for name, term in terms.items():                                          # wrapper.py:109-123: the sum of the terms
+            if name != "img_loss":
+                loss = loss + term
         e1 = self._ev() if timed else None
         loss.backward()
         e2 = self._ev() if timed else None
@@ -197,7 +205,8 @@ class TrainStep:
         e5 = self._ev() if timed else None
         if timed:
             self.timing.setdefault("events", []).append((e0, e1, e2, e3, e4, e5))
-        return {"loss": loss.detach(), "stepped": stepped, "collectives": ncoll, "allreduce_bytes": nbytes,
+        return {"loss": loss.detach(), "losses": {k: v.detach() for k, v in terms.items()}, "stepped": stepped,
+                "collectives": ncoll, "allreduce_bytes": nbytes,
                 "host_reads": (0 if on_device else 1) + (0 if ex is None else ex.host_reads - reads_before),
                 "mask_exchanges": 0 if ex is None else ex.mask_exchanges,
                 "at_wt": out["at_wt"].detach(), "ray_order": ray_order, "skipped_in_a_row": self.skipped_in_a_row}

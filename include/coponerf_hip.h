@@ -654,6 +654,26 @@ int cpn_corr_mean3(const float* c0, int h0, const float* c1, int h1, const float
 int cpn_prepare_input(const uint8_t* frames_u8, int B, int Hs, int Ws, int y0, int x0, int H, int W, int R,
                       const int32_t* ray_pix, float* ctx_rgb, float* qry_rgb, void* stream);
 
+/* ==== the flow-warp SSIM term of the training loss, both directions of every pair in 2 + 2 launches (round 8) ===========
+ * replaces models/loss_function.py:19-60, 109-120 (gaussian / create_window / _ssim / SSIM and the `ssim` branch of
+ * LFLoss.__call__) with utils_training/utils.py:642-671 (`warp`) inside it; the validity masks of
+ * utils_training/utils.py:576-602 (get_gt_correspondence_mask) times the cycle check arrive as `mask`.
+ *   item k = 2 b + d: view 1 - d of rgb (B, 2, H, W, 3) fp32 (channels last, as the input dict stores it) warped by
+ *   s * bilinear(flow_d[b]) (flow_d (B, 2, h, w) fp32, align_corners=False, s = H / h = W / w in {1, 2, 4, 8}, CPN_E_SHAPE
+ *   otherwise) against view d, under mask (2B, H, W) bytes (item order) and the 11-tap `window` (fp32, sigma 1.5).
+ * cpn_ssim_warp writes coords (2B, 2, H, W): the fp32 sampling coordinates (ix, iy) in pixels; maps (2B, 9, H, W): per channel
+ *   the mask-weighted d(1 - ssim)/d(mu1, E[x^2], E[xy]); partial: 2 * 2B * cpn_ssim_warp_blocks(H, W) floats; sums (2B, 2):
+ *   (sum (1 - ssim) mask, sum mask) of every item; loss (2) and inv3den (2): per direction, over the batch as upstream
+ *   normalises it: sum_b num / sum_b den / 3 and 1 / (3 sum_b den).  An empty mask gives NaN, as upstream.
+ * cpn_ssim_warp_bwd: gout (2) = dL/dloss[d] and inv3den stay device scalars; gup (2B, 2, H, W) is scratch (the gradient of
+ *   the upsampled flow); dflow (2B, 2, h, w) is gathered per low-resolution cell.  No atomics in either: bit-reproducible. */
+int cpn_ssim_warp_blocks(int H, int W);
+int cpn_ssim_warp(const float* rgb, const float* flow0, const float* flow1, const uint8_t* mask, const float* window, int B,
+                  int H, int W, int h, int w, float* coords, float* maps, float* partial, float* sums, float* loss,
+                  float* inv3den, void* stream);
+int cpn_ssim_warp_bwd(const float* rgb, const float* coords, const float* maps, const float* window, const float* gout,
+                      const float* inv3den, int B, int H, int W, int h, int w, float* gup, float* dflow, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

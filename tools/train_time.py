@@ -23,6 +23,11 @@ def main():
     ap.add_argument("--train-precision", choices=("f16", "f32"), default="f16",
                     help="RenderEngine.train_precision of the render path (f32: the reference's arithmetic, train_f32.py)")
     ap.add_argument("--trunk-f32", action="store_true", help="the trunk's fp32 backward (encoder.trunk_bwd.enabled = False)")
+    ap.add_argument("--loss", default="image", help="comma-separated terms of the reference's loss: image,cycle,pose,ssim "
+                                                    "(losses.LossConfig; the image term is always on)")
+    ap.add_argument("--ssim-term", choices=("hip", "stock"), default="hip",
+                    help="the flow-warp SSIM term as csrc/ssim_warp.hip (the product) or as the stock-op composition of "
+                         "tests/ssim_ref.py (the yardstick: ~170 launches; not kept in the product)")
     a = ap.parse_args()
     torch.backends.cudnn.benchmark = a.cudnn_benchmark
     dev = torch.device("cuda:0")
@@ -44,8 +49,22 @@ def main():
     inp = mv(inp)
     if not (a.detach_z or a.flow_loss):
         # the product's own step (forward, loss, backward, guard + clip, one-launch Adam): coponerf_amd.train_step.TrainStep
+        from coponerf_amd import losses
         from coponerf_amd.train_step import TrainStep
-        step = TrainStep(model, lr=1e-5)
+        terms = set(a.loss.split(","))
+        if not terms <= {"image", "cycle", "pose", "ssim"}:
+            ap.error(f"--loss: unknown term in {a.loss}")
+        if a.ssim_term == "stock":
+            from coponerf_amd.aux_outputs import cycle_masks
+            from tests import ssim_ref
+            window = ssim_ref.window2d().to(dev)
+
+            def stock_ssim(ctx_rgb, flow0, flow1, masks=None):
+                with torch.no_grad():
+                    m0, m1 = cycle_masks((flow0.detach(), flow1.detach()), flow0.shape[2])
+                return (ssim_ref.stock_loss(ctx_rgb, flow0, m0, 0, window) + ssim_ref.stock_loss(ctx_rgb, flow1, m1, 1, window)) / 2
+            losses.ssim_warp_loss = stock_ssim
+        step = TrainStep(model, lr=1e-5, loss=losses.LossConfig(cycle="cycle" in terms, pose="pose" in terms, ssim="ssim" in terms))
         step.timing = {}
         gt = inp["query"]["rgb"]
         for it in range(a.warmup + a.steps):
@@ -69,7 +88,8 @@ def main():
         ph["host_enqueue_ms"] = min(host)
         print(json.dumps({"train_ms_per_step": dt * 1e3, "rays_per_s": a.batch * a.rays / dt, **{k: round(v, 3) for k, v in ph.items()},
                           "peak_mem_GB": torch.cuda.max_memory_allocated() / 2**30, "batch": a.batch, "rays_per_pair": a.rays,
-                          "train_precision": a.train_precision, "trunk_f32": a.trunk_f32, "stepped": bool(res["stepped"]), "loss": float(res["loss"])}))
+                          "train_precision": a.train_precision, "trunk_f32": a.trunk_f32, "stepped": bool(res["stepped"]), "loss": float(res["loss"]),
+                          "loss_terms": {k: float(v) for k, v in res["losses"].items()}, "ssim_term": a.ssim_term}))
         return
     opt = torch.optim.Adam(model.parameters(), lr=1e-5)
     ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
