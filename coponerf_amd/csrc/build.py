@@ -43,6 +43,7 @@ UNITS = [
     ("trunk_conv.hip", []),
     ("pose.hip", []),
     ("ssim_warp.hip", ["-ffp-contract=off"]),
+    ("image_metrics.hip", []),
 ]
 
 

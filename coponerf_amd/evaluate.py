@@ -1,0 +1,312 @@
+"""The reference's evaluation metrics (test.py:222-300), kept on the device.
+
+test.py turns every rendered validation pair into numbers on the host: five `.item()` reads, two images copied to numpy,
+`skimage.metrics.structural_similarity` twice on the CPU, and Python lists that `np.mean` / `torch.median` walk after every
+pair.  Here
+
+  image_metrics   MSE, PSNR and the 11-tap gaussian SSIM of N images: csrc/image_metrics.hip, 2 launches      test.py:227-229, 246-253, 267
+  pose_metrics    rotation geodesic, translation distance, translation angle: stock ops on (B, 4, 4)         test.py:34-48, 232-243
+  Evaluator       one row per image in a device-resident table; `summary()` makes the ONE host read and      test.py:160, 271-300
+                  returns the statistics of the reference's printed line for "all" / "small" / "medium" / "large"
+
+`Evaluator.add` reads no device value on the host and copies no pageable host memory, so it can follow
+`pipeline.render_images` without stalling it.  LPIPS is not shipped (its VGG weights are not part of this
+package): `Evaluator(extra={"lpips": fn})` takes any callable for it.
+"""
+from __future__ import annotations
+
+import math
+from collections import deque
+from typing import Callable, Dict, Iterable, List, Optional, Sequence, Tuple
+
+import torch
+
+from . import _hip
+
+COLUMNS = ("mse", "psnr", "ssim", "rot", "trans", "angle_trans", "overlap", "call")
+BUCKETS = ("small", "medium", "large")
+WIN = 11                                                  # structural_similarity(win_size=11): the smallest image side
+
+
+def _check(pred: torch.Tensor, target: torch.Tensor, image_shape: Optional[Sequence[int]]) -> Tuple[int, int, int]:
+    if not (torch.is_tensor(pred) and torch.is_tensor(target)):
+        raise TypeError("image_metrics: pred and target must be tensors")
+    if not (pred.is_cuda and target.is_cuda):
+        raise RuntimeError("image_metrics runs on the HIP device only (coponerf_amd has no non-HIP compute path)")
+    if pred.device != target.device:
+        raise ValueError(f"image_metrics: pred is on {pred.device}, target on {target.device}")
+    if pred.dtype != torch.float32 or target.dtype != torch.float32:
+        raise ValueError(f"image_metrics: fp32 tensors only, got {pred.dtype} and {target.dtype}")
+    if not (pred.is_contiguous() and target.is_contiguous()):
+        raise ValueError("image_metrics: pred and target must be contiguous (N, H, W, 3) images, or views of them")
+    if pred.dim() < 1 or pred.shape[-1] != 3 or target.dim() < 1 or target.shape[-1] != 3:
+        raise ValueError(f"image_metrics: channels last, got {tuple(pred.shape)} and {tuple(target.shape)}")
+    if image_shape is None:
+        if pred.dim() != 4:
+            raise ValueError(f"image_metrics: pass image_shape=(H, W) for a tensor of shape {tuple(pred.shape)}")
+        image_shape = pred.shape[1:3]
+    H, W = int(image_shape[0]), int(image_shape[1])
+    if H < WIN or W < WIN:
+        raise ValueError(f"image_metrics: the {WIN}-tap SSIM window needs H, W >= {WIN}, got {H} x {W}")
+    per = H * W * 3
+    if pred.numel() == 0 or pred.numel() % per or pred.numel() != target.numel():
+        raise ValueError(f"image_metrics: {tuple(pred.shape)} and {tuple(target.shape)} are not the same number of "
+                         f"{H} x {W} x 3 images")
+    return pred.numel() // per, H, W
+
+
+def image_metrics(pred: torch.Tensor, target: torch.Tensor, image_shape: Optional[Sequence[int]] = None) -> torch.Tensor:
+    """(N, 3) fp32 on the device: mse, psnr (dB), ssim of every image, as test.py:227-229, 246-253, 267 compute them.
+
+    pred, target: contiguous fp32 (N, H, W, 3) in the model's range [-1, 1], or any contiguous view of that memory such as
+    the (B, 1, H*W, 3) of `forward(val=True)['rgb']` and `gt['rgb']` with image_shape=(H, W).  Only the prediction is clamped;
+    a NaN sample makes its image's three values NaN.  Bit-reproducible, and an image's values do not depend on N."""
+    N, H, W = _check(pred, target, image_shape)
+    n = _hip.lib().cpn_image_metrics_scratch(N, H, W)
+    if n <= 0:
+        raise ValueError(f"image_metrics: {N} images of {H} x {W} are too many for one launch")
+    partial = torch.empty(n, dtype=torch.float32, device=pred.device)
+    out = torch.empty(N, 3, dtype=torch.float32, device=pred.device)
+    with torch.cuda.device(pred.device):
+        _hip.call("cpn_image_metrics", pred.data_ptr(), target.data_ptr(), N, H, W, partial.data_ptr(), out.data_ptr(),
+                  _hip.stream_handle())
+    return out
+
+
+def pose_metrics(rel_pose: torch.Tensor, gt_rel_pose: torch.Tensor) -> torch.Tensor:
+    """(B, 3): rotation geodesic in RADIANS (the reference calls it `rot_distance_degrees`; acos returns radians and nothing
+    converts them - test.py:34-48, 232), translation distance (test.py:235) and the angle between the two translation
+    directions in radians (test.py:238-243).  rel_pose, gt_rel_pose: (B, 4, 4) on the device."""
+    if rel_pose.dim() != 3 or tuple(rel_pose.shape[1:]) != (4, 4) or rel_pose.shape != gt_rel_pose.shape:
+        raise ValueError(f"pose_metrics: two (B, 4, 4) poses, got {tuple(rel_pose.shape)} and {tuple(gt_rel_pose.shape)}")
+    if not (rel_pose.is_cuda and gt_rel_pose.is_cuda):
+        raise RuntimeError("pose_metrics runs on the HIP device only (coponerf_amd has no non-HIP compute path)")
+    m = torch.bmm(rel_pose[:, :3, :3], gt_rel_pose[:, :3, :3].transpose(1, 2))
+    cos = (m[:, 0, 0] + m[:, 1, 1] + m[:, 2, 2] - 1) / 2
+    rot = torch.acos(cos.clamp(-1.0, 1.0))
+    tp, tg = rel_pose[:, :3, 3], gt_rel_pose[:, :3, 3]
+    trans = torch.linalg.norm(tp - tg, dim=-1)
+    npred = tp / torch.linalg.norm(tp, dim=-1, keepdim=True)
+    ngt = tg / torch.linalg.norm(tg, dim=-1, keepdim=True)
+    angle = torch.acos((npred * ngt).sum(-1).clamp(-1.0, 1.0))
+    return torch.stack((rot, trans, angle), dim=-1)
+
+
+def bucket_of(overlap: float) -> Optional[str]:
+    """test.py:271-272; None for an image that came without an overlap."""
+    if overlap != overlap:
+        return None
+    return "large" if overlap > 0.75 else ("medium" if overlap >= 0.5 else "small")
+
+
+def _stats(values: Sequence[float]) -> Dict[str, float]:
+    """torch.mean / torch.median (the lower middle) / torch.std (unbiased; NaN for one value) of fp32 values, as the reference
+    takes them of its fp32 lists.  `rot` and `trans` are fp32 already; the "all" group's `angle_trans` entries are per-call
+    means formed in float64 and rounded to fp32 here, half an ulp from the reference's own fp32 mean."""
+    t = torch.tensor(list(values), dtype=torch.float32)
+    return {"mean": float(t.mean()), "median": float(t.median()), "std": float(t.std()) if t.numel() > 1 else float("nan")}
+
+
+def _mean(values: Sequence[float]) -> float:
+    return math.fsum(values) / len(values)                 # np.mean of Python floats, without its rounding
+
+
+def _to_device(obj, dev):
+    if torch.is_tensor(obj):
+        return obj if obj.device == dev else obj.to(dev, non_blocking=True)
+    if isinstance(obj, dict):
+        return {k: _to_device(v, dev) for k, v in obj.items()}
+    if isinstance(obj, (list, tuple)):
+        return type(obj)(_to_device(v, dev) for v in obj)
+    return obj
+
+
+class Evaluator:
+    """The bookkeeping of test.py:160, 222-300 as one device-resident table.
+
+        ev = Evaluator()
+        ev.run(model, val_loader, nchunks=18)        # or ev.add(model_output, gt, overlap) per rendered batch
+        print(ev.format_summary())
+
+    A row per image: COLUMNS, then one column per entry of `extra`.  The table is float64 (fp32 metrics, overlaps and call
+    indices are all exact in it), preallocated at `capacity` rows and doubled when it fills.  `host_reads` counts the device
+    -> host reads made here: `add` and `run` make none, `summary`, `format_summary` and `rows(host=True)` one each."""
+
+    def __init__(self, extra: Optional[Dict[str, Callable]] = None, capacity: int = 256, device=None):
+        self.extra: Dict[str, Callable] = dict(extra or {})
+        for name in self.extra:
+            if name in COLUMNS:
+                raise ValueError(f"Evaluator: extra metric {name!r} collides with a built-in column")
+        self.columns: Tuple[str, ...] = COLUMNS + tuple(self.extra)
+        self._capacity = max(1, int(capacity))
+        self._device = torch.device(device) if device is not None else None
+        self._table: Optional[torch.Tensor] = None
+        self._n = 0
+        self._calls = 0
+        self.host_reads = 0
+
+    def __len__(self) -> int:
+        return self._n
+
+    # ------------------------------------------------------------------------------------------------------ the table
+    def _reserve(self, rows: int, dev) -> None:
+        if self._table is None:
+            self._device = self._device or dev
+            while self._capacity < rows:
+                self._capacity *= 2
+            self._table = torch.empty(self._capacity, len(self.columns), dtype=torch.float64, device=self._device)
+        elif self._n + rows > self._capacity:
+            while self._capacity < self._n + rows:
+                self._capacity *= 2
+            grown = torch.empty(self._capacity, len(self.columns), dtype=torch.float64, device=self._device)
+            grown[:self._n] = self._table[:self._n]
+            self._table = grown
+
+    @staticmethod
+    def _overlap_column(overlap, B: int, dev) -> Optional[torch.Tensor]:
+        if overlap is None:
+            return None
+        if torch.is_tensor(overlap):
+            ov = overlap.detach().reshape(-1)
+            if not ov.is_cuda:                              # a loader's CPU tensor: pinned, so the copy does not wait
+                ov = ov.to(torch.float64).pin_memory().to(dev, non_blocking=True)
+        else:
+            overlap = list(overlap)
+            if any(torch.is_tensor(v) and v.is_cuda for v in overlap):     # float() of each would be a host read per image
+                raise TypeError("Evaluator.add: overlap holds device tensors; pass one tensor of length B, or host numbers")
+            ov = torch.tensor([float(v) for v in overlap], dtype=torch.float64).pin_memory().to(dev, non_blocking=True)
+        if ov.numel() != B:
+            raise ValueError(f"Evaluator.add: {ov.numel()} overlaps for {B} images")
+        return ov
+
+    @torch.no_grad()
+    def add(self, model_output: Dict, gt_rgb, overlap=None, image_shape: Optional[Sequence[int]] = None) -> None:
+        """One rendered batch (test.py:222-296): `model_output` is the joined dict of `forward(val=True)` / `render_images`
+        ('rgb', 'rel_pose', 'gt_rel_pose'), `gt_rgb` the ground truth (gt['rgb'], or the gt dict itself), `overlap` one value
+        per image (host sequence, tensor, or None: then the images join no bucket).  image_shape=(H, W); None takes a 4-D
+        (B, H, W, 3) shape as it is and a (B, 1, R, 3) one as square.  Enqueues device work only."""
+        rgb = model_output["rgb"].contiguous()              # as forward() and the chunk join return it: no copy
+        gt = (gt_rgb["rgb"] if isinstance(gt_rgb, dict) else gt_rgb).contiguous()
+        rel, gt_rel = model_output["rel_pose"], model_output["gt_rel_pose"]
+        B = int(rel.shape[0])
+        if image_shape is None and not (rgb.dim() == 4 and rgb.shape[1] > 1):
+            side = math.isqrt(rgb.numel() // (3 * B)) if B else 0
+            if side * side * 3 * B != rgb.numel():
+                raise ValueError(f"Evaluator.add: pass image_shape=(H, W) for rgb of shape {tuple(rgb.shape)}")
+            image_shape = (side, side)
+        N, H, W = _check(rgb, gt, image_shape)
+        if N != B:
+            raise ValueError(f"Evaluator.add: {N} images of {H} x {W} but {B} poses")
+        dev = rgb.device
+        ov = self._overlap_column(overlap, B, dev)
+        self._reserve(B, dev)
+        rows = self._table[self._n:self._n + B]
+        rows[:, 0:3] = image_metrics(rgb, gt, (H, W))
+        rows[:, 3:6] = pose_metrics(rel, gt_rel)
+        if ov is None:
+            rows[:, 6].fill_(float("nan"))
+        else:
+            rows[:, 6] = ov
+        rows[:, 7].fill_(float(self._calls))
+        if self.extra:
+            # test.py:258-259: both images back in [-1, 1], channels first; the prediction is the clamped one
+            p = rgb.view(B, H, W, 3).clamp(-1, 1).permute(0, 3, 1, 2)
+            t = gt.view(B, H, W, 3).permute(0, 3, 1, 2)
+            for j, fn in enumerate(self.extra.values()):
+                rows[:, len(COLUMNS) + j] = torch.as_tensor(fn(p, t), device=dev).reshape(B)
+        self._n += B
+        self._calls += 1
+
+    @torch.no_grad()
+    def run(self, model, loader: Iterable, nchunks: Optional[int] = None, image_shape: Optional[Sequence[int]] = None,
+            **render_images_kwargs) -> "Evaluator":
+        """test.py:161-296 over a validation loader that yields (model_input, gt, overlap) triples
+        (data/realestate10k_dataio.py:683): every batch rendered through `pipeline.render_images` (nchunks=18 is test.py's own
+        chunking) and added.  Tensors still on the host are moved to the model's device first, as utils.dict_to_gpu does."""
+        from .pipeline import render_images
+        dev = next(model.parameters()).device
+        pending: deque = deque()
+
+        def inputs():
+            for model_input, gt, overlap in loader:
+                pending.append((_to_device(gt, dev), overlap))
+                yield _to_device(model_input, dev)
+
+        for _, out in render_images(model, inputs(), nchunks=nchunks, **render_images_kwargs):
+            gt, overlap = pending.popleft()
+            self.add(out, gt, overlap, image_shape=image_shape)
+        return self
+
+    # ------------------------------------------------------------------------------------------------- reading it back
+    def rows(self, host: bool = False) -> torch.Tensor:
+        """The (images, len(columns)) float64 table: on the device (a copy; no host read), or with host=True on the CPU.
+        Before the first `add` it is empty, on the device the Evaluator was given (on the CPU if it was given none)."""
+        if self._table is None:                             # nothing added yet: no device is known unless one was given
+            return torch.empty(0, len(self.columns), dtype=torch.float64, device=None if host else self._device)
+        t = self._table[:self._n]
+        if host:
+            self.host_reads += 1
+            return t.cpu()
+        return t.clone()
+
+    def summary(self) -> Dict[str, Dict[str, float]]:
+        """{"all" | "small" | "medium" | "large": statistics}: what test.py:298-300 prints, from one host read.
+
+        Every group has `n`, mean `psnr` / `ssim` / `mse`, `{rot,trans,angle_trans}_{mean,median,std}` and a mean per extra.
+        A bucket (test.py:271-272 by the image's overlap) holds per-image values.  "all" follows test.py:246-280 per `add`
+        call: the MSE pooled over the call's images, the PSNR of that pooled MSE, the call's mean SSIM, translation angle and
+        extras, and `rot` / `trans` per image.  Groups without entries are omitted."""
+        table = self.rows(host=True).tolist()
+        c = {name: i for i, name in enumerate(self.columns)}
+        groups: Dict[str, Dict[str, List[float]]] = {}
+
+        def push(key: str, **values) -> None:
+            g = groups.setdefault(key, {})
+            for k, v in values.items():
+                g.setdefault(k, []).extend(v if isinstance(v, list) else [v])
+
+        calls: Dict[int, List[List[float]]] = {}
+        for r in table:
+            calls.setdefault(int(r[c["call"]]), []).append(r)
+            key = bucket_of(r[c["overlap"]])
+            if key is not None:
+                push(key, **{name: r[c[name]] for name in self.columns if name not in ("overlap", "call")})
+        for idx in sorted(calls):
+            rs = calls[idx]
+            mse = _mean([r[c["mse"]] for r in rs])          # equal-sized images: the mean over all their samples
+            psnr = -10.0 * math.log10(mse) if mse > 0 else (float("inf") if mse == 0 else float("nan"))
+            push("all", mse=mse, psnr=psnr, ssim=_mean([r[c["ssim"]] for r in rs]),
+                 rot=[r[c["rot"]] for r in rs], trans=[r[c["trans"]] for r in rs],
+                 angle_trans=_mean([r[c["angle_trans"]] for r in rs]),
+                 **{name: _mean([r[c[name]] for r in rs]) for name in self.extra})
+        out: Dict[str, Dict[str, float]] = {}
+        for key in ("all",) + BUCKETS:
+            g = groups.get(key)
+            if not g:
+                continue
+            s: Dict[str, float] = {"n": len(g["mse"])}
+            for name in ("psnr", "ssim", "mse"):
+                s[name] = _mean(g[name])
+            for name in ("rot", "trans", "angle_trans"):
+                for stat, v in _stats(g[name]).items():
+                    s[f"{name}_{stat}"] = v
+            for name in self.extra:
+                s[name] = _mean(g[name])
+            out[key] = s
+        return out
+
+    def format_summary(self, summary: Optional[Dict[str, Dict[str, float]]] = None) -> str:
+        """The line test.py:300 prints after every pair, one per group; extras are printed by their upper-cased names."""
+        summary = self.summary() if summary is None else summary
+        lines = []
+        for key, s in summary.items():
+            parts = [f"PSNR: {s['psnr']:.4f}", f"SSIM: {s['ssim']:.4f}"]
+            parts += [f"{name.upper()}: {s[name]:.4f}" for name in self.extra if name in s]
+            parts.append(f"MSE: {s['mse']:.4f}")
+            for label, name in (("Rot", "rot"), ("Trans", "trans")):
+                parts += [f"{label}_avg: {s[name + '_mean']:.4f}", f"{label}_median: {s[name + '_median']:.4f}",
+                          f"{label}_std: {s[name + '_std']:.4f}"]
+            parts += [f"Avg_Trans_angle: {s['angle_trans_mean']:.4f}", f"Med_Trans_angle: {s['angle_trans_median']:.4f}",
+                      f"std_Trans_angle: {s['angle_trans_std']:.4f}"]
+            lines.append(f"{key}: " + ", ".join(parts))
+        return "\n".join(lines)

@@ -674,6 +674,18 @@ int cpn_ssim_warp(const float* rgb, const float* flow0, const float* flow1, cons
 int cpn_ssim_warp_bwd(const float* rgb, const float* coords, const float* maps, const float* window, const float* gout,
                       const float* inv3den, int B, int H, int W, int h, int w, float* gup, float* dflow, void* stream);
 
+/* ==== the image metrics of the evaluation script, any number of images in 2 launches (round 9) ===========================
+ * replaces test.py:227-229 (clamp of the prediction, both images to [0, 1]), test.py:90-91, 246-253 (img2mse, mse2psnr per
+ * image) and test.py:265-268 (the two .cpu().numpy() copies and skimage.metrics.structural_similarity(win_size=11,
+ * gaussian_weights=True, channel_axis=-1, data_range=1) on the host).
+ *   pred, target (N, H, W, 3) fp32 in the model's range [-1, 1]; only pred is clamped, a NaN stays a NaN.
+ *   out (N, 3) fp32 = mse, psnr (dB; +inf at mse 0), ssim of every image: 11-tap sigma-1.5 separable window, scipy's
+ *   `reflect` boundary, C1 = 1e-4, C2 = 9e-4, the map cropped by 5 pixels on every side, mean over the channels.
+ *   H, W >= 11 (CPN_E_SHAPE otherwise: skimage raises there too).  partial: cpn_image_metrics_scratch(N, H, W) floats
+ *   (0 for a shape cpn_image_metrics rejects).  No atomics: bit-reproducible, and image n's values do not depend on N.      */
+int cpn_image_metrics_scratch(int N, int H, int W);
+int cpn_image_metrics(const float* pred, const float* target, int N, int H, int W, float* partial, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
