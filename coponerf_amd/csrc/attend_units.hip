@@ -38,16 +38,6 @@ constexpr int AU_THREADS = (NL + NS) * 64;
 constexpr int RU = HID_BLOCK_ROWS;       // rows per load block (= the blocks of hid_sum.h); up to two blocks in flight per lane and chunk
 constexpr int LDS_MAX = 160 * 1024;
 
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
-    return v;
-}
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
 // the workgroup barrier of a ray group: LDS writes done, nothing else waited for (global loads stay in flight across it)
 __device__ __forceinline__ void group_barrier() {
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");

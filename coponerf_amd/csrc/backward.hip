@@ -11,8 +11,7 @@
 //                          coordinates derive from poses only and `pt` is detached, CoPoNeRF.py:380-381, 433)
 #include <algorithm>
 
-#include "common.h"
-#include "taps.h"
+#include "encode_geometry.h"
 
 namespace {
 
@@ -265,11 +264,6 @@ namespace {
 
 constexpr int HC = 1664;
 
-__device__ __forceinline__ float wave_sum_f(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
 
 // One workgroup per ray.  T = V*S rows.
 //   dw[row]   = <hid[row], dhbar> + dw_ext[row]
@@ -314,7 +308,7 @@ __global__ __launch_bounds__(256) void attend_hidden_bwd_kernel(
         for (int k = 0; k < 4; ++k)
 #pragma unroll
             for (int e = 0; e < 8; ++e) acc += (float)h[k][e] * dreg[k][e];
-        return wave_sum_f(acc);
+        return wave_sum(acc);
     };
     auto load_row = [&](int row, half8 (&h)[4]) {
         const __half* hp = hid + (row0 + min(row, T - 1)) * HC;
@@ -436,7 +430,7 @@ __global__ __launch_bounds__(256) void attend_hidden_bwd_f32_kernel(
         for (int k = 0; k < 4; ++k)
 #pragma unroll
             for (int e = 0; e < 8; ++e) acc += ((float)h[k][e] + (float)l[k][e]) * dreg[k][e];
-        return wave_sum_f(acc);
+        return wave_sum(acc);
     };
     float part = 0.f;
     auto finish = [&](int row, float acc) {
@@ -559,41 +553,6 @@ struct GatherBwdPlan {
     int col0;                                              // first column of the level's channels in a gradient row
 };
 
-// the rows that read image `img`: idx in [0, 2*nr*S) -> (first j=0: own view at pixel_val, then j=1: other view at
-// sec_grid); same enumeration in both passes
-struct RowRef {
-    unsigned row;      // row of dxin
-    float2 g;          // normalised sample coordinate
-    int j;
-};
-__device__ __forceinline__ RowRef row_of(int idx, int per, int S, bool s_pow2, int s_shift, int rlo, int b, int vi, int V,
-                                         int R, int ray0, const float* __restrict__ pixel_val,
-                                         const float* __restrict__ sec_grid) {
-    RowRef o;
-    o.j = idx >= per;
-    const int rem = idx - o.j * per;
-    const int rr = s_pow2 ? (rem >> s_shift) : (rem / S);
-    const int sm = rem - rr * S;
-    const int r = rlo + rr;
-    const int v = o.j ? (V - 1 - vi) : vi;
-    const size_t sidx = (((size_t)(b * V + v)) * R + r) * S + sm;
-    o.g = *reinterpret_cast<const float2*>((o.j ? sec_grid : pixel_val) + sidx * 2);
-    o.row = ((((unsigned)(b * R + r - ray0)) * V + v) * S + sm) * 2 + o.j;
-    return o;
-}
-// pixel-space sample position at a level, with the clamps of make_taps
-__device__ __forceinline__ void level_xy(float2 g, int j, float fW, float fH, float& x, float& y) {
-    x = ((g.x + 1.0f) * fW - 1.0f) / 2.0f;
-    y = ((g.y + 1.0f) * fH - 1.0f) / 2.0f;
-    if (!j) {
-        x = fminf(fmaxf(x, 0.0f), fW - 1.0f);
-        y = fminf(fmaxf(y, 0.0f), fH - 1.0f);
-    } else {
-        x = fminf(fmaxf(x, -2.0f), fW + 1.0f);
-        y = fminf(fmaxf(y, -2.0f), fH + 1.0f);
-    }
-}
-
 // Conservative pixel boxes of the rows' footprints at ONE level, per 16-row QUARTER of a 64-row chunk (round 6).  A chunk
 // is one ray's samples along its epipolar line: the box of the whole line covers some 300 tiles of which 40 hold samples,
 // and the tiles' scan evaluated every row of every chunk whose box they touched (that scan, not the accumulation, was the
@@ -614,9 +573,8 @@ __global__ __launch_bounds__(256) void gather_bbox_kernel(
     int x0 = 1 << 30, y0 = 1 << 30, x1 = -(1 << 30), y1 = -(1 << 30);
     if (live) {
         const RowRef rf = row_of(idx, per, S, (S & (S - 1)) == 0, 31 - __builtin_clz(S), rlo, b, vi, V, R, ray0, pixel_val, sec_grid);
-        float x, y;
-        level_xy(rf.g, rf.j, (float)(W >> shift), (float)(H >> shift), x, y);
-        x0 = (int)floorf(x); y0 = (int)floorf(y);
+        const float2 p = level_xy(rf.g.x, rf.g.y, W >> shift, H >> shift, !rf.j);
+        x0 = (int)floorf(p.x); y0 = (int)floorf(p.y);
         x1 = x0 + 1; y1 = y0 + 1;
     }
 #pragma unroll
@@ -663,7 +621,6 @@ __global__ __launch_bounds__(64 * WAVES) void gather_rows_bwd_kernel(
     const int c_end = min(nchunks, (g + 1) * cpg);
     const bool s_pow2 = (S & (S - 1)) == 0;
     const int s_shift = 31 - __builtin_clz(S);
-    const float fW = (float)Wl, fH = (float)Hl;
     const int4* boxes = bbox + (size_t)img * plan.maxchunks * 4;          // [chunk][16-row quarter], this level
 
     auto drain = [&](int n) {
@@ -740,8 +697,8 @@ __global__ __launch_bounds__(64 * WAVES) void gather_rows_bwd_kernel(
             int flags = 0;
             if (idx < total) {
                 const RowRef rf = row_of(idx, per, S, s_pow2, s_shift, rlo, b, vi, V, R, ray0, pixel_val, sec_grid);
-                float x, y;
-                level_xy(rf.g, rf.j, fW, fH, x, y);
+                const float2 p = level_xy(rf.g.x, rf.g.y, Wl, Hl, !rf.j);
+                const float x = p.x, y = p.y;
                 const float xf = floorf(x), yf = floorf(y);
                 const int x0 = (int)xf, y0 = (int)yf;
                 const float fx = x - xf, fy = y - yf;

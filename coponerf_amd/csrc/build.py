@@ -53,7 +53,9 @@ def _newer(src, dst):
 
 def build(force=False, verbose=True):
     objs = []
-    deps = [os.path.join(HERE, "common.h"), os.path.join(HERE, "taps.h"), os.path.join(HERE, "encode_common.h"), os.path.join(HERE, "local_units_body.h"), os.path.join(HERE, "hid_sum.h"), os.path.join(HERE, "..", "..", "include", "coponerf_hip.h")]
+    # every header beside the sources, and the C interface: a changed header rebuilds every object
+    deps = sorted(os.path.join(HERE, f) for f in os.listdir(HERE) if f.endswith(".h"))
+    deps.append(os.path.join(HERE, "..", "..", "include", "coponerf_hip.h"))
     for name, extra in UNITS:
         src = os.path.join(HERE, name)
         obj = os.path.join(HERE, os.path.splitext(name)[0] + ".o")

@@ -79,19 +79,11 @@ __global__ void node_features_kernel(const __half* __restrict__ map0, const __ha
     const long long node = idx / 96;
     const int lvl = chunk >> 5, c8 = chunk & 31;
     const NodeGrid ng{W >> 1, H >> 1};
-    const long long npi = ng.nodes_per_image();
-    const int img = (int)(node / npi);
-    long long rem = node - (long long)img * npi;
-    const bool border = rem < ng.border_nodes();
-    if (!border) rem -= ng.border_nodes();
-    const int nw = border ? ng.bw() : ng.zw(), pad = border ? 0 : PAD;
-    const int ny = (int)(rem / nw) - pad, nx = (int)(rem % nw) - pad;
-    // node t <-> u = t / M <-> normalised g = 2u - 1 (exact when M is a power of two)
-    const float gx = (float)(2 * nx - ng.Mx) / (float)ng.Mx, gy = (float)(2 * ny - ng.My) / (float)ng.My;
+    const NodeId nd = node_of(node, ng);
     const int shift = 4 - lvl;
     const int Hl = H >> shift, Wl = W >> shift;
-    const Taps tp = make_taps(gx, gy, Wl, Hl, border);
-    const __half* m = (lvl == 0 ? map0 : lvl == 1 ? map1 : map2) + (size_t)img * Hl * Wl * 256 + c8 * 8;
+    const Taps tp = make_taps(nd.gx, nd.gy, Wl, Hl, nd.border);
+    const __half* m = (lvl == 0 ? map0 : lvl == 1 ? map1 : map2) + (size_t)nd.img * Hl * Wl * 256 + c8 * 8;
     float acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 #pragma unroll
     for (int k = 0; k < 4; ++k) {

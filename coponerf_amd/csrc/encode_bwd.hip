@@ -15,56 +15,12 @@
 #include <algorithm>
 #include <cstdlib>
 
-#include "common.h"
-#include "taps.h"
+#include "encode_geometry.h"
 
 namespace {
 
-constexpr int PAD = CPN_NODE_PAD;
 constexpr int TLD = CPN_TAB_LD;                    // 832
-
-struct NodeGridB {                                  // same geometry as encode.hip's NodeGrid
-    int Mx, My;
-    __host__ __device__ int w(int kind) const { return Mx + 1 + (kind ? 2 * PAD : 0); }
-    __host__ __device__ int h(int kind) const { return My + 1 + (kind ? 2 * PAD : 0); }
-    __host__ __device__ long long border_nodes() const { return (long long)(Mx + 1) * (My + 1); }
-    __host__ __device__ long long zeros_nodes() const { return (long long)(Mx + 1 + 2 * PAD) * (My + 1 + 2 * PAD); }
-    __host__ __device__ long long per_image() const { return border_nodes() + zeros_nodes(); }
-};
-
-// table coordinates (>= 0) of the node cell of sample coordinate g: EXACTLY node_taps() of encode.hip
-__device__ __forceinline__ void node_cell(float2 g, int kind, const NodeGridB ng, int& xi, int& yi, float& fx, float& fy) {
-    const int pad = kind ? PAD : 0;
-    float tx = (g.x + 1.0f) * (0.5f * (float)ng.Mx), ty = (g.y + 1.0f) * (0.5f * (float)ng.My);
-    tx = fminf(fmaxf(tx, (float)-pad), (float)(ng.Mx + pad));
-    ty = fminf(fmaxf(ty, (float)-pad), (float)(ng.My + pad));
-    const int x0 = min((int)floorf(tx), ng.Mx + pad - 1), y0 = min((int)floorf(ty), ng.My + pad - 1);
-    fx = tx - (float)x0;
-    fy = ty - (float)y0;
-    xi = x0 + pad;
-    yi = y0 + pad;
-}
-
-// rows that read image `img` (same enumeration as backward.hip): idx in [0, per) own view (kind 0, pixel_val),
-// [per, 2 per) other view (kind 1, sec_grid)
-struct RowRefT {
-    unsigned row;
-    float2 g;
-    int j;
-};
-__device__ __forceinline__ RowRefT row_of_t(int idx, int per, int S, int rlo, int b, int vi, int V, int R, int ray0,
-                                            const float* __restrict__ pixel_val, const float* __restrict__ sec_grid) {
-    RowRefT o;
-    o.j = idx >= per;
-    const int rem = idx - o.j * per;
-    const int rr = rem / S, sm = rem - rr * S;
-    const int r = rlo + rr;
-    const int v = o.j ? (V - 1 - vi) : vi;
-    const size_t sidx = (((size_t)(b * V + v)) * R + r) * S + sm;
-    o.g = *reinterpret_cast<const float2*>((o.j ? sec_grid : pixel_val) + sidx * 2);
-    o.row = ((((unsigned)(b * R + r - ray0)) * V + v) * S + sm) * 2 + o.j;
-    return o;
-}
+// row_of(idx, per, S, false, 0, ...) below: these kernels take rem / S as a division, without the power-of-two shortcut
 
 // per 64-row chunk: the node-cell bounding box of its kind-0 rows and of its kind-1 rows (a chunk holds both kinds only
 // where it straddles idx = per)
@@ -79,14 +35,12 @@ __global__ __launch_bounds__(256) void table_bbox_kernel(int H, int W, const flo
     const int rlo = max(ray0, b * R) - b * R, rhi = min(ray0 + nrays, (b + 1) * R) - b * R;
     const int per = max(rhi - rlo, 0) * S, total = 2 * per;
     const int idx = c * 64 + lane;
-    const NodeGridB ng{W >> 1, H >> 1};
+    const NodeGrid ng{W >> 1, H >> 1};
     int box[2][4] = {{1 << 30, 1 << 30, -(1 << 30), -(1 << 30)}, {1 << 30, 1 << 30, -(1 << 30), -(1 << 30)}};
     if (idx < total) {
-        const RowRefT rf = row_of_t(idx, per, S, rlo, b, vi, V, R, ray0, pixel_val, sec_grid);
-        int xi, yi;
-        float fx, fy;
-        node_cell(rf.g, rf.j, ng, xi, yi, fx, fy);
-        box[rf.j][0] = xi; box[rf.j][1] = yi; box[rf.j][2] = xi + 1; box[rf.j][3] = yi + 1;
+        const RowRef rf = row_of(idx, per, S, false, 0, rlo, b, vi, V, R, ray0, pixel_val, sec_grid);
+        const NodeCell nc = node_cell(rf.g.x, rf.g.y, rf.j, ng);
+        box[rf.j][0] = nc.xi; box[rf.j][1] = nc.yi; box[rf.j][2] = nc.xi + 1; box[rf.j][3] = nc.yi + 1;
     }
 #pragma unroll
     for (int k = 0; k < 2; ++k) {
@@ -134,7 +88,7 @@ __global__ __launch_bounds__(64 * SW) void scatter_tables_kernel(
     const int g = role % G;
     const int img = role / G;
     const int tx0 = (tidx % plan.tiles_x) * TP, ty0 = (tidx / plan.tiles_x) * TPY;
-    const NodeGridB ng{W >> 1, H >> 1};
+    const NodeGrid ng{W >> 1, H >> 1};
     const int nw = ng.w(kind), nh = ng.h(kind);
     const __half* dcol = d + wave * TC + lane;
 
@@ -215,11 +169,11 @@ __global__ __launch_bounds__(64 * SW) void scatter_tables_kernel(
                 const int c = cand[slot * 64 + (ci - prefix[slot])];
                 const int idx = c * 64 + lane;
                 if (idx < total) {
-                    const RowRefT rf = row_of_t(idx, per, S, rlo, b, vi, V, R, ray0, pixel_val, sec_grid);
+                    const RowRef rf = row_of(idx, per, S, false, 0, rlo, b, vi, V, R, ray0, pixel_val, sec_grid);
                     if (rf.j == kind) {
-                        int xi, yi;
-                        float fx, fy;
-                        node_cell(rf.g, kind, ng, xi, yi, fx, fy);
+                        const NodeCell nc = node_cell(rf.g.x, rf.g.y, kind, ng);
+                        const int xi = nc.xi, yi = nc.yi;
+                        const float fx = nc.fx, fy = nc.fy;
                         const int hx = xi - tx0, hy = yi - ty0;
                         if (hx >= -1 && hx < TP && hy >= -1 && hy < TPY) {
 #pragma unroll
@@ -265,14 +219,14 @@ __global__ __launch_bounds__(64 * SW) void scatter_tables_kernel(
     }
     if (qn_s) drain(qn_s);
 
-    float* m = dtab + ((size_t)img * ng.per_image() + (kind ? ng.border_nodes() : 0)) * TLD + wave * TC + lane;
+    float* m = dtab + ng.table_base(img, kind) * TLD + wave * TC + lane;
 #pragma unroll 4
     for (int pix = 0; pix < TP * TPY; ++pix) {
         const float v = tile[pix * TC + lane];
         const int gy = ty0 + (pix >> 3), gx = tx0 + (pix & 7);
         if (v != 0.0f && gy < nh && gx < nw) {
-            if (G > 1) atomicAdd(m + ((size_t)gy * nw + gx) * TLD, v);
-            else m[((size_t)gy * nw + gx) * TLD] = v;           // the tile's only writer: dtab is zero on entry
+            if (G > 1) atomicAdd(m + ng.cell<size_t>(kind, gx, gy) * TLD, v);
+            else m[ng.cell<size_t>(kind, gx, gy) * TLD] = v;    // the tile's only writer: dtab is zero on entry
         }
     }
 }
@@ -294,10 +248,10 @@ struct BucketGeo {
 // the tiles a row's 2x2 node footprint touches: calls f(tile, cells, weights) with, for the four taps, the LDS cell of the
 // tile (byte k of `cells`; taps outside the tile or of zero weight point at the dummy cell TP*TPY with weight 0)
 template <class F>
-__device__ __forceinline__ void for_each_touched_tile(const RowRefT& rf, int kind, const NodeGridB ng, const BucketGeo& geo, F f) {
-    int xi, yi;
-    float fx, fy;
-    node_cell(rf.g, kind, ng, xi, yi, fx, fy);
+__device__ __forceinline__ void for_each_touched_tile(const RowRef& rf, int kind, const NodeGrid ng, const BucketGeo& geo, F f) {
+    const NodeCell nc = node_cell(rf.g.x, rf.g.y, kind, ng);
+    const int xi = nc.xi, yi = nc.yi;
+    const float fx = nc.fx, fy = nc.fy;
     const int txa = xi / TP, txb = (xi + 1) / TP, tya = yi / TPY, tyb = (yi + 1) / TPY;
 #pragma unroll
     for (int ty = 0; ty < 2; ++ty)
@@ -334,8 +288,8 @@ __global__ __launch_bounds__(256) void bucket_rows_kernel(BucketGeo geo, const f
     const int rlo = max(geo.ray0, b * geo.R) - b * geo.R, rhi = min(geo.ray0 + geo.nrays, (b + 1) * geo.R) - b * geo.R;
     const int per = max(rhi - rlo, 0) * geo.S, total = 2 * per;
     if (idx >= total || idx >= maxrows) return;
-    const RowRefT rf = row_of_t(idx, per, geo.S, rlo, b, vi, geo.V, geo.R, geo.ray0, pixel_val, sec_grid);
-    const NodeGridB ng{geo.W >> 1, geo.H >> 1};
+    const RowRef rf = row_of(idx, per, geo.S, false, 0, rlo, b, vi, geo.V, geo.R, geo.ray0, pixel_val, sec_grid);
+    const NodeGrid ng{geo.W >> 1, geo.H >> 1};
     const int group = img * 2 + rf.j;
     for_each_touched_tile(rf, rf.j, ng, geo, [&](int tile, int sub, unsigned cells, const f32x4& w4) {
         const int slot = (group * geo.T + tile) * NSUB + sub;
@@ -461,7 +415,7 @@ __global__ __launch_bounds__(64 * BSW, 1) void bucket_accumulate_kernel(const __
     const int4 item = work[blockIdx.x];
     const int group = item.x / geo.T, tidx = item.x - group * geo.T;
     const int img = group >> 1, kind = group & 1;
-    const NodeGridB ng{geo.W >> 1, geo.H >> 1};
+    const NodeGrid ng{geo.W >> 1, geo.H >> 1};
     const int nw = ng.w(kind), nh = ng.h(kind);
     const int tx0 = (tidx % geo.tiles_x[kind]) * TP, ty0 = (tidx / geo.tiles_x[kind]) * TPY;
     const int ch0 = wave * BTC + lane * CPL;
@@ -546,7 +500,7 @@ __global__ __launch_bounds__(64 * BSW, 1) void bucket_accumulate_kernel(const __
         dnxt = dfar;
     }
     if (held != 0xffffffffu) spill();
-    float* m = dtab + ((size_t)img * ng.per_image() + (kind ? ng.border_nodes() : 0)) * TLD + (ch_ok ? ch0 : 0);
+    float* m = dtab + ng.table_base(img, kind) * TLD + (ch_ok ? ch0 : 0);
 #pragma unroll 4
     for (int pix = 0; pix < TP * TPY; ++pix) {
         const fv v = tile[pix * 64];
@@ -555,7 +509,7 @@ __global__ __launch_bounds__(64 * BSW, 1) void bucket_accumulate_kernel(const __
 #pragma unroll
         for (int c = 0; c < CPL; ++c) any = any || v[c] != 0.0f;
         if (ch_ok && gy < nh && gx < nw && any) {
-            float* o = m + ((size_t)gy * nw + gx) * TLD;
+            float* o = m + ng.cell<size_t>(kind, gx, gy) * TLD;
             if (item.w) {                                          // the tile was split over several work items
 #pragma unroll
                 for (int c = 0; c < CPL; ++c)
@@ -586,11 +540,11 @@ __global__ __launch_bounds__(256) void node_features_bwd_kernel(const float* __r
     const int tx = (int)(rem % Wl); rem /= Wl;
     const int ty = (int)(rem % Hl);
     const int img = (int)(rem / Hl);
-    const NodeGridB ng{W >> 1, H >> 1};
+    const NodeGrid ng{W >> 1, H >> 1};
     const int texel = ty * Wl + tx;
     f32x4 acc = {0.f, 0.f, 0.f, 0.f};
     for (int kind = 0; kind < 2; ++kind) {
-        const int pad = kind ? PAD : 0, nw = ng.w(kind);
+        const int pad = NodeGrid::pad(kind);
         int x_lo = max(p * tx - p, -pad), x_hi = min(p * tx + 2 * p, ng.Mx + pad);
         int y_lo = max(p * ty - p, -pad), y_hi = min(p * ty + 2 * p, ng.My + pad);
         if (!kind) {                                           // border padding: clamped coordinates pile up on the edge texels
@@ -599,7 +553,7 @@ __global__ __launch_bounds__(256) void node_features_bwd_kernel(const float* __r
             if (ty == 0) y_lo = 0;
             if (ty == Hl - 1) y_hi = ng.My;
         }
-        const float* base = dfeat + ((size_t)img * ng.per_image() + (kind ? ng.border_nodes() : 0)) * 768 + lvl * 256 + lane * 4;
+        const float* base = dfeat + ng.table_base(img, kind) * 768 + lvl * 256 + lane * 4;
         // 64 candidate nodes are evaluated at once, one per lane (round 6: evaluated one after the other by the whole wave -
         // up to 1 250 make_taps per texel of the coarsest level - the kernel was bound by that redundant arithmetic: 0.64 ms);
         // the ones that touch the texel are then visited in the same (ny, nx) order as before, so the sums are unchanged
@@ -610,11 +564,10 @@ __global__ __launch_bounds__(256) void node_features_bwd_kernel(const float* __r
             int noff = 0;
             if (cand < ncand) {
                 const int ny = y_lo + cand / wc, nx = x_lo + cand % wc;
-                const float gx = (float)(2 * nx - ng.Mx) / (float)ng.Mx, gy = (float)(2 * ny - ng.My) / (float)ng.My;
-                const Taps tp = make_taps(gx, gy, Wl, Hl, kind == 0);
+                const Taps tp = make_taps(ng.gx(nx), ng.gy(ny), Wl, Hl, kind == 0);
 #pragma unroll
                 for (int k = 0; k < 4; ++k) wsum += (tp.off[k] == texel) ? tp.w[k] : 0.0f;
-                noff = (ny + pad) * nw + (nx + pad);
+                noff = ng.node(kind, nx, ny);
             }
             unsigned long long hit = __ballot(wsum != 0.0f);
             while (hit) {
@@ -695,15 +648,14 @@ __global__ __launch_bounds__(256) void absmax_kernel(const float* __restrict__ x
         const f32x4 v = reinterpret_cast<const f32x4*>(x)[i];
         m = fmaxf(m, fmaxf(fmaxf(fabsf(v[0]), fabsf(v[1])), fmaxf(fabsf(v[2]), fabsf(v[3]))));
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
+    m = wave_max(m);
     // ONE atomic per workgroup: with one per wave of an 8 192-block grid the 32 768 atomics on the same word were the
     // kernel (164 us on a 33 MB tensor that streams in 10)
-    __shared__ float wave_max[4];
-    if ((threadIdx.x & 63) == 0) wave_max[threadIdx.x >> 6] = m;
+    __shared__ float wmax[4];
+    if ((threadIdx.x & 63) == 0) wmax[threadIdx.x >> 6] = m;
     __syncthreads();
     if (threadIdx.x == 0) {
-        m = fmaxf(fmaxf(wave_max[0], wave_max[1]), fmaxf(wave_max[2], wave_max[3]));
+        m = fmaxf(fmaxf(wmax[0], wmax[1]), fmaxf(wmax[2], wmax[3]));
         if (m == m) atomicMax(amax_bits, __float_as_uint(m));                            // non-negative floats order like their bits
     }
 }
@@ -762,7 +714,7 @@ extern "C" int cpn_scale_to_f16(const float* x, long long n, float target, uint3
 }
 
 static void bucket_geo(BucketGeo& g, int H, int W, int B, int V, int R, int S, int ray0, int nrays) {
-    const NodeGridB ng{W >> 1, H >> 1};
+    const NodeGrid ng{W >> 1, H >> 1};
     g.V = V; g.R = R; g.S = S; g.ray0 = ray0; g.nrays = nrays; g.nimg = B * V; g.H = H; g.W = W;
     for (int k = 0; k < 2; ++k) {
         g.tiles_x[k] = (ng.w(k) + TP - 1) / TP;
@@ -841,7 +793,7 @@ extern "C" int cpn_scatter_rows_tables(const uint16_t* d, int ldx, int H, int W,
     const long long nwaves = (long long)nimg * maxchunks;
     hipLaunchKernelGGL(table_bbox_kernel, dim3((unsigned)((nwaves + 3) / 4)), dim3(256), 0, st, H, W, pixel_val, sec_grid, V,
                        R, S, ray0, nrays, maxchunks, nimg, (int4*)chunk_boxes);
-    const NodeGridB ng{W >> 1, H >> 1};
+    const NodeGrid ng{W >> 1, H >> 1};
     const long long cand = (long long)((nrays + B - 1) / B) * S;            // rows of one kind that read one image
     for (int kind = 0; kind < 2; ++kind) {
         ScatterPlan plan;

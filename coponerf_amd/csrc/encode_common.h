@@ -1,10 +1,10 @@
-// Pieces shared by the two forms of the first encoder layer on the node tables: cpn_encode_hidden (encode.hip) and
-// cpn_encode_key (encode_key.hip, the same layer with the folded key_map contraction fused behind it) - geometry of the
-// node tables, tap records, the (ray, sample) <-> tile-row map, the channel order of an MFMA tile, the hid store.
-// Design notes: encode.hip.
+// Pieces shared by the forms of the first encoder layer's forward on the node tables: cpn_encode_hidden (encode.hip),
+// cpn_encode_key (encode_fused.hip, the same layer with the folded key_map contraction fused behind it) and the fp32 mode
+// (encode_f32.hip) -
+// tap records, the (ray, sample) <-> tile-row map, the channel order of an MFMA tile, the hid store.  The geometry of the
+// node tables is in encode_geometry.h.  Design notes: encode.hip.
 #pragma once
-#include "common.h"
-#include "taps.h"
+#include "encode_geometry.h"
 
 namespace {
 
@@ -12,7 +12,6 @@ constexpr int NSLICE = 13;                // 832 = 13 x 64 output channels
 constexpr int SLICE_CH = 64;
 constexpr int NT = 4;                     // 16-channel MFMA tiles per slice
 // K = 80 = 2 x 32 full-resolution channels (v_mfma_f32_16x16x32_f16) + a 16-wide tail (3 point encodings + zeros, 16x16x16)
-constexpr int PAD = CPN_NODE_PAD;         // zero rim of the 'zeros' table, in nodes (= level-0 texel pitch / 2)
 constexpr int TAB_SLICE_BYTES = SLICE_CH * 2;                  // 128: one cache line per node and slice
 constexpr int TAB_ROW_BYTES = CPN_TAB_LD * 2;                  // 1664 per node, channels in natural order
 typedef __attribute__((address_space(3))) void lds_void;
@@ -62,38 +61,22 @@ __device__ __forceinline__ void store16(__half* p, half8 v) {
 #endif
 }
 
-// node-grid geometry of one image: border table first, zeros table behind it
-struct NodeGrid {
-    int Mx, My;                           // W/2, H/2
-    __host__ __device__ int bw() const { return Mx + 1; }
-    __host__ __device__ int bh() const { return My + 1; }
-    __host__ __device__ int zw() const { return Mx + 1 + 2 * PAD; }
-    __host__ __device__ int zh() const { return My + 1 + 2 * PAD; }
-    __host__ __device__ long long border_nodes() const { return (long long)bw() * bh(); }
-    __host__ __device__ long long zeros_nodes() const { return (long long)zw() * zh(); }
-    __host__ __device__ long long nodes_per_image() const { return border_nodes() + zeros_nodes(); }
-};
-
-// the 4 nodes around normalised coordinate g (grid_sample convention, [-1,1] = image) and their bilinear weights
+// the 4 nodes around normalised coordinate g (node_cell) as byte offsets inside the (image, mode) table, and their
+// bilinear weights
 __device__ __forceinline__ TapRec node_taps(float gx, float gy, const NodeGrid ng, bool border) {
-    const int pad = border ? 0 : PAD;
-    const int nw = border ? ng.bw() : ng.zw();
-    float tx = (gx + 1.0f) * (0.5f * (float)ng.Mx), ty = (gy + 1.0f) * (0.5f * (float)ng.My);
-    // beyond the rim the function is constant (border: clamped; zeros: 0), and |g| can reach 1e10 (geometry.py:390-391)
-    tx = fminf(fmaxf(tx, (float)-pad), (float)(ng.Mx + pad));
-    ty = fminf(fmaxf(ty, (float)-pad), (float)(ng.My + pad));
-    const int x0 = min((int)floorf(tx), ng.Mx + pad - 1), y0 = min((int)floorf(ty), ng.My + pad - 1);
-    const float fx = tx - (float)x0, fy = ty - (float)y0;
-    const int base = (y0 + pad) * nw + (x0 + pad);
+    const int kind = !border;
+    const NodeCell c = node_cell(gx, gy, kind, ng);
+    const int nw = ng.w(kind);
+    const int base = ng.cell(kind, c.xi, c.yi);
     TapRec t;
     t.off[0] = base * TAB_ROW_BYTES;
     t.off[1] = (base + 1) * TAB_ROW_BYTES;
     t.off[2] = (base + nw) * TAB_ROW_BYTES;
     t.off[3] = (base + nw + 1) * TAB_ROW_BYTES;
-    t.w[0] = (1.0f - fx) * (1.0f - fy);
-    t.w[1] = fx * (1.0f - fy);
-    t.w[2] = (1.0f - fx) * fy;
-    t.w[3] = fx * fy;
+    t.w[0] = (1.0f - c.fx) * (1.0f - c.fy);
+    t.w[1] = c.fx * (1.0f - c.fy);
+    t.w[2] = (1.0f - c.fx) * c.fy;
+    t.w[3] = c.fx * c.fy;
     return t;
 }
 

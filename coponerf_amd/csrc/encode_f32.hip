@@ -54,18 +54,11 @@ __global__ void node_features_f32_kernel(const float* __restrict__ map0, const f
     const long long node = idx / 192;
     const int lvl = chunk >> 6, c4 = chunk & 63;
     const NodeGrid ng{W >> 1, H >> 1};
-    const long long npi = ng.nodes_per_image();
-    const int img = (int)(node / npi);
-    long long rem = node - (long long)img * npi;
-    const bool border = rem < ng.border_nodes();
-    if (!border) rem -= ng.border_nodes();
-    const int nw = border ? ng.bw() : ng.zw(), pad = border ? 0 : PAD;
-    const int ny = (int)(rem / nw) - pad, nx = (int)(rem % nw) - pad;
-    const float gx = (float)(2 * nx - ng.Mx) / (float)ng.Mx, gy = (float)(2 * ny - ng.My) / (float)ng.My;
+    const NodeId nd = node_of(node, ng);
     const int shift = 4 - lvl;
     const int Hl = H >> shift, Wl = W >> shift;
-    const Taps tp = make_taps(gx, gy, Wl, Hl, border);
-    const float* m = (lvl == 0 ? map0 : lvl == 1 ? map1 : map2) + (size_t)img * Hl * Wl * 256 + c4 * 4;
+    const Taps tp = make_taps(nd.gx, nd.gy, Wl, Hl, nd.border);
+    const float* m = (lvl == 0 ? map0 : lvl == 1 ? map1 : map2) + (size_t)nd.img * Hl * Wl * 256 + c4 * 4;
     f32x4 acc = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
@@ -297,16 +290,6 @@ __global__ __launch_bounds__(64 * EWAVES, 1) void encode_hidden_f32_kernel(
 
 constexpr int HCF = 1664;
 
-__device__ __forceinline__ float wave_max_f(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
-    return v;
-}
-__device__ __forceinline__ float wave_sum_f2(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
 
 // one workgroup per ray: logits from (rows,128) fp32 operands, softmax over the V*S rows, hbar = sum_rows w (hi + lo);
 // LIST: the workgroup's ray is rays[ray0 + blockIdx.x] (its at_wt rows are skipped if that lies outside [0, nraytot))
@@ -337,7 +320,7 @@ __global__ __launch_bounds__(256) void attend_hidden_f32_kernel(const float* __r
             lmax = fmaxf(lmax, logit);
         }
     }
-    lmax = wave_max_f(lmax);
+    lmax = wave_max(lmax);
     if (lane == 0) red[wave] = lmax;
     __syncthreads();
     const float gmax = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
@@ -347,7 +330,7 @@ __global__ __launch_bounds__(256) void attend_hidden_f32_kernel(const float* __r
         wts[row] = e;
         lsum += e;
     }
-    lsum = wave_sum_f2(lsum);
+    lsum = wave_sum(lsum);
     if (lane == 0) red[4 + wave] = lsum;
     __syncthreads();
     const float inv = 1.0f / ((red[4] + red[5]) + (red[6] + red[7]));

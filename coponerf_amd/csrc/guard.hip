@@ -18,16 +18,6 @@
 
 namespace {
 
-__device__ __forceinline__ float g_wave_max(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
-    return v;
-}
-__device__ __forceinline__ float g_wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
 
 // one workgroup of 256 threads per ray of the chunk; wts: V*S floats of LDS
 __global__ __launch_bounds__(256) void logit_guard_kernel(const float* __restrict__ logits, int V, int S, int ray0,
@@ -46,13 +36,13 @@ __global__ __launch_bounds__(256) void logit_guard_kernel(const float* __restric
         wts[row] = logit;
         lmax = fmaxf(lmax, logit);
     }
-    lmax = g_wave_max(lmax);
+    lmax = wave_max(lmax);
     if (lane == 0) red[wave] = lmax;
     __syncthreads();
     const float gmax = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
     float lsum = 0.f;
     for (int row = tid; row < T; row += 256) lsum += __expf(wts[row] - gmax);
-    lsum = g_wave_sum(lsum);
+    lsum = wave_sum(lsum);
     if (lane == 0) red[4 + wave] = lsum;
     __syncthreads();
     const float inv = 1.0f / ((red[4] + red[5]) + (red[6] + red[7]));
@@ -62,7 +52,7 @@ __global__ __launch_bounds__(256) void logit_guard_kernel(const float* __restric
         const float w = __expf(l - gmax) * inv;
         acc += (w * (1.0f - w)) * fabsf(l);
     }
-    acc = g_wave_sum(acc);
+    acc = wave_sum(acc);
     if (lane == 0) red[8 + wave] = acc;
     __syncthreads();
     if (tid == 0) {

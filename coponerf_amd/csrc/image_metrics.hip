@@ -48,11 +48,6 @@ __device__ __forceinline__ int reflect(int i, int n) {
 // torch.clamp: a NaN stays a NaN (both comparisons are false)
 __device__ __forceinline__ float clamp_unit(float v) { return v < -1.0f ? -1.0f : (v > 1.0f ? 1.0f : v); }
 
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
 
 __global__ __launch_bounds__(NT) void image_metrics_kernel(const float* __restrict__ pred, const float* __restrict__ target,
                                                            int H, int W, Window win, float* __restrict__ partial) {

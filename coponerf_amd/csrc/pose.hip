@@ -52,8 +52,7 @@ __device__ __forceinline__ void dense_relu_in(const float* x, const float* __res
             float s = 0.0f;
 #pragma unroll
             for (int i = 0; i < PER; ++i) s += xv[i] * wv[q][i];
-#pragma unroll
-            for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
+            s = wave_sum(s);
             if (lane == 0 && o0 + q < n_out) y[o0 + q] = s + b[o0 + q];
         }
     }
@@ -86,8 +85,7 @@ __global__ __launch_bounds__(256) void pose_gemv_kernel(const float* __restrict_
 #pragma unroll
     for (int b = 0; b < NB; ++b) {
         float v = acc[b];
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+        v = wave_sum(v);
         if (lane == 0) red[b][wave] = v;
     }
     __syncthreads();

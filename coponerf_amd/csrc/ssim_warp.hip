@@ -34,7 +34,7 @@ constexpr int RW = TW + 2 * RAD, RH = TH + 2 * RAD;
 constexpr int NT = 256;
 constexpr float SSIM_C1 = 0.01f * 0.01f, SSIM_C2 = 0.03f * 0.03f;
 
-struct Taps {
+struct WarpTaps {
     int x0, y0, x1, y1;             // clamped tap indices (valid only where the flag is set)
     bool vx0, vx1, vy0, vy1;
     float wx0, wx1, wy0, wy1;       // ATen's (ix_se - ix), (ix - ix_nw), (iy_se - iy), (iy - iy_nw)
@@ -70,8 +70,8 @@ __device__ __forceinline__ void sample_coord(const float* __restrict__ fl, int h
 }
 
 // tap indices are formed only from floats known to lie inside the image: a coordinate of 1e9, inf or NaN selects no tap
-__device__ __forceinline__ Taps make_taps(float ix, float iy, int H, int W) {
-    Taps t;
+__device__ __forceinline__ WarpTaps warp_taps(float ix, float iy, int H, int W) {
+    WarpTaps t;
     const float fx0 = floorf(ix), fy0 = floorf(iy);
     const float fx1 = fx0 + 1.0f, fy1 = fy0 + 1.0f;
     t.vx0 = fx0 >= 0.f && fx0 <= (float)(W - 1);
@@ -89,11 +89,6 @@ __device__ __forceinline__ Taps make_taps(float ix, float iy, int H, int W) {
     return t;
 }
 
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
 
 __global__ __launch_bounds__(NT) void ssim_warp_fwd_kernel(const float* __restrict__ rgb, const float* __restrict__ flow0,
                                                            const float* __restrict__ flow1, const uint8_t* __restrict__ mask,
@@ -122,7 +117,7 @@ __global__ __launch_bounds__(NT) void ssim_warp_fwd_kernel(const float* __restri
         if (gy >= 0 && gy < H && gx >= 0 && gx < W) {
             float ix, iy;
             sample_coord(fl, h, w, H, W, fs, rs, gx, gy, ix, iy);
-            const Taps t = make_taps(ix, iy, H, W);
+            const WarpTaps t = warp_taps(ix, iy, H, W);
             const float w00 = t.wx0 * t.wy0, w01 = t.wx1 * t.wy0, w10 = t.wx0 * t.wy1, w11 = t.wx1 * t.wy1;
             const float* const p00 = src + ((size_t)t.y0 * W + t.x0) * 3;
             const float* const p01 = src + ((size_t)t.y0 * W + t.x1) * 3;
@@ -273,7 +268,7 @@ __global__ __launch_bounds__(NT) void ssim_warp_bwd_kernel(const float* __restri
     if (tid < WIN) swin[tid] = window[tid];
     constexpr int PER = TH * TW / NT;
     float gix[PER], giy[PER];
-    Taps tp[PER];
+    WarpTaps tp[PER];
     bool in[PER];
 #pragma unroll
     for (int j = 0; j < PER; ++j) {
@@ -286,7 +281,7 @@ __global__ __launch_bounds__(NT) void ssim_warp_bwd_kernel(const float* __restri
             ix = coords[((size_t)item * 2 + 0) * HW + (size_t)gy * W + gx];
             iy = coords[((size_t)item * 2 + 1) * HW + (size_t)gy * W + gx];
         }
-        tp[j] = make_taps(ix, iy, H, W);
+        tp[j] = warp_taps(ix, iy, H, W);
     }
     for (int c = 0; c < 3; ++c) {
         for (int idx = tid; idx < RH * RW; idx += NT) {
@@ -328,7 +323,7 @@ __global__ __launch_bounds__(NT) void ssim_warp_bwd_kernel(const float* __restri
                 gb = __builtin_fmaf(g, sh[1][o], gb);
                 gc = __builtin_fmaf(g, sh[2][o], gc);
             }
-            const Taps& t = tp[j];
+            const WarpTaps& t = tp[j];
             const float v00 = (t.vy0 && t.vx0) ? src[((size_t)t.y0 * W + t.x0) * 3 + c] : 0.f;
             const float v01 = (t.vy0 && t.vx1) ? src[((size_t)t.y0 * W + t.x1) * 3 + c] : 0.f;
             const float v10 = (t.vy1 && t.vx0) ? src[((size_t)t.y1 * W + t.x0) * 3 + c] : 0.f;

@@ -1,7 +1,7 @@
 // Bilinear tap set of one feature level, exactly ATen's grid_sampler_2d with align_corners=False
 // (/root/reference models/CoPoNeRF.py:312 'border', :370 'zeros').  Shared by the forward gathers (gather.hip,
-// encode.hip) and the scatter of the training backward (backward.hip) so that all three agree bit for bit on the
-// texel indices.
+// encode.hip) and the scatter of the training backward (backward.hip, through level_xy) so that all three agree bit for
+// bit on the texel indices.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -10,7 +10,8 @@ struct Taps {
     float w[4];      // weights; 0 for out-of-map taps (zeros padding)
 };
 
-__device__ __forceinline__ Taps make_taps(float gx, float gy, int Wl, int Hl, bool border) {
+// pixel-space position of normalised coordinate g at a level of Wl x Hl texels, clamped the way the padding mode needs
+__device__ __forceinline__ float2 level_xy(float gx, float gy, int Wl, int Hl, bool border) {
     float x = ((gx + 1.0f) * (float)Wl - 1.0f) / 2.0f;
     float y = ((gy + 1.0f) * (float)Hl - 1.0f) / 2.0f;
     if (border) {
@@ -22,6 +23,12 @@ __device__ __forceinline__ Taps make_taps(float gx, float gy, int Wl, int Hl, bo
         x = fminf(fmaxf(x, -2.0f), (float)Wl + 1.0f);
         y = fminf(fmaxf(y, -2.0f), (float)Hl + 1.0f);
     }
+    return make_float2(x, y);
+}
+
+__device__ __forceinline__ Taps make_taps(float gx, float gy, int Wl, int Hl, bool border) {
+    const float2 p = level_xy(gx, gy, Wl, Hl, border);
+    const float x = p.x, y = p.y;
     const float xf = floorf(x), yf = floorf(y);
     const int x0 = (int)xf, y0 = (int)yf;
     const float fx = x - xf, fy = y - yf;

@@ -939,8 +939,7 @@ __global__ __launch_bounds__(256) void dwconv3x3_wgrad_kernel(const float* __res
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #pragma unroll
     for (int t = 0; t < 10; ++t) {
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) a[t] += __shfl_xor(a[t], off);
+        a[t] = wave_sum(a[t]);
         if (lane == 0) sh[wave][t] = a[t];
     }
     __syncthreads();
@@ -1095,8 +1094,7 @@ __global__ __launch_bounds__(256) void l2norm_rows_kernel(const float* __restric
     const float* xr = x + (size_t)row * C;
     float ss = 0.f;
     for (int c = lane; c < C; c += 64) ss += xr[c] * xr[c];
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) ss += __shfl_xor(ss, off);
+    ss = wave_sum(ss);
     const float d = sqrtf(ss) + eps;
     for (int c = lane; c < C; c += 64) y[(size_t)row * C + c] = xr[c] / d;
 }
@@ -1268,8 +1266,7 @@ __global__ __launch_bounds__(256) void soft_argmax_rows_kernel(const float* __re
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     float m = -INFINITY;
     for (int t = threadIdx.x; t < T; t += 256) m = fmaxf(m, row[t]);
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) m = fmaxf(m, __shfl_xor(m, off));
+    m = wave_max(m);
     if (lane == 0) red[wave] = m;
     __syncthreads();
     m = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
@@ -1806,15 +1803,13 @@ __global__ __launch_bounds__(256) void soft_argmax_rows_bwd_kernel(const float* 
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     float m = -INFINITY;
     for (int t = threadIdx.x; t < T; t += 256) m = fmaxf(m, row[t]);
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) m = fmaxf(m, __shfl_xor(m, off));
+    m = wave_max(m);
     if (lane == 0) red[wave] = m;
     __syncthreads();
     m = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
     float se = 0.f;
     for (int t = threadIdx.x; t < T; t += 256) se += expf((row[t] - m) / beta);
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) se += __shfl_xor(se, off);
+    se = wave_sum(se);
     if (lane == 0) red[4 + wave] = se;
     __syncthreads();
     const float inv = 1.0f / (((red[4] + red[5]) + (red[6] + red[7])) * beta);
@@ -1882,19 +1877,16 @@ __global__ __launch_bounds__(256) void row_stats_kernel(const float* __restrict_
     if (mode == 0) {
         float m = -INFINITY;
         for (int j = lane; j < M; j += 64) m = fmaxf(m, ar[j]);
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) m = fmaxf(m, __shfl_xor(m, off));
+        m = wave_max(m);
         float se = 0.f;
         for (int j = lane; j < M; j += 64) se += expf(ar[j] - m);
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) se += __shfl_xor(se, off);
+        se = wave_sum(se);
         if (lane == 0) { stat[row * 2] = m; stat[row * 2 + 1] = se; }
     } else {
         const float* wr = w + (size_t)row * M;
         float sacc = 0.f;
         for (int j = lane; j < M; j += 64) sacc += ar[j] * wr[j];
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) sacc += __shfl_xor(sacc, off);
+        sacc = wave_sum(sacc);
         if (lane == 0) stat[row] = sacc;
     }
 }

@@ -221,12 +221,10 @@ __global__ __launch_bounds__(256) void cross_rows_kernel(const float* __restrict
     float* p = prob + wave * T;
     float m = -INFINITY;
     for (int t = lane; t < T; t += 64) { const float x = row[t]; p[t] = x; m = fmaxf(m, x); }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
+    m = wave_max(m);
     float z = 0.0f;
     for (int t = lane; t < T; t += 64) { const float e = expf(p[t] - m); p[t] = e; z += e; }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) z += __shfl_xor(z, o);
+    z = wave_sum(z);
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     // lanes 0..C-1 own a channel; lanes C..2C-1 take the second half of the t range (C = 32: the whole wave works)
     const int ch = lane % C, part = lane / C, nparts = 64 / C;
@@ -328,12 +326,10 @@ __global__ __launch_bounds__(256) void cross_bwd_stats_kernel(const float* __res
         const float* row = cm + (size_t)s * T;
         float m = -INFINITY;
         for (int t = lane; t < T; t += 64) m = fmaxf(m, row[t]);
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
+        m = wave_max(m);
         float z = 0.0f;
         for (int t = lane; t < T; t += 64) z += expf(row[t] - m);
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) z += __shfl_xor(z, o);
+        z = wave_sum(z);
         float r = 0.0f;
         if (lane < XB_C) {
             const size_t o = (((size_t)b * S + s) * H + h) * XB_C + lane;
