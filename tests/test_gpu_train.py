@@ -435,6 +435,18 @@ def test_backward_entry_points_reject_bad_shapes():
         call("cpn_linear_attention_bwd", f.data_ptr(), f.data_ptr(), f.data_ptr(), f.data_ptr(), 1, 0, 1, 8, 0, 1e-6, 1,
              f.data_ptr(), f.data_ptr(), f.data_ptr(), f.data_ptr(), st)
     assert _hip.lib().cpn_wgrad_tall_scratch(100, 128) == 0
+    # the documented limits of the get_z backward's entries (held to float64 inside them by tests/test_gpu_ufc_f64.py)
+    fp = f.data_ptr()
+    with pytest.raises(RuntimeError, match="cpn_soft_argmax_pair_bwd: bad shape"):      # h = 1: linspace(-1, 1, 1) has no step
+        call("cpn_soft_argmax_pair_bwd", fp, 1, 1, 0.02, fp, fp, fp, fp, fp, st)
+    with pytest.raises(RuntimeError, match="cpn_l2norm_rows_bwd: need 0 < C <= 1024"):  # a row is held in 16 registers per lane
+        call("cpn_l2norm_rows_bwd", fp, fp, fp, 4, 1025, 1e-5, fp, st)
+    with pytest.raises(RuntimeError, match="S, T <= 512"):                              # the LDS request of the row kernel
+        call("cpn_cross_attention_bwd", fp, fp, fp, fp, fp, fp, fp, 1, 1, 513, 8, 32, fp, fp, fp, fp, st)
+    with pytest.raises(RuntimeError, match="cpn_conv4d_dgrad: need Cin"):               # channel groups of 4 or 8
+        call("cpn_conv4d_dgrad", fp, fp, fp, 1, 8, 6, 4, 4, 4, 4, fp, st)
+    torch.cuda.synchronize()
+    assert bool((f == 0).all()) and bool((a == 0).all()), "a rejected call wrote something"
 
 
 @pytest.mark.gpu
