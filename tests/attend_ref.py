@@ -107,7 +107,7 @@ def attend_fwd_ref(qa, qb, logits, hid, B, R, S, ray0, nrays):
         x = (l - l.max(1, keepdim=True).values).abs()
         assert float(x.max()) < 87.0, "an exponential underflows fp32: the weight bound does not cover this input"
         terms = {"logit": (2 * dl.max(1, keepdim=True).values).expand(nrays, T), "expf": (x + 4) * 2.0 ** -22,
-                 "sum": torch.full((nrays, T), (T + 4) * U32, dtype=torch.float64)}
+                 "sum": torch.full((nrays, T), (T + 4) * U32, dtype=torch.float64, device=l.device)}
         w_bound = w * sum(terms.values())
     return {"l": l, "w": w, "hbar": hbar, "idx": weight_index(B, R, S, ray0, nrays), "terms": terms, "w_bound": w_bound}
 
