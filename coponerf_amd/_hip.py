@@ -100,6 +100,10 @@ SIGNATURES: Dict[str, List] = {
     "cpn_ssim_warp_bwd": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P],
     "cpn_image_metrics_scratch": [_I, _I, _I],             # returns the count of partial floats, not a status
     "cpn_image_metrics": [_P, _P, _I, _I, _I, _P, _P, _P],
+    "cpn_flow_panels": [_P, _P, _P, _I, _I, _I, _P, _P, _P, _P],
+    "cpn_depth_jet": [_P, ctypes.c_longlong, _P, _P, _P],
+    "cpn_attention_entropy_blocks": [ctypes.c_longlong],   # returns the count of partial floats, not a status
+    "cpn_attention_entropy": [_P, ctypes.c_longlong, _I, _I, _P, _P, _P],
 }
 
 CAM_STRIDE = 96
@@ -107,7 +111,7 @@ CAM_TQ, CAM_M, CAM_AOWN, CAM_AOTH, CAM_KQ, CAM_KC, CAM_KO, CAM_KN = 0, 16, 32, 4
 TAB_LD = 832
 RAYC_STRIDE = 64
 LIGHTFIELD_PACK_FLOATS = 128 * 32 + 128 + 3 * (128 * 416 + 128 + 2 * (128 * 128 + 128)) + 16 * 128 + 16
-ABI_VERSION = 12               # (cpn_attend_units, round 7, cpn_ssim_warp*, round 8, and cpn_image_metrics*, round 9, are additive: symbols added, none altered)
+ABI_VERSION = 12               # (cpn_attend_units, round 7, cpn_ssim_warp*, round 8, cpn_image_metrics*, round 9, and summaries.hip, round 10, are additive: symbols added, none altered)
 ADAM_SEG_BYTES = 48
 
 

@@ -5,7 +5,7 @@
 
 geometry.hip is compiled with -ffp-contract=off: its arithmetic must reproduce the oracle's
 IEEE operation sequence bit for bit (sample coordinates / tap indices); ssim_warp.hip likewise, for the
-sampling coordinates of the flow warp (its window sums name their FMAs).
+sampling coordinates of the flow warp (its window sums name their FMAs), and summaries.hip, which shares them.
 """
 import os
 import subprocess
@@ -44,6 +44,7 @@ UNITS = [
     ("pose.hip", []),
     ("ssim_warp.hip", ["-ffp-contract=off"]),
     ("image_metrics.hip", []),
+    ("summaries.hip", ["-ffp-contract=off"]),
 ]
 
 

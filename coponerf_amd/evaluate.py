@@ -219,10 +219,12 @@ class Evaluator:
 
     @torch.no_grad()
     def run(self, model, loader: Iterable, nchunks: Optional[int] = None, image_shape: Optional[Sequence[int]] = None,
-            **render_images_kwargs) -> "Evaluator":
+            summary_log=None, **render_images_kwargs) -> "Evaluator":
         """test.py:161-296 over a validation loader that yields (model_input, gt, overlap) triples
         (data/realestate10k_dataio.py:683): every batch rendered through `pipeline.render_images` (nchunks=18 is test.py's own
-        chunking) and added.  Tensors still on the host are moved to the model's device first, as utils.dict_to_gpu does."""
+        chunking) and added.  Tensors still on the host are moved to the model's device first, as utils.dict_to_gpu does.
+        summary_log: a `summaries.SummaryLog`; every batch is also logged through it (test.py:270), under the index of its
+        `add` call as the step.  The caller flushes it."""
         from .pipeline import render_images
         dev = next(model.parameters()).device
         pending: deque = deque()
@@ -232,8 +234,10 @@ class Evaluator:
                 pending.append((_to_device(gt, dev), overlap))
                 yield _to_device(model_input, dev)
 
-        for _, out in render_images(model, inputs(), nchunks=nchunks, **render_images_kwargs):
+        for model_input, out in render_images(model, inputs(), nchunks=nchunks, **render_images_kwargs):
             gt, overlap = pending.popleft()
+            if summary_log is not None:
+                summary_log.add(model_input, out, self._calls, image_shape=image_shape)
             self.add(out, gt, overlap, image_shape=image_shape)
         return self
 

@@ -686,6 +686,27 @@ int cpn_ssim_warp_bwd(const float* rgb, const float* coords, const float* maps, 
 int cpn_image_metrics_scratch(int N, int H, int W);
 int cpn_image_metrics(const float* pred, const float* target, int N, int H, int W, float* partial, float* out, void* stream);
 
+/* ==== the training / validation log on the device: flow panels, depth colours, attention entropy (round 10) ==============
+ * cpn_flow_panels replaces summary/summaries.py:163-207 (and :42-63, :74-100 inside it) minus the OpenCV contour: both
+ *   F.interpolate(mode="bilinear") * (S / h), both cycle checks torch.norm(flow + warp(flow2, flow)).le(10), both
+ *   get_gt_correspondence_mask, the per-image loop of warp((rgb + 1) * 127.5, flow) -> .cpu().numpy() ->
+ *   overlay_semantic_mask(color=[255, 102, 51], alpha=0.5), for both directions and all B in ONE launch.
+ *   rgb (B, 2, S, S, 3) fp32 in [-1, 1] (channels last), flow0 / flow1 (B, 2, h, h) fp32, any square S >= h (the reference
+ *   hard-codes 256).  Direction d warps view 1 - d by flow_d.  warped (2, B, S, S, 3) fp32 in [0, 255]; mask (2, B, S, S)
+ *   bytes: norm <= 10 and the mapping inside [0, S - 1]; overlay (2, B, S, S, 3) bytes: trunc(warped), and where the mask is
+ *   false trunc(0.5 u8 + 0.5 colour).  The S x S flows are never stored.
+ * cpn_depth_jet replaces summaries.py:129-133: out (n, 3) fp32 = table[trunc(fl32(fl32(d / 10) * 256))] with matplotlib's
+ *   under / over / bad rules (below 0 -> entry 0, 256 or above -> entry 255, NaN -> 0 0 0); table (256, 3) fp32 on the device.
+ * cpn_attention_entropy replaces summaries.py:114-117 and wrapper.py:126-130: out (1) fp32 = mean over the rows of
+ *   -sum_s w log(w + 1e-5) of at_wt (rows, S) fp32, any S >= 1, read once; nan_to_zero counts a NaN row as 0 (wrapper.py:129).
+ *   partial: cpn_attention_entropy_blocks(rows) floats (0 for a row count it rejects); the finish runs in float64.
+ * No atomics in any of them: bit-reproducible, and an image's panels do not depend on the batch around it.                   */
+int cpn_flow_panels(const float* rgb, const float* flow0, const float* flow1, int B, int S, int h, float* warped, uint8_t* mask,
+                    uint8_t* overlay, void* stream);
+int cpn_depth_jet(const float* depth, long long n, const float* table, float* out, void* stream);
+int cpn_attention_entropy_blocks(long long rows);
+int cpn_attention_entropy(const float* at_wt, long long rows, int S, int nan_to_zero, float* partial, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
