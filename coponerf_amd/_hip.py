@@ -104,6 +104,9 @@ SIGNATURES: Dict[str, List] = {
     "cpn_depth_jet": [_P, ctypes.c_longlong, _P, _P, _P],
     "cpn_attention_entropy_blocks": [ctypes.c_longlong],   # returns the count of partial floats, not a status
     "cpn_attention_entropy": [_P, ctypes.c_longlong, _I, _I, _P, _P, _P],
+    "cpn_lpips_stem": [_P, _P, _P, _P, _I, _I, _I, _P, _P],
+    "cpn_lpips_head_scratch": [_I, _I, _P, _P],            # host arrays of ints; returns the count of partial floats, not a status
+    "cpn_lpips_head": [_P, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P],      # the first five are HOST arrays
 }
 
 CAM_STRIDE = 96
@@ -111,7 +114,7 @@ CAM_TQ, CAM_M, CAM_AOWN, CAM_AOTH, CAM_KQ, CAM_KC, CAM_KO, CAM_KN = 0, 16, 32, 4
 TAB_LD = 832
 RAYC_STRIDE = 64
 LIGHTFIELD_PACK_FLOATS = 128 * 32 + 128 + 3 * (128 * 416 + 128 + 2 * (128 * 128 + 128)) + 16 * 128 + 16
-ABI_VERSION = 12               # (cpn_attend_units, round 7, cpn_ssim_warp*, round 8, cpn_image_metrics*, round 9, and summaries.hip, round 10, are additive: symbols added, none altered)
+ABI_VERSION = 12               # (cpn_attend_units, round 7, cpn_ssim_warp*, round 8, cpn_image_metrics*, round 9, summaries.hip, round 10, and lpips.hip, round 11, are additive: symbols added, none altered)
 ADAM_SEG_BYTES = 48
 
 

@@ -45,6 +45,7 @@ UNITS = [
     ("ssim_warp.hip", ["-ffp-contract=off"]),
     ("image_metrics.hip", []),
     ("summaries.hip", ["-ffp-contract=off"]),
+    ("lpips.hip", []),                                     # its two exact statements switch contraction off by pragma
 ]
 
 

@@ -10,8 +10,9 @@ pair.  Here
                   returns the statistics of the reference's printed line for "all" / "small" / "medium" / "large"
 
 `Evaluator.add` reads no device value on the host and copies no pageable host memory, so it can follow
-`pipeline.render_images` without stalling it.  LPIPS is not shipped (its VGG weights are not part of this
-package): `Evaluator(extra={"lpips": fn})` takes any callable for it.
+`pipeline.render_images` without stalling it.  LPIPS (test.py:149, 258-263) is `coponerf_amd.lpips.LPIPS`, on
+the user's own weight files (none are part of this package): `Evaluator(extra={"lpips": LPIPS.from_files(...).to(dev)})` adds
+its column, and `extra` takes any other callable `fn(pred, target) -> (N,)` the same way.
 """
 from __future__ import annotations
 

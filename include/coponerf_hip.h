@@ -707,6 +707,32 @@ int cpn_depth_jet(const float* depth, long long n, const float* table, float* ou
 int cpn_attention_entropy_blocks(long long rows);
 int cpn_attention_entropy(const float* at_wt, long long rows, int S, int nan_to_zero, float* partial, float* out, void* stream);
 
+/* ==== LPIPS (VGG): the two ends of the metric around the library's convolutions (round 11) ================================
+ * test.py:149, 258-263 call lpips.LPIPS(net='vgg') per image and read it with .item(); the package is version='0.1',
+ * lpips=True, spatial=False, normalize=False.  The symbols are additive: the ABI version stays.
+ * cpn_lpips_stem replaces test.py:227-229, 258-259 (clamp of the prediction; both images through [0, 1] and back, each
+ *   operation rounded to fp32), the package's ScalingLayer ((x - shift) / scale, shift -.030 -.088 -.188, scale .458 .448 .450)
+ *   and conv1_1 + bias + ReLU of torchvision's vgg16().features in one launch.
+ *   pred, target (N, H, W, 3) fp32 in [-1, 1], channels last; only pred is clamped, a NaN stays a NaN.  w (64, 3, 3, 3),
+ *   bias (64).  out (2N, H, W, 64) fp32, channels last, predictions first.  Zero padding follows the scaling: a border tap reads
+ *   0.  Exact fp32 products, bias + 27 terms in (ci, ky, kx) order: bit-reproducible.  H, W >= 16 (four pools must leave a pixel;
+ *   CPN_E_SHAPE otherwise).
+ * cpn_lpips_head replaces the package's normalize_tensor, (a - b)^2, the bias-free 1 x 1 `lin` layers, spatial_average and the
+ *   sum over the layers, for all layers and images in 2 launches.  host_* are HOST arrays of `layers` <= CPN_LPIPS_LAYERS
+ *   entries, copied into the kernel's arguments: host_feat[k] (2N, h_k, w_k, C_k) fp32 channels last, predictions first;
+ *   host_lin[k] (C_k); C_k a multiple of 64 up to 512, any h_k, w_k >= 1 (CPN_E_SHAPE otherwise); all 16-byte aligned.
+ *   out (N) fp32 = sum_k mean_pixels sum_c lin_k[c] (a_c - b_c)^2 with a = f_pred / (sqrt(sum_c f_pred^2) + 1e-10), b likewise
+ *   from f_target; per_layer (N, CPN_LPIPS_LAYERS) fp32 or NULL: the terms of that sum (0 for a layer not given).
+ *   partial: cpn_lpips_head_scratch(N, layers, host_h, host_w) floats (0 for sizes cpn_lpips_head rejects).  Every feature
+ *   value is read once; the finish runs in float64.  No atomics: bit-reproducible, image n's values do not depend on N, and a
+ *   NaN stays in its image.                                                                                                  */
+#define CPN_LPIPS_LAYERS 5
+int cpn_lpips_stem(const float* pred, const float* target, const float* w, const float* bias, int N, int H, int W, float* out,
+                   void* stream);
+int cpn_lpips_head_scratch(int N, int layers, const int* host_h, const int* host_w);
+int cpn_lpips_head(const float* const* host_feat, const float* const* host_lin, const int* host_C, const int* host_h,
+                   const int* host_w, int layers, int N, float* partial, float* out, float* per_layer, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
