@@ -1,4 +1,9 @@
-"""ctypes binding of libcoponerf_hip.so (C ABI: include/coponerf_hip.h).
+"""ctypes binding of libcoponerf_hip.so, derived from its C ABI: include/coponerf_hip.h.
+
+The header is the only description of the interface.  It is parsed once at import (the built library is not needed for
+that): every `<ret> cpn_<name>(<args>);` becomes a PROTOTYPES entry and every integer `#define CPN_<NAME>` a constant of this
+module.  A new entry point is declared in the header and defined in a unit of csrc/ - nothing is added here.  A
+declaration the parser does not understand raises: it is never skipped.
 
 The library is the product's only compute path: if it is missing or a symbol
 is absent this module raises — there is no PyTorch/CPU fallback.
@@ -8,121 +13,89 @@ from __future__ import annotations
 import ctypes
 import os
 import re
-from typing import Dict, List
+from typing import Dict, List, Tuple
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # COPONERF_HIP_LIB: another build of the SAME library (kernel-variant experiments, tools/_build/); never a fallback
 LIB_PATH = os.environ.get("COPONERF_HIP_LIB") or os.path.join(_HERE, "libcoponerf_hip.so")
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "coponerf_hip.h")
 
-_P, _I, _F = ctypes.c_void_p, ctypes.c_int, ctypes.c_float
+_SCALARS = {"int": ctypes.c_int, "float": ctypes.c_float, "double": ctypes.c_double, "long long": ctypes.c_longlong}
 
-# name -> argtypes (every function returns int status except the two noted below)
-SIGNATURES: Dict[str, List] = {
-    "cpn_stream_create_cu_range": [_I, _I, ctypes.POINTER(ctypes.c_void_p)],
-    "cpn_stream_destroy": [_P],
-    "cpn_project_rays": [_P, _P, ctypes.c_longlong, _I, _I, _I, _P, _P, _P, _P],
-    "cpn_sample_geometry": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P],
-    "cpn_nchw_to_nhwc_f16": [_P, _P, _I, _I, _I, _I, _P],
-    "cpn_pack_weight_f16": [_P, _I, _I, _P, _I, _P],
-    "cpn_pack_encode_weights": [_P, _I, _P, _P, _P],
-    "cpn_node_features": [_P, _P, _P, _I, _I, _I, _P, _P],
-    "cpn_encode_key": [_P, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _I, _P],
-    "cpn_local_units": [_I, _P, _P, _P, _I, _P, _P, _P, _I, _P, _P, _I, _P, _P, _I, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P],
-    "cpn_attend_units": [_I, _P, _P, _P, _I, _P, _P, _P, _I, _P, _P, _I, _P, _P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P],
-    "cpn_local_hidden": [_P, _P, _P, _I, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P],
-    "cpn_gemm_f16": [_P, _I, _P, _I, _P, _P, _I, _I, _I, _I, _I, _I, _P],
-    "cpn_pack_gemm_frags": [_P, _I, _I, _I, _P, _P],
-    "cpn_gemm_f16_fewrows": [_P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _P],
-    "cpn_attend_hidden": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P],
-    "cpn_node_features_f32": [_P, _P, _P, _I, _I, _I, _P, _P],
-    "cpn_encode_hidden_f32": [_P, _P, _I, _I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P],
-    "cpn_attend_hidden_f32": [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P],
-    "cpn_logit_guard": [_P, _I, _I, _I, _I, _I, _I, _P, _I, _P],
-    "cpn_select_rays": [_P, _I, _F, _P, _P, _P],
-    "cpn_encode_hidden_f32_rays": [_P, _P, _I, _I, _P, _P, _P, _P, _I, _I, _I, _I, _P, _I, _I, _P, _P],
-    "cpn_attend_hidden_f32_rays": [_P, _P, _P, _I, _I, _I, _I, _P, _I, _I, _P, _P, _P],
-    "cpn_linear_f32": [_P, _I, _P, _I, _P, _P, _I, _P, _I, _I, _I, _I, _I, _I, _P],
-    "cpn_lightfield_decode": [_P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P],
-    "cpn_ray_outputs": [_P, _P, _P, ctypes.c_longlong, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P],
-    "cpn_attend_hidden_bwd": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P],
-    "cpn_attend_hidden_bwd_f32": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P],
-    "cpn_hid_grad_combine": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P],
-    "cpn_gemm_f16_combine": [_P, _I, _P, _I, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P],
-    "cpn_gemm_f16_combine_hs": [_P, _I, _P, _I, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P],
-    "cpn_gemm_f16_masked": [_P, _I, _P, _I, _P, _I, _P, _I, _I, _I, _I, _P],
-    "cpn_wgrad_skinny_f16": [_P, _P, _I, ctypes.c_longlong, _P, _P, _P],
-    "cpn_wgrad_tall_f16": [_P, _I, _P, _I, ctypes.c_longlong, _I, _I, _P, _P, _P, _P],
-    "cpn_local_hidden_bwd": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P],
-    "cpn_gather_rows_bwd_level3": [_P, _I, _I, _I, _I, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P],
-    "cpn_scatter_rows_tables": [_P, _I, _I, _I, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P],
-    "cpn_node_features_bwd": [_P, _I, _I, _I, _P, _P, _P, _P],
-    "cpn_scale_to_f16": [_P, ctypes.c_longlong, _F, _P, _P, _P, _P],
-    "cpn_gather_tail": [_P, _I, _I, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P],
-    "cpn_conv4d_gn_relu": [_P, _P, _P, _P, _P, _P, _P, _P, _F, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P],
-    "cpn_conv4d": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P],
-    "cpn_transpose_pairs": [_P, _I, _I, _I, _P, _P],
-    "cpn_conv4d_dgrad": [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P],
-    "cpn_gn_relu": [_P, _P, _P, _P, _P, _F, _I, _I, ctypes.c_longlong, _P, _P],
-    "cpn_gn_relu_bwd": [_P, _P, _P, _P, _P, _F, _I, _I, ctypes.c_longlong, _P, _P, _P, _P, _P],
-    "cpn_conv_wgrad_planes": [_P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P],
-    "cpn_dwconv3x3_wgrad": [_P, _P, _I, _I, _I, _I, _P, _P, _P],
-    "cpn_dwconv3x3_tokens": [_P, _P, _P, _I, _I, _I, _I, _I, _P, _P],
-    "cpn_dwconv3x3_tokens_wgrad": [_P, _P, _I, _I, _I, _I, _P, _P, _P, _P],
-    "cpn_dual_softmax": [_P, _I, _I, _I, _P, _P, _P, _P],
-    "cpn_dual_softmax_bwd": [_P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P],
-    "cpn_correlation": [_P, _P, _I, _I, _I, _F, _P, _P, _P, _P],
-    "cpn_l2norm_rows_bwd": [_P, _P, _P, ctypes.c_longlong, _I, _F, _P, _P],
-    "cpn_wgrad_f32": [_P, _I, _P, _I, ctypes.c_longlong, _I, _I, _P, _P, _P, _P],
-    "cpn_adam_step": [_P, _P, _I, _P, _P, _P, _P, _P, _P, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, _P],
-    "cpn_soft_argmax_pair": [_P, _I, _I, _F, _P, _P, _P],
-    "cpn_soft_argmax_pair_bwd": [_P, _I, _I, _F, _P, _P, _P, _P, _P, _P],
-    "cpn_linear_attention": [_P, _P, _P, _I, _I, _I, _I, _I, _F, _I, _P, _P, _P],
-    "cpn_cross_attention_bwd": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P],
-    "cpn_linear_attention_bwd": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _I, _P, _P, _P, _P, _P],
-    "cpn_qk_assemble": [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P],
-    "cpn_cost_volume_attention": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _P, _P, _P],
-    "cpn_cross_attention": [_P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P],
-    "cpn_conv_map7x7": [_P, _P, _P, _I, _I, _I, _P, _P, _P],
-    "cpn_pose_positional": [_P, _I, _I, _F, _P, _I, _P, _P],
-    "cpn_pose_gemv": [_P, _P, _I, _I, _I, _I, _P, _P],
-    "cpn_pose_tail": [_P, _I, _P, _P, _I, _P, _P],
-    "cpn_pack_conv_weight": [_P, _I, _I, _I, _P, _P],
-    "cpn_trunk_conv_bn_act": [_P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _F, _P, _I, _P, _P, _P, _P],
-    "cpn_bn_act": [_P, _P, _P, _P, _P, _P, _F, _I, _I, _I, _I, _P, _P],
-    "cpn_prepare_input": [_P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P],
-    "cpn_resize_bilinear_ac": [_P, _P, ctypes.c_longlong, _I, _I, _I, _I, _P],
-    "cpn_resize_bilinear_ac_adjoint": [_P, _P, ctypes.c_longlong, _I, _I, _I, _I, _P],
-    "cpn_corr_mean3": [_P, _I, _P, _I, _P, _I, _I, _P, _P],
-    "cpn_conv4d_strided_bwd": [_P, _P, _P, _P] + [_I] * 10 + [_P] * 6,
-    "cpn_ssim_warp_blocks": [_I, _I],                      # returns the count of (num, den) partial pairs per item, not a status
-    "cpn_ssim_warp": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P],
-    "cpn_ssim_warp_bwd": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P],
-    "cpn_image_metrics_scratch": [_I, _I, _I],             # returns the count of partial floats, not a status
-    "cpn_image_metrics": [_P, _P, _I, _I, _I, _P, _P, _P],
-    "cpn_flow_panels": [_P, _P, _P, _I, _I, _I, _P, _P, _P, _P],
-    "cpn_depth_jet": [_P, ctypes.c_longlong, _P, _P, _P],
-    "cpn_attention_entropy_blocks": [ctypes.c_longlong],   # returns the count of partial floats, not a status
-    "cpn_attention_entropy": [_P, ctypes.c_longlong, _I, _I, _P, _P, _P],
-    "cpn_lpips_stem": [_P, _P, _P, _P, _I, _I, _I, _P, _P],
-    "cpn_lpips_head_scratch": [_I, _I, _P, _P],            # host arrays of ints; returns the count of partial floats, not a status
-    "cpn_lpips_head": [_P, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P],      # the first five are HOST arrays
-}
 
-CAM_STRIDE = 96
-CAM_TQ, CAM_M, CAM_AOWN, CAM_AOTH, CAM_KQ, CAM_KC, CAM_KO, CAM_KN = 0, 16, 32, 48, 64, 68, 72, 76
-TAB_LD = 832
-RAYC_STRIDE = 64
-LIGHTFIELD_PACK_FLOATS = 128 * 32 + 128 + 3 * (128 * 416 + 128 + 2 * (128 * 128 + 128)) + 16 * 128 + 16
-ABI_VERSION = 12               # (cpn_attend_units, round 7, cpn_ssim_warp*, round 8, cpn_image_metrics*, round 9, summaries.hip, round 10, and lpips.hip, round 11, are additive: symbols added, none altered)
-ADAM_SEG_BYTES = 48
+class HeaderError(ValueError):
+    pass
+
+
+def _ctype(decl: str, is_return: bool):
+    """ctypes type of one return type or one parameter (`const` and the parameter's name are ignored)."""
+    words = [w for w in decl.replace("*", " * ").split() if w != "const"]
+    if not words or not all(w == "*" or re.fullmatch(r"\w+", w) for w in words):
+        raise HeaderError(f"cannot classify {decl.strip()!r}")
+    if is_return:
+        if words == ["char", "*"]:
+            return ctypes.c_char_p
+    elif "*" in words:
+        return ctypes.POINTER(ctypes.c_void_p) if words[:3] == ["void", "*", "*"] else ctypes.c_void_p
+    elif " ".join(words) not in _SCALARS:
+        words = words[:-1]                     # the parameter's name
+    if " ".join(words) not in _SCALARS:
+        raise HeaderError(f"unknown type in {decl.strip()!r}")
+    return _SCALARS[" ".join(words)]
+
+
+def parse_header(text: str) -> Tuple[Dict[str, Tuple[object, List]], Dict[str, int]]:
+    """(name -> (restype, argtypes) of every cpn_ prototype, NAME -> value of every integer `#define CPN_NAME`) of a header."""
+    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    constants = {}
+    for name, expr in re.findall(r"^[ \t]*#[ \t]*define[ \t]+CPN_(\w+)[ \t]+(.+?)[ \t]*$", text, flags=re.M):
+        if re.fullmatch(r"[-0-9+*() \t]+", expr):
+            constants[name] = int(eval(expr, {"__builtins__": {}}))
+    text = re.sub(r"^[ \t]*#.*$", "", text, flags=re.M)
+    prototypes = {}
+    for ret, name, args in re.findall(r"([\w\s*]+?)\b(cpn_\w+)\s*\(([^;{}]*)\)\s*;", text):
+        if name in prototypes:
+            raise HeaderError(f"{name} is declared twice")
+        params = [] if args.strip() in ("", "void") else args.split(",")
+        prototypes[name] = (_ctype(ret, True), [_ctype(p, False) for p in params])
+    mentioned = re.findall(r"\b(cpn_\w+)\s*\(", text)
+    if sorted(mentioned) != sorted(prototypes):
+        raise HeaderError(f"not a prototype this parser reads: {sorted(set(mentioned) - set(prototypes)) or mentioned}")
+    return prototypes, constants
+
+
+with open(HEADER_PATH) as _f:
+    PROTOTYPES, CONSTANTS = parse_header(_f.read())
+if set(CONSTANTS) & set(globals()):
+    raise HeaderError(f"CPN_ constants shadow names of this module: {sorted(set(CONSTANTS) & set(globals()))}")
+globals().update(CONSTANTS)                    # every #define CPN_<NAME> <integer expression> is _hip.<NAME>
+
+# name -> argtypes
+SIGNATURES: Dict[str, List] = {name: argtypes for name, (_, argtypes) in PROTOTYPES.items()}
+
+# the constants the package and the tests read, by name
+ABI_VERSION = CONSTANTS["ABI_VERSION"]
+CAM_STRIDE = CONSTANTS["CAM_STRIDE"]
+CAM_TQ = CONSTANTS["CAM_TQ"]
+CAM_M = CONSTANTS["CAM_M"]
+CAM_AOWN = CONSTANTS["CAM_AOWN"]
+CAM_AOTH = CONSTANTS["CAM_AOTH"]
+CAM_KQ = CONSTANTS["CAM_KQ"]
+CAM_KC = CONSTANTS["CAM_KC"]
+CAM_KO = CONSTANTS["CAM_KO"]
+CAM_KN = CONSTANTS["CAM_KN"]
+TAB_LD = CONSTANTS["TAB_LD"]
+ENC_FRAG_HALVES = CONSTANTS["ENC_FRAG_HALVES"]
+RAYC_STRIDE = CONSTANTS["RAYC_STRIDE"]
+LIGHTFIELD_PACK_FLOATS = CONSTANTS["LIGHTFIELD_PACK_FLOATS"]
+ADAM_SEG_BYTES = CONSTANTS["ADAM_SEG_BYTES"]
+POSE_TAIL_TENSORS = CONSTANTS["POSE_TAIL_TENSORS"]
+LPIPS_LAYERS = CONSTANTS["LPIPS_LAYERS"]
 
 
 def declared_symbols() -> List[str]:
     """Every function name include/coponerf_hip.h declares."""
-    with open(HEADER_PATH) as f:
-        text = re.sub(r"/\*.*?\*/", "", f.read(), flags=re.S)
-    return sorted(set(re.findall(r"\b(cpn_[a-z0-9_]+)\s*\(", text)))
+    return sorted(PROTOTYPES)
 
 
 class HipLibraryError(RuntimeError):
@@ -145,55 +118,13 @@ def lib() -> ctypes.CDLL:
         handle = ctypes.CDLL(LIB_PATH)
     except OSError as e:  # pragma: no cover - depends on the machine
         raise HipLibraryError(f"cannot load {LIB_PATH}: {e}") from e
-    for name, argtypes in SIGNATURES.items():
+    for name, (restype, argtypes) in PROTOTYPES.items():
         try:
             fn = getattr(handle, name)
         except AttributeError as e:
             raise HipLibraryError(f"{LIB_PATH} does not export {name}; rebuild it") from e
         fn.argtypes = argtypes
-        fn.restype = ctypes.c_int
-    handle.cpn_abi_version.argtypes = []
-    handle.cpn_abi_version.restype = ctypes.c_int
-    handle.cpn_device_cu_count.argtypes = []
-    handle.cpn_device_cu_count.restype = ctypes.c_int
-    handle.cpn_stream_cu_count.argtypes = [_P]
-    handle.cpn_stream_cu_count.restype = ctypes.c_int
-    handle.cpn_encode_table_nodes.argtypes = [_I, _I]
-    handle.cpn_encode_table_nodes.restype = ctypes.c_longlong
-    handle.cpn_encode_units.argtypes = [_I] * 5
-    handle.cpn_encode_units.restype = ctypes.c_longlong
-    handle.cpn_linear_attention_scratch.argtypes = [_I, _I, _I, _I]
-    handle.cpn_linear_attention_scratch.restype = ctypes.c_longlong
-    handle.cpn_cost_volume_attention_scratch.argtypes = [_I] * 5
-    handle.cpn_cost_volume_attention_scratch.restype = ctypes.c_longlong
-    handle.cpn_cross_attention_bwd_scratch.argtypes = [_I, _I, _I, _I]
-    handle.cpn_cross_attention_bwd_scratch.restype = ctypes.c_longlong
-    handle.cpn_linear_attention_bwd_scratch.argtypes = [_I, _I, _I, _I, _I]
-    handle.cpn_linear_attention_bwd_scratch.restype = ctypes.c_longlong
-    handle.cpn_gather_bwd_chunks.argtypes = [_I, _I]
-    handle.cpn_gather_bwd_chunks.restype = ctypes.c_longlong
-    handle.cpn_scatter_tables_scratch.argtypes = [_I] * 6
-    handle.cpn_scatter_tables_scratch.restype = ctypes.c_longlong
-    handle.cpn_conv4d_strided_bwd_scratch.argtypes = [_I] * 10
-    handle.cpn_conv4d_strided_bwd_scratch.restype = ctypes.c_longlong
-    handle.cpn_conv4d_scratch.argtypes = [_I] * 7
-    handle.cpn_conv4d_scratch.restype = ctypes.c_longlong
-    handle.cpn_gn_stats_doubles.argtypes = [_I, _I, ctypes.c_longlong]
-    handle.cpn_gn_stats_doubles.restype = ctypes.c_longlong
-    handle.cpn_wgrad_tall_scratch.argtypes = [_I, _I]
-    handle.cpn_wgrad_tall_scratch.restype = ctypes.c_longlong
-    handle.cpn_conv_wgrad_scratch.argtypes = [_I, _I]
-    handle.cpn_conv_wgrad_scratch.restype = ctypes.c_longlong
-    handle.cpn_dwconv3x3_tokens_wgrad_scratch.argtypes = [_I, _I, _I]
-    handle.cpn_dwconv3x3_tokens_wgrad_scratch.restype = ctypes.c_longlong
-    handle.cpn_wgrad_f32_scratch_floats.argtypes = [ctypes.c_longlong, _I, _I]
-    handle.cpn_wgrad_f32_scratch_floats.restype = ctypes.c_longlong
-    handle.cpn_trunk_conv_scratch_floats.argtypes = [_I] * 7
-    handle.cpn_trunk_conv_scratch_floats.restype = ctypes.c_longlong
-    handle.cpn_adam_chunk.argtypes = []
-    handle.cpn_adam_chunk.restype = ctypes.c_int
-    handle.cpn_last_error.argtypes = []
-    handle.cpn_last_error.restype = ctypes.c_char_p
+        fn.restype = restype
     got = handle.cpn_abi_version()
     if got != ABI_VERSION:
         raise HipLibraryError(f"{LIB_PATH} has ABI version {got}, binding expects {ABI_VERSION}; rebuild it")

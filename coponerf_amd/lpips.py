@@ -42,7 +42,7 @@ CONV_CHANNELS = ((3, 64), (64, 64), (64, 128), (128, 128), (128, 256), (256, 256
                  (512, 512), (512, 512), (512, 512))
 BLOCKS = ((0, 2), (5, 7), (10, 12, 14), (17, 19, 21), (24, 26, 28))     # a 2 x 2 max pool before every block but the first
 TAP_CHANNELS = (64, 128, 256, 512, 512)                                # relu1_2, relu2_2, relu3_3, relu4_3, relu5_3
-LAYERS = 5
+LAYERS = _hip.LPIPS_LAYERS
 MIN_SIDE = 16                                                          # four pools must leave a pixel
 
 

@@ -383,7 +383,7 @@ class EncodeFn(Function):
             maps.append(dst)
         Wc = W.detach().contiguous().float()
         bc = b.detach().contiguous().float()
-        frag = torch.empty(13 * 3 * 4 * 64 * 8, dtype=torch.float16, device=dev)
+        frag = torch.empty(_hip.ENC_FRAG_HALVES, dtype=torch.float16, device=dev)
         wtab = torch.empty(_hip.TAB_LD, 768, dtype=torch.float16, device=dev)
         call("cpn_pack_encode_weights", Wc.data_ptr(), Wc.shape[1], frag.data_ptr(), wtab.data_ptr(), s)
         nimg = z0.shape[0]

@@ -816,6 +816,7 @@ class HipOps:
             for t in (m.weight, m.bias):
                 assert t.is_contiguous() and t.dtype == torch.float32 and t.device == h.device
                 ptrs.append(t.data_ptr())
+        assert len(ptrs) == _hip.POSE_TAIL_TENSORS
         arr = (ctypes.c_void_p * len(ptrs))(*ptrs)
         out = torch.empty(h.shape[0], 4, 4, dtype=torch.float32, device=h.device)
         call("cpn_pose_tail", h.data_ptr(), nsplit, bias0, arr, h.shape[0], out.data_ptr(), _stream())

@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define CPN_ABI_VERSION 12   /* cpn_attend_units (round 7) is additive - one more symbol, none altered: the version stays */
+#define CPN_ABI_VERSION 12   /* cpn_attend_units (round 7), cpn_ssim_warp* (round 8), cpn_image_metrics* (round 9), summaries.hip (round 10) and lpips.hip (round 11) are additive - symbols added, none altered: the version stays */
 
 #define CPN_E_ARG   (-1)   /* bad argument (null pointer, size, alignment) */
 #define CPN_E_SHAPE (-2)   /* shape not supported by the compiled tiles    */
@@ -120,11 +120,12 @@ int cpn_local_hidden(const float* loc8, const float* coords9, const float* w, in
  * A row is then 4 weighted table taps + a K = 80 MFMA product over [level-3 gather (64) | pt (3) | bias hi, lo | 0].
  * Table rows hold the 832 channels in natural order (1664 B, 13 cache lines; the kernel walks 13 slices of 64 channels).
  *   cpn_pack_encode_weights: W (832, ldw >= 835) fp32 query_encode_latent.weight ->
- *       wfrag (13*3*4*64*8 halves) MFMA A-operand fragments of W[:, 768:835] (K padded to 96)
+ *       wfrag (CPN_ENC_FRAG_HALVES halves) MFMA A-operand fragments of W[:, 768:835] (K padded to 96)
  *       wtab  (832, 768) fp16 table projection weights W[:, 0:768]
  *   the layer itself: cpn_encode_key below (until round 5 also as a kernel without the key layer, cpn_encode_hidden)  */
 #define CPN_TAB_LD    832
 #define CPN_NODE_PAD  4
+#define CPN_ENC_FRAG_HALVES (13 * 3 * 4 * 64 * 8)
 long long cpn_encode_table_nodes(int H, int W);
 int cpn_pack_encode_weights(const float* W, int ldw, uint16_t* wfrag, uint16_t* wtab, void* stream);
 int cpn_node_features(const uint16_t* map0, const uint16_t* map1, const uint16_t* map2, int H, int W, int nimg,
