@@ -5,7 +5,8 @@
 
 geometry.hip is compiled with -ffp-contract=off: its arithmetic must reproduce the oracle's
 IEEE operation sequence bit for bit (sample coordinates / tap indices); ssim_warp.hip likewise, for the
-sampling coordinates of the flow warp (its window sums name their FMAs), and summaries.hip, which shares them.
+sampling coordinates of the flow warp (its window sums name their FMAs), and summaries.hip, which shares them;
+novel_views.hip for the one-rounding-per-operation sums of its resample and its byte pack.
 """
 import os
 import subprocess
@@ -46,6 +47,7 @@ UNITS = [
     ("image_metrics.hip", []),
     ("summaries.hip", ["-ffp-contract=off"]),
     ("lpips.hip", []),                                     # its two exact statements switch contraction off by pragma
+    ("novel_views.hip", ["-ffp-contract=off"]),            # one rounding per operation in the resample sums and the byte pack
 ]
 
 

@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define CPN_ABI_VERSION 12   /* cpn_attend_units (round 7), cpn_ssim_warp* (round 8), cpn_image_metrics* (round 9), summaries.hip (round 10) and lpips.hip (round 11) are additive - symbols added, none altered: the version stays */
+#define CPN_ABI_VERSION 12   /* cpn_attend_units (round 7), cpn_ssim_warp* (round 8), cpn_image_metrics* (round 9), summaries.hip (round 10), lpips.hip (round 11) and novel_views.hip (round 12) are additive - symbols added, none altered: the version stays */
 
 #define CPN_E_ARG   (-1)   /* bad argument (null pointer, size, alignment) */
 #define CPN_E_SHAPE (-2)   /* shape not supported by the compiled tiles    */
@@ -733,6 +733,33 @@ int cpn_lpips_stem(const float* pred, const float* target, const float* w, const
 int cpn_lpips_head_scratch(int N, int layers, const int* host_h, const int* host_w);
 int cpn_lpips_head(const float* const* host_feat, const float* const* host_lin, const int* host_C, const int* host_h,
                    const int* host_w, int layers, int N, float* partial, float* out, float* per_layer, void* stream);
+
+/* ==== novel views from two photos: fit the photos, the camera path, the frames (round 12) ================================
+ * What a caller of test.py does by hand around forward(val=True).  The symbols are additive: the ABI version stays.
+ * cpn_fit_images_u8 replaces cv2.resize (realestate10k_dataio.py:340), the centre square crop of
+ *   utils_training/data_util.py:116-121 and `rgb.astype(np.float32) / 127.5 - 1` (dataio.py:353) for photos of any size.
+ *   img (N, Hi, Wi, 3) bytes.  The crop is rows [Hi/2 - m/2, + side), columns [Wi/2 - m/2, + side), m = min(Hi, Wi),
+ *   side = (m / 2) * 2; it is resampled to size x size, separably: output i of an axis reads the taps
+ *   j in [max(trunc(c - sup + 0.5), 0), min(trunc(c + sup + 0.5), side)) with weights max(0, 1 - |j + 0.5 - c| / sup) over their
+ *   sum, c = (i + 0.5) side / size, sup = max(side / size, 1) - F.interpolate(mode="bilinear", antialias=True,
+ *   align_corners=False); antialias = 0 takes sup = 1 (antialias=False: the half-pixel bilinear rule of cv2.resize, in float).
+ *   Image n goes to out + (n % B) * batch_stride + (n / B) * view_stride (floats) as (size, size, 3) fp32 = v / 127.5f - 1.0f
+ *   of the fp32 resampled v, never rounded to a byte; side == size gives cpn_prepare_input's values bit for bit.
+ *   tmp: N * size * side * 3 floats.  Tap positions and weights in float64, rounded once; fp32 sums in tap order, rows first.
+ *   2 launches; at most 1024 taps per axis (CPN_E_SHAPE beyond).
+ * cpn_camera_path replaces test.py:96-121 (make_circle, unused there) and the ground-truth query pose: out (K, B, 4, 4) fp32,
+ *   pose k of pair b = [exp(t_k log R) | t_k p] of rel_pose[b] = [R | p] (B, 4, 4) fp32 on the device, t (K) float64 on the
+ *   device, any real t_k (t_k == 0: the identity, t_k == 1: R itself).  An angle below 1e-12 gives the identity rotation; beyond
+ *   a quarter turn the axis comes from the symmetric part of R.  sway > 0 adds R_k (sway cos(2 pi turns t_k),
+ *   sway sin(2 pi turns t_k), 0) to the position.  float64 inside, one launch.
+ * cpn_pack_frames replaces the float -> uint8 round trip of a frame on the host: rgb (B, h * w, 3) fp32 in [-1, 1] -> out
+ *   (B, h, w, 3) bytes = rint(min(max((x + 1) * 127.5, 0), 255)), NaN -> 0, every operation rounded to fp32.  With depth
+ *   (B, h * w) fp32 and table (256, 3) fp32 (both or neither) out is (B, h, 2 w, 3): the right half is cpn_depth_jet's lookup
+ *   of depth (summaries.py:129-133) times 255, rounded the same way.  One launch.                                             */
+int cpn_fit_images_u8(const uint8_t* img, int N, int B, int Hi, int Wi, int size, int antialias, float* tmp, float* out,
+                      long long batch_stride, long long view_stride, void* stream);
+int cpn_camera_path(const float* rel_pose, const double* t, int B, int K, double sway, double turns, float* out, void* stream);
+int cpn_pack_frames(const float* rgb, const float* depth, const float* table, int B, int h, int w, uint8_t* out, void* stream);
 
 #ifdef __cplusplus
 }
