@@ -32,7 +32,10 @@ UNITS = [
     ("attend_units.hip", []),
     ("linear_f32.hip", []),
     ("rayout.hip", []),
-    ("ufc.hip", []),
+    ("ufc_conv4d.hip", []),
+    ("ufc_wgrad.hip", []),
+    ("ufc_corr.hip", []),
+    ("ufc_match.hip", []),
     ("ufc_attn.hip", []),
     ("ufc_strided_bwd.hip", []),
     ("encoder.hip", []),

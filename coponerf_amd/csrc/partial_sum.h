@@ -1,0 +1,51 @@
+// The two fixed-order sums of partial results that keep the training gradients bit-reproducible, once each: the reducers of
+// ufc_wgrad.hip and ufc_strided_bwd.hip (sum_partials_16x64), of wgrad_f32.hip and wgrad_tall.hip (sum_slabs_f32x4).
+#pragma once
+#include "common.h"
+
+namespace {
+
+// Body of a 1 024-thread workgroup that finishes the outputs blockIdx.x * 64 + lane < n_out from n_part partials each:
+//   wave p (0 .. 15) adds the partials p, p + 16, p + 32, ... in ascending order, starting from 0.0f;
+//   wave 0 then adds the 16 wave sums in the order 0 .. 15, starting from 0.0f, and stores.
+// load(part, out) returns a partial, store(out, value) writes the result.  Eight loads are in flight per thread (issued
+// together, added in ascending order), the rest is walked with stride 16: the same sequence of additions either way.
+// Why 16 x 64: few outputs, hundreds of partials; one thread per output waits for one load at a time on a handful of
+// workgroups.  Measured per call: 4 waves walking 64 partials each took 17 us (conv_wgrad_planes); one thread per output
+// 70 us on 40 workgroups, 2.4 x the kernel that produces the partials (dwconv3x3_tokens_wgrad), and 21 us on five (strided
+// Conv4d).  Must be called by all threads of the workgroup (contains a barrier).
+template <class Load, class Store>
+__device__ __forceinline__ void sum_partials_16x64(int n_out, long long n_part, Load load, Store store) {
+    __shared__ float sh[16][64];
+    const int j = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int i = blockIdx.x * 64 + j;
+    float sacc = 0.0f;
+    if (i < n_out) {
+        long long b = wave;
+        for (; b + 16 * 7 < n_part; b += 16 * 8) {
+            float v[8];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) v[u] = load(b + 16 * u, i);
+#pragma unroll
+            for (int u = 0; u < 8; ++u) sacc += v[u];
+        }
+        for (; b < n_part; b += 16) sacc += load(b, i);
+    }
+    sh[wave][j] = sacc;
+    __syncthreads();
+    if (wave != 0 || i >= n_out) return;
+    float v = 0.0f;
+#pragma unroll
+    for (int q = 0; q < 16; ++q) v += sh[q][j];
+    store(i, v);
+}
+
+// Element i of the sum of nslab slabs of n4 16-byte vectors each, in slab order: part[i] + part[n4 + i] + part[2 n4 + i] ...
+__device__ __forceinline__ f32x4 sum_slabs_f32x4(const float* __restrict__ part, long long n4, int nslab, long long i) {
+    f32x4 s = reinterpret_cast<const f32x4*>(part)[i];
+#pragma unroll 8
+    for (int q = 1; q < nslab; ++q) s += reinterpret_cast<const f32x4*>(part)[q * n4 + i];
+    return s;
+}
+
+}  // namespace

@@ -9,6 +9,7 @@
 // their permute copies / two strided softmaxes and two einsums): HBM/launch-bound glue.  Here each is two launches
 // that read every operand once in its native layout.  fp32 throughout.
 #include "common.h"
+#include "ac_taps.h"
 
 namespace {
 
@@ -698,12 +699,9 @@ __device__ __forceinline__ void ac_taps(int Y, int X, int n_out, int n_in, int (
     // the 4 source positions / weights of output pixel (Y, X) of an n_in -> n_out bilinear resize (align_corners=True),
     // with the arithmetic of resize_bilinear_ac_kernel
     const float s = n_out > 1 ? (float)(n_in - 1) / (float)(n_out - 1) : 0.0f;
-    const float fy = s * (float)Y, fx = s * (float)X;
-    const int y0 = (int)fy, x0 = (int)fx;
-    const int y1 = y0 + (y0 < n_in - 1), x1 = x0 + (x0 < n_in - 1);
-    const float ly = fy - (float)y0, lx = fx - (float)x0;
-    idx[0] = y0 * n_in + x0; idx[1] = y0 * n_in + x1; idx[2] = y1 * n_in + x0; idx[3] = y1 * n_in + x1;
-    w[0] = (1.0f - lx) * (1.0f - ly); w[1] = lx * (1.0f - ly); w[2] = (1.0f - lx) * ly; w[3] = lx * ly;
+    const AxisTap ty = axis_tap(Y, n_in, s), tx = axis_tap(X, n_in, s);
+    idx[0] = ty.i0 * n_in + tx.i0; idx[1] = ty.i0 * n_in + tx.i1; idx[2] = ty.i1 * n_in + tx.i0; idx[3] = ty.i1 * n_in + tx.i1;
+    w[0] = (1.0f - tx.l) * (1.0f - ty.l); w[1] = tx.l * (1.0f - ty.l); w[2] = (1.0f - tx.l) * ty.l; w[3] = tx.l * ty.l;
 }
 
 // K1: workgroup = (block of 32 low-res positions, (b, h)).  Kd of its positions as a GATHER over the tokens whose bilinear
@@ -738,10 +736,8 @@ __global__ __launch_bounds__(256) void cva_kd_kernel(const float* __restrict__ k
     // the upsampling is separable: weight of token (Y, X) at position (y, x) = wy(Y, y) * wx(X, x), each the 1-D bilinear
     // weight of resize_bilinear_ac_kernel (y0 = (int)(sc*Y), y1 = y0 + (y0 < hs-1), ly = sc*Y - y0)
     auto w1d = [&](int T, int t) {
-        const float f = sc * (float)T;
-        const int t0 = (int)f, t1 = t0 + (t0 < hs - 1);
-        const float l = f - (float)t0;
-        return (t == t0 ? 1.0f - l : 0.0f) + (t == t1 ? l : 0.0f);
+        const AxisTap a = axis_tap(T, hs, sc);
+        return (t == a.i0 ? 1.0f - a.l : 0.0f) + (t == a.i1 ? a.l : 0.0f);
     };
     for (int pp = g; pp < CVA_BP; pp += 8) {
         const int p = blk * CVA_BP + pp;

@@ -1,7 +1,7 @@
 // VJP of the strided Conv4d layers (models/conv4d.py:57-135 with stride > 1: k3 s2 p1 on 32^4, k5 s4 p2 on 64^4 —
 // Encoder4D((1, nhead), k, s, p) of UFC.embedding / UFCLayer.feat_to_corr1,2, aggregation.py:198-199, 369-371).
 //
-// Forward (csrc/ufc.hip): the two max-pooled volumes
+// Forward (csrc/ufc_conv4d.hip): the two max-pooled volumes
 //   Ps[b,c,Y,X,sy',sx'] = max_{dy,dx<s} x[b,c,Y,X,sy'*s+dy,sx'*s+dx]     (query branch: support dims pooled, ceil mode)
 //   Pq[b,c,qy',qx',U,V] = max_{dy,dx<s} x[b,c,qy'*s+dy,qx'*s+dx,U,V]     (support branch: query dims pooled)
 // and   y[b,o,qy,qx,sy,sx] = bq[o] + bs[o] + sum_{c,i,j} wq[o,c,i,j] Ps[b,c,qy*s+i-p,qx*s+j-p,sy,sx]
@@ -18,17 +18,12 @@
 #include <algorithm>
 
 #include "common.h"
+#include "conv4d_geometry.h"
+#include "partial_sum.h"
 
 namespace {
 
 constexpr int WG_CHUNK = 4096;             // positions per weight-gradient workgroup (16 per thread)
-
-struct SGeo {
-    int B, Cin, Cout, Hq, Wq, Hs, Ws, k, s, p, Oq, Pq, Os, Ps;
-    __host__ __device__ long long n_ps() const { return (long long)B * Cin * Hq * Wq * Os * Ps; }
-    __host__ __device__ long long n_pq() const { return (long long)B * Cin * Oq * Pq * Hs * Ws; }
-    __host__ __device__ long long npos() const { return (long long)Oq * Pq * Os * Ps; }
-};
 
 __device__ __forceinline__ bool takes_max(float v, float m) { return v > m || v != v; }
 
@@ -232,48 +227,25 @@ __global__ __launch_bounds__(1024) void wgrad_strided_reduce_kernel(const float*
                                                                     const float* __restrict__ partb, int nchunk, SGeo g,
                                                                     float* __restrict__ gwq, float* __restrict__ gws,
                                                                     float* __restrict__ gb) {
-    // 64 outputs per workgroup, the chunks split over 16 waves (fixed combination order); one thread per output walking all
-    // chunks on five workgroups took 21 us per call
-    __shared__ float sh[16][64];
-    const int kk = g.k * g.k, na = g.Cout * g.Cin, ntap = 2 * kk;
-    const int nw = ntap * na;
-    const int j = threadIdx.x & 63, p = threadIdx.x >> 6;
-    const int e = blockIdx.x * 64 + j;
-    float v = 0.0f;
-    if (e < nw) {
-        const int tap = e / na, a = e % na;
-        for (int ch = p; ch < nchunk; ch += 16) v += part[((size_t)ch * ntap + tap) * na + a];
-    } else if (e < nw + g.Cout) {
-        for (int ch = p; ch < nchunk; ch += 16) v += partb[(size_t)ch * g.Cout + (e - nw)];
-    }
-    sh[p][j] = v;
-    __syncthreads();
-    if (p == 0 && e < nw + g.Cout) {
-        float acc = 0.0f;
-#pragma unroll
-        for (int q = 0; q < 16; ++q) acc += sh[q][j];
-        if (e < nw) {
-            const int tap = e / na, a = e % na;
-            const int br = tap / kk, ij = tap % kk;
-            (br == 0 ? gwq : gws)[(size_t)a * kk + ij] = acc;        // a = o * Cin + c
-        } else {
-            gb[e - nw] = acc;
-        }
-    }
-}
-
-bool make_geo(int B, int Cin, int Cout, int Hq, int Wq, int Hs, int Ws, int k, int s, int p, SGeo* g) {
-    auto co = [&](int n) { return (n + 2 * p - k) / s + 1; };
-    auto po = [&](int n) { return (n + s - 1) / s; };
-    *g = SGeo{B, Cin, Cout, Hq, Wq, Hs, Ws, k, s, p, co(Hq), co(Wq), co(Hs), co(Ws)};
-    return g->Oq == po(Hq) && g->Pq == po(Wq) && g->Os == po(Hs) && g->Ps == po(Ws);
+    // output e < nw is element e = tap * na + a of part[chunk], the rest are the biases of partb[chunk]; the chunks in the
+    // fixed order of sum_partials_16x64
+    const int kk = g.k * g.k, na = g.Cout * g.Cin, nw = 2 * kk * na;
+    sum_partials_16x64(
+        nw + g.Cout, nchunk,
+        [&](long long ch, int e) { return e < nw ? part[(size_t)ch * nw + e] : partb[(size_t)ch * g.Cout + (e - nw)]; },
+        [&](int e, float acc) {
+            const int tap = e / na, a = e % na;                              // a = o * Cin + c
+            if (e < nw) (tap / kk == 0 ? gwq : gws)[(size_t)a * kk + tap % kk] = acc;
+            else gb[e - nw] = acc;
+        });
 }
 
 long long nchunks(const SGeo& g) { return ((long long)g.B * g.npos() + WG_CHUNK - 1) / WG_CHUNK; }
 
 }  // namespace
 
-// floats of scratch: Ps | Pq | gPs | gPq | window positions of the maxima (bytes) | weight / bias gradient partials
+// floats of scratch: Ps | Pq | gPs | gPq (n_ps, n_pq, n_ps, n_pq; n = n_ps + n_pq) | window positions of the maxima (n bytes, (n + 3) / 4
+// floats) | part[chunk][tap = branch * k*k + i*k + j][o * Cin + c] | partb[chunk][o], chunks = ceil(B * npos / 4096)
 extern "C" long long cpn_conv4d_strided_bwd_scratch(int B, int Cin, int Cout, int Hq, int Wq, int Hs, int Ws, int k, int s,
                                                     int p) {
     SGeo g;
@@ -319,12 +291,8 @@ extern "C" int cpn_conv4d_strided_bwd(const float* x, const float* dy, const flo
     }
     if (gwq) {
         dim3 grid((unsigned)nch, 2 * k * k);
-        if (Cout == 8 && Cin == 1)
-            hipLaunchKernelGGL((wgrad_strided_kernel<8, 1>), grid, dim3(256), 0, st, dy, psv, pqv, g, part, partb);
-        else if (Cout == 8 && Cin == 2)
-            hipLaunchKernelGGL((wgrad_strided_kernel<8, 2>), grid, dim3(256), 0, st, dy, psv, pqv, g, part, partb);
-        else
-            hipLaunchKernelGGL((wgrad_strided_kernel<8, 8>), grid, dim3(256), 0, st, dy, psv, pqv, g, part, partb);
+        auto* kernel = Cin == 1 ? wgrad_strided_kernel<8, 1> : Cin == 2 ? wgrad_strided_kernel<8, 2> : wgrad_strided_kernel<8, 8>;
+        hipLaunchKernelGGL(kernel, grid, dim3(256), 0, st, dy, psv, pqv, g, part, partb);
         hipLaunchKernelGGL(wgrad_strided_reduce_kernel, dim3(cpn_cdiv(2LL * k * k * Cout * Cin + Cout, 64)), dim3(1024), 0, st,
                            part, partb, (int)nch, g, gwq, gws, gb);
         CPN_LAUNCH_CHECK("cpn_conv4d_strided_bwd(wgrad)");

@@ -17,6 +17,7 @@
 //               wave 0 writes the slab's partial tile; a second kernel sums the slabs in slab order: deterministic
 //   bias      = the tiles of the first column block also sum their dY operands (4 more accumulators per lane)
 #include "common.h"
+#include "partial_sum.h"
 
 namespace {
 
@@ -151,9 +152,7 @@ __global__ void wgrad_f32_reduce_kernel(const float* __restrict__ part, const fl
                                         long long n4, int O, float* __restrict__ dW, float* __restrict__ db) {
     const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (t < n4) {
-        f32x4 s = reinterpret_cast<const f32x4*>(part)[t];
-        for (int k = 1; k < nslab; ++k) s += reinterpret_cast<const f32x4*>(part)[t + (long long)k * n4];
-        reinterpret_cast<f32x4*>(dW)[t] = s;
+        reinterpret_cast<f32x4*>(dW)[t] = sum_slabs_f32x4(part, n4, nslab, t);
     } else if (db != nullptr && t - n4 < O) {
         const long long o = t - n4;
         float s = bpart[o];
@@ -173,6 +172,7 @@ static inline int wf_slabs(long long R, int O, int I) {
 
 }  // namespace
 
+// floats of scratch: part[slab][O][I] for all slabs, then bpart[slab][O]
 extern "C" long long cpn_wgrad_f32_scratch_floats(long long R, int O, int I) {
     return (long long)wf_slabs(R, O, I) * ((long long)O * I + O);
 }
@@ -191,12 +191,8 @@ extern "C" int cpn_wgrad_f32(const float* dY, int ldy, const float* X, int ldx, 
     float* bpart = scratch + (size_t)nslab * O * I;
     hipStream_t st = (hipStream_t)stream;
     const unsigned grid = (unsigned)(nslab * nto * nti);
-    if (db != nullptr)
-        hipLaunchKernelGGL(wgrad_f32_kernel<true>, dim3(grid), dim3(64 * WF_WAVES), 0, st, dY, ldy, X, ldx, R, O, I, nto, nti,
-                           slab_rows, part, bpart);
-    else
-        hipLaunchKernelGGL(wgrad_f32_kernel<false>, dim3(grid), dim3(64 * WF_WAVES), 0, st, dY, ldy, X, ldx, R, O, I, nto, nti,
-                           slab_rows, part, bpart);
+    hipLaunchKernelGGL(db != nullptr ? wgrad_f32_kernel<true> : wgrad_f32_kernel<false>, dim3(grid), dim3(64 * WF_WAVES), 0, st, dY,
+                       ldy, X, ldx, R, O, I, nto, nti, slab_rows, part, bpart);
     CPN_LAUNCH_CHECK("cpn_wgrad_f32");
     const long long n4 = (long long)O * I / 4;
     hipLaunchKernelGGL(wgrad_f32_reduce_kernel, dim3(cpn_cdiv(n4 + (db ? O : 0), 256)), dim3(256), 0, st, part, bpart, nslab,

@@ -22,6 +22,7 @@
 //               loads: non-temporal ones re-fetched every tile's operands, 3x slower)
 //   result    = per-slab partial sums, summed in a fixed order by a second kernel (deterministic; also applies 1/scale)
 #include "common.h"
+#include "partial_sum.h"
 
 // timing-only phase ablations for tools/wgrad_bench.py (results are wrong): 1 no global loads, 2 no LDS stage writes,
 // 4 no fragment reads, 8 no MFMA
@@ -167,15 +168,14 @@ __global__ __launch_bounds__(256) void wgrad_tall_reduce_kernel(const float* __r
                                                                 const float* __restrict__ scale, float* __restrict__ dW) {
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
     if (i >= n4) return;
-    f32x4 s = reinterpret_cast<const f32x4*>(part)[i];
-#pragma unroll 8
-    for (int q = 1; q < nslab; ++q) s += reinterpret_cast<const f32x4*>(part)[q * n4 + i];
+    const f32x4 s = sum_slabs_f32x4(part, n4, nslab, i);
     const float inv = scale ? 1.0f / scale[0] : 1.0f;
     reinterpret_cast<f32x4*>(dW)[i] = s * inv;
 }
 
 }  // namespace
 
+// floats of `part`: [slab][N][K]; the slab count is the result divided by N * K
 extern "C" long long cpn_wgrad_tall_scratch(int N, int K) {
     return (N < WT_N || K < WT_K || N % WT_N || K % WT_K) ? 0 : (long long)wt_slabs(N, K) * N * K;
 }

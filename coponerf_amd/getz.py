@@ -326,7 +326,7 @@ class _DWConv(nn.Module):
     def forward(self, x):                       # (B, L, C) tokens
         B, L, C = x.shape
         if x.is_cuda and x.dtype == torch.float32 and C % 4 == 0:
-            from .ufc_ops import DwConvTokensFn            # the convolution on the token layout itself (csrc/ufc.hip)
+            from .ufc_ops import DwConvTokensFn            # the convolution on the token layout itself (csrc/ufc_wgrad.hip)
             return DwConvTokensFn.apply(x, self.dwconv.weight, self.dwconv.bias, self.size)
         xm = x.transpose(1, 2).reshape(B, C, self.size, self.size)
         y = self.dwconv(xm)

@@ -1,6 +1,6 @@
 """HIP bindings of the UFC 4-D operators (the `ops` interface used by coponerf_amd.getz).
 
-Forward values ALWAYS come from the HIP kernels (csrc/ufc.hip).  When a caller trains (BASELINE config 3) the
+Forward values ALWAYS come from the HIP kernels (csrc/ufc_*.hip).  When a caller trains (BASELINE config 3) the
 operators are wrapped in `_HipForwardVjp`: the backward pass evaluates the vector-Jacobian product of the same
 operator written with library ops (MIOpen conv2d / pooling / group_norm, hipBLASLt einsum) at the saved inputs.
 That restatement is never used to produce a forward value.
@@ -604,7 +604,7 @@ _LINSPACE = {}
 
 
 class HipOps:
-    """conv4d + GroupNorm + ReLU, cosine correlation, soft-argmax (csrc/ufc.hip) and the two attention forms of
+    """conv4d + GroupNorm + ReLU, cosine correlation, soft-argmax (csrc/ufc_conv4d.hip, ufc_corr.hip, ufc_match.hip) and the two attention forms of
     UFCLayer (csrc/ufc_attn.hip) on gfx950."""
 
     @staticmethod

@@ -245,7 +245,7 @@ def test_pipelined_images_equal_serial(dev):
 
 def test_get_z_is_bit_reproducible(dev):
     """Two get_z calls on the same pair give the same bits (features, flows, pose): the GroupNorm sums of the 63 Conv4d
-    layers are reduced in a fixed order by the last workgroup of each sample (csrc/ufc.hip gn_publish) — the per-slot
+    layers are reduced in a fixed order by the last workgroup of each sample (csrc/ufc_conv4d.hip gn_publish) — the per-slot
     atomicAdd accumulation of round 2 made every run differ in the last bits, and with val=True the estimated pose feeds
     the view-2 sample coordinates."""
     from coponerf_amd import CoPoNeRF

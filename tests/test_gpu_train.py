@@ -528,6 +528,34 @@ def test_resize_adjoint_kernel_equals_library_backward(h, n):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("h,w,H,W", [(8, 8, 16, 16), (3, 5, 7, 12), (2, 2, 4, 4), (4, 4, 7, 7)])
+def test_resize_adjoint_is_the_transpose_of_the_forward(h, w, H, W):
+    """cpn_resize_bilinear_ac_adjoint is the transpose of cpn_resize_bilinear_ac's matrix, bit for bit: both form every tap
+    with the one axis_tap of csrc/ac_taps.h (a rounded product, then a difference).  The forward's matrix comes from the
+    h*w one-hot planes, the adjoint's from the H*W one-hot gradients; an entry is one product of two 1-D weights on either
+    side.  With the fraction fused into one multiply-add on the adjoint's side alone, (8,8,16,16) and (3,5,7,12) differ."""
+    if not torch.cuda.is_available():
+        pytest.skip("no HIP device")
+    import numpy as np
+    from coponerf_amd._hip import call
+    dev = torch.device("cuda:0")
+    st = torch.cuda.current_stream().cuda_stream
+    # exact equality needs the last fine index not to be clamped with a non-zero fraction
+    for n, N in ((h, H), (w, W)):
+        scale = np.float32(n - 1) / np.float32(N - 1)
+        assert np.float32(scale * np.float32(N - 1)) <= n - 1, (n, N)
+    coarse, fine = torch.eye(h * w, device=dev), torch.eye(H * W, device=dev)
+    fwd = torch.empty(h * w, H * W, device=dev)                          # row = coarse one-hot, i.e. the matrix transposed
+    call("cpn_resize_bilinear_ac", coarse.data_ptr(), fwd.data_ptr(), h * w, h, w, H, W, st)
+    adj = torch.empty(H * W, h * w, device=dev)                          # row = fine one-hot, i.e. the adjoint transposed
+    call("cpn_resize_bilinear_ac_adjoint", fine.data_ptr(), adj.data_ptr(), H * W, h, w, H, W, st)
+    torch.cuda.synchronize()
+    forward, adjoint = fwd.t(), adj.t()                                  # (H*W, h*w) and (h*w, H*W)
+    assert float(forward.sum(1).min()) > 0.99
+    assert torch.equal(adjoint, forward.t())
+
+
+@pytest.mark.gpu
 @pytest.mark.parametrize("R,O,I,ldy,ldx", [(256, 4, 4, 4, 4), (257, 64, 64, 64, 64), (1000, 128, 144, 128, 144),
                                            (4099, 68, 260, 72, 264), (8192, 256, 1024, 256, 1024),
                                            (32768, 1024, 256, 1024, 256), (16384, 128, 416, 128, 416)])

@@ -1,6 +1,6 @@
 """Float64 references, with element-wise error bounds, of the fp32 kernels behind the training backward of get_z - the
 soft-argmax pair, the dual softmax, the cost-volume cross attention, the linear attention, GroupNorm + ReLU, the Conv4d data
-gradient, the row normalisation's VJP (csrc/ufc.hip, csrc/ufc_attn.hip) - and the case lists, for tests/test_ufc_bwd_ref.py
+gradient, the row normalisation's VJP (csrc/ufc_match.hip, csrc/ufc_conv4d.hip, csrc/ufc_corr.hip, csrc/ufc_attn.hip) - and the case lists, for tests/test_ufc_bwd_ref.py
 (CPU) and tests/test_gpu_ufc_f64.py (GPU).  Helpers, not tests.
 
 Every reference takes the values a kernel READS (fp32 bits converted to float64; a backward that is handed forward outputs or
@@ -288,7 +288,7 @@ def dual_f_ref(a, rstat, cstat):
 
 def dual_bwd_ref(a, rstat, cstat, f, df):
     """da = 2 r c df - r Srow - c Scol with r, c recomputed from the statistics as given and Srow_i = sum_j f df,
-    Scol_j = sum_i f df over the f as GIVEN (csrc/ufc.hip states it so; r c is f up to f's own rounding).  Terms:
+    Scol_j = sum_i f df over the f as GIVEN (csrc/ufc_match.hip states it so; r c is f up to f's own rounding).  Terms:
         expf      the three products' exponentials: |2 r c df| (ar + ac + 4) u + |r Srow| (ar + 2) u + |c Scol| (ac + 2) u
         sum       r gam(ceil(M/64) + 7) sum_j |f df| + c gam(ceil(L/64) + CR_GROUPS + 1) sum_i |f df|
         ops       gam(6) (|2 r c df| + |r Srow| + |c Scol|): divisions, products, the two subtractions - a difference of
