@@ -6,7 +6,8 @@
 geometry.hip is compiled with -ffp-contract=off: its arithmetic must reproduce the oracle's
 IEEE operation sequence bit for bit (sample coordinates / tap indices); ssim_warp.hip likewise, for the
 sampling coordinates of the flow warp (its window sums name their FMAs), and summaries.hip, which shares them;
-novel_views.hip for the one-rounding-per-operation sums of its resample and its byte pack.
+novel_views.hip for the one-rounding-per-operation sums of its resample and its byte pack; epipolar.hip for the float64
+operation sequence of its fundamental matrices and line end points.
 """
 import os
 import subprocess
@@ -51,6 +52,7 @@ UNITS = [
     ("summaries.hip", ["-ffp-contract=off"]),
     ("lpips.hip", []),                                     # its two exact statements switch contraction off by pragma
     ("novel_views.hip", ["-ffp-contract=off"]),            # one rounding per operation in the resample sums and the byte pack
+    ("epipolar.hip", ["-ffp-contract=off"]),               # one rounding per float64 operation of the line geometry
 ]
 
 

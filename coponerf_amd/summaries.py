@@ -12,9 +12,20 @@ matplotlib colour map and a `.cpu()` per grid; every one of those host reads wai
   SummaryLog         packs a Summary into ONE pinned buffer with one asynchronous copy and writes   test.py:270, wrapper.py:240
                      it `lag` calls later, when no render waits for it
 
-Left out: the epipolar-line drawings (summary/inspect_epipolar_geometry.py: cv2.circle / cv2.line) and the 1-pixel contour
-that overlay_semantic_mask draws around the masked region (cv2.findContours / drawContours).  Tags `epipolar_GT` and
-`epipolar_pred` are therefore never written, and `masked_warped_img*` lack the contour line.
+  epipolar_lines     two_view_geometry and the epilines' end points in float64: csrc/epipolar.hip, 1 launch   inspect_epipolar_geometry.py:13-43, 54-55
+  epipolar_panels    the nine dots on view 1 and their epipolar lines on view 0, under the estimated    inspect_epipolar_geometry.py:46-57, 75-120
+                     and under the true pose, whole batch: 2 launches (the lines, the pixels)
+  mask_contour       the 1-pixel contour of overlay_semantic_mask around the invalid region, 1 launch    summaries.py:65-71
+
+The two OpenCV pieces are opt-in (`epipolar=True`, `contour=True` of image_summaries / SummaryLog): by default the tags
+`epipolar_GT` / `epipolar_pred` are not written and `masked_warped_img*` carry no contour, as before.  Which pixels a disc, a
+thick line and the contour cover is this package's own definition (include/coponerf_hip.h); `cv2` was not available, so
+agreement with OpenCV's rasteriser on edge pixels has not been checked.  Where the reference's inspect() raises (a line with
+b == 0, a non-finite pose, an end point beyond int32) its `except` drops both images for the whole batch; here that one line
+is left out and everything else is drawn.  The epilines are not scaled to a^2 + b^2 = 1 (the drawing does not depend on it),
+and a pixel no line covers keeps its value instead of passing through 0.4 v + 0.6 v.
+
+Left out: drawpoint (inspect_epipolar_geometry.py:59-69), which nothing upstream calls.
 """
 from __future__ import annotations
 
@@ -30,6 +41,11 @@ from . import _hip
 
 IMAGE_TAGS = ("predictions", "depth_images", "context_images", "query_images", "warped_img", "masked_warped_img",
               "warped_img_flip", "masked_warped_img_flip")
+EPIPOLAR_TAGS = ("epipolar_GT", "epipolar_pred")            # written after IMAGE_TAGS, in this order (summaries.py:213-219)
+
+# inspect_epipolar_geometry.py:83-84: the nine points are the {S/4, S/2, 3S/4}^2 grid (64 / 128 / 192 at S = 256), x outermost
+EPIPOLAR_COLORS = ((63, 228, 92), (222, 155, 167), (56, 220, 130), (216, 43, 206), (47, 172, 72), (198, 181, 0), (137, 99, 246),
+                   (22, 160, 10), (23, 240, 252))
 
 # matplotlib's `jet` (matplotlib/_cm.py, public since 0.x): piecewise-linear through these (x, y) nodes per channel
 _JET_NODES = (
@@ -55,15 +71,37 @@ def _jet_on(dev: torch.device) -> torch.Tensor:
     return t
 
 
-def _device_f32(name: str, what: str, t) -> None:
+def _device_tensor(name: str, what: str, t, dtype: torch.dtype, kind: str) -> None:
     if not torch.is_tensor(t):
         raise TypeError(f"{name}: {what} must be a tensor")
     if not t.is_cuda:
         raise RuntimeError(f"{name} runs on the HIP device only (coponerf_amd has no non-HIP compute path)")
-    if t.dtype != torch.float32:
-        raise ValueError(f"{name}: fp32 tensors only, {what} is {t.dtype}")
+    if t.dtype != dtype:
+        raise ValueError(f"{name}: {kind} tensors only, {what} is {t.dtype}")
     if not t.is_contiguous():
         raise ValueError(f"{name}: {what} must be contiguous")
+
+
+def _device_f32(name: str, what: str, t) -> None:
+    _device_tensor(name, what, t, torch.float32, "fp32")
+
+
+def default_points(S: int) -> Tuple[Tuple[int, int], ...]:
+    """The reference's nine points (x, y) for images of side S, in its order."""
+    at = (S // 4, S // 2, 3 * S // 4)
+    return tuple((x, y) for x in at for y in at)
+
+
+_SETTINGS_DEVICE: Dict[tuple, torch.Tensor] = {}
+
+
+def _settings_on(dev: torch.device, values, dtype: torch.dtype) -> torch.Tensor:
+    """A small table of settings (points, colours) on the device: uploaded once per value from pinned memory, asynchronously."""
+    key = (dev, dtype, tuple(tuple(v) for v in values))
+    t = _SETTINGS_DEVICE.get(key)
+    if t is None:
+        t = _SETTINGS_DEVICE[key] = torch.tensor(key[2], dtype=dtype).pin_memory().to(dev, non_blocking=True)
+    return t
 
 
 # ---------------------------------------------------------------------------------------------------------- the kernels
@@ -86,11 +124,13 @@ def attention_entropy(at_wt: torch.Tensor, nan_to_zero: bool = False) -> torch.T
     return out[0]
 
 
-def flow_panels(context_rgb: torch.Tensor, flow: Sequence[torch.Tensor]) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+def flow_panels(context_rgb: torch.Tensor, flow: Sequence[torch.Tensor],
+                contour: bool = False) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
     """(warped (2, B, S, S, 3) fp32 in [0, 255], mask (2, B, S, S) uint8, overlay (2, B, S, S, 3) uint8) of
     summaries.py:163-207: entry d warps view 1 - d of context_rgb (B, 2, S, S, 3) by flow[d] (B, 2, h, h), upsampled
     bilinearly and scaled by S / h; the mask is the cycle check (norm <= 10) times get_gt_correspondence_mask; the overlay
-    is overlay_semantic_mask(color=[255, 102, 51], alpha=0.5) without its contour.  Any square S >= h."""
+    is overlay_semantic_mask(color=[255, 102, 51], alpha=0.5), with its contour (mask_contour) when contour=True.  Any
+    square S >= h."""
     f0, f1 = flow[0], flow[1]
     for what, t in (("context_rgb", context_rgb), ("flow[0]", f0), ("flow[1]", f1)):
         _device_f32("flow_panels", what, t)
@@ -111,7 +151,113 @@ def flow_panels(context_rgb: torch.Tensor, flow: Sequence[torch.Tensor]) -> Tupl
     with torch.cuda.device(dev):
         _hip.call("cpn_flow_panels", context_rgb.data_ptr(), f0.data_ptr(), f1.data_ptr(), B, S, h, warped.data_ptr(),
                   mask.data_ptr(), overlay.data_ptr(), _hip.stream_handle())
+    if contour:
+        overlay = mask_contour(overlay, mask)
     return warped, mask, overlay
+
+
+def mask_contour(overlay: torch.Tensor, mask: torch.Tensor) -> torch.Tensor:
+    """A new overlay (..., S, S, 3) uint8 with the 1-pixel contour of summaries.py:65-71: exactly (255, 102, 51) on every
+    invalid pixel (mask (..., S, S) uint8 == 0) with a valid or outside-the-image 4-neighbour - the border points that
+    cv2.findContours follows and drawContours(thickness=1) repaints - and the overlay's value elsewhere.  One launch."""
+    _device_tensor("mask_contour", "overlay", overlay, torch.uint8, "uint8")
+    _device_tensor("mask_contour", "mask", mask, torch.uint8, "uint8")
+    if (overlay.dim() < 3 or overlay.shape[-1] != 3 or overlay.shape[-2] != overlay.shape[-3] or mask.shape != overlay.shape[:-1]
+            or overlay.numel() == 0):
+        raise ValueError(f"mask_contour: overlay (..., S, S, 3) and mask (..., S, S), got {tuple(overlay.shape)} and {tuple(mask.shape)}")
+    if mask.device != overlay.device:
+        raise ValueError("mask_contour: overlay and mask are on different devices")
+    S = int(overlay.shape[-2])
+    out = torch.empty_like(overlay)
+    with torch.cuda.device(overlay.device):
+        _hip.call("cpn_mask_contour", overlay.data_ptr(), mask.data_ptr(), mask.numel() // (S * S), S, out.data_ptr(),
+                  _hip.stream_handle())
+    return out
+
+
+def _check_geometry(name: str, intrinsics, rel_pose, gt_rel_pose) -> int:
+    for what, t in (("intrinsics", intrinsics), ("rel_pose", rel_pose), ("gt_rel_pose", gt_rel_pose)):
+        _device_f32(name, what, t)
+    if intrinsics.dim() != 4 or tuple(intrinsics.shape[1:]) != (2, 4, 4) or intrinsics.shape[0] < 1:
+        raise ValueError(f"{name}: intrinsics must be (B, 2, 4, 4), got {tuple(intrinsics.shape)}")
+    B = int(intrinsics.shape[0])
+    if tuple(rel_pose.shape) != (B, 4, 4) or tuple(gt_rel_pose.shape) != (B, 4, 4):
+        raise ValueError(f"{name}: rel_pose and gt_rel_pose must be (B, 4, 4) for B = {B}, got {tuple(rel_pose.shape)} and "
+                         f"{tuple(gt_rel_pose.shape)}")
+    if rel_pose.device != intrinsics.device or gt_rel_pose.device != intrinsics.device:
+        raise ValueError(f"{name}: intrinsics and poses are on different devices")
+    return B
+
+
+def _check_points(name: str, points, dev: torch.device) -> int:
+    _device_tensor(name, "points", points, torch.int32, "int32")
+    if points.dim() != 2 or points.shape[1] != 2 or points.shape[0] < 1:
+        raise ValueError(f"{name}: points must be (P, 2) with P >= 1, got {tuple(points.shape)}")
+    if points.device != dev:
+        raise ValueError(f"{name}: points are on another device")
+    return int(points.shape[0])
+
+
+def epipolar_lines(intrinsics: torch.Tensor, rel_pose: torch.Tensor, gt_rel_pose: torch.Tensor, points: torch.Tensor,
+                   width: int) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """(F (2, B, 3, 3) float64, lines (2, B, P, 3) float64, ends (2, B, P, 4) int32, valid (2, B, P) uint8); entry 0 under
+    rel_pose, entry 1 under gt_rel_pose.  two_view_geometry (inspect_epipolar_geometry.py:13-43) in float64 from the fp32
+    inputs: F = inv(K_view0[:3,:3]).T [t]x R inv(K_view1[:3,:3]) of intrinsics (B, 2, 4, 4), each inverse rounded to fp32 as
+    np.linalg.inv returns it for an fp32 matrix; line p = F (x, y, 1) of points
+    (P, 2) int32 in view 1; ends = (0, int(-c / b), width, int(-(c + a width) / b)) as drawpointslines forms them; valid is 0
+    where b == 0, a value is not finite or an end point does not fit an int32.  One launch."""
+    B = _check_geometry("epipolar_lines", intrinsics, rel_pose, gt_rel_pose)
+    P = _check_points("epipolar_lines", points, intrinsics.device)
+    width = int(width)
+    if width < 1:
+        raise ValueError(f"epipolar_lines: width must be >= 1, got {width}")
+    dev = intrinsics.device
+    Fm = torch.empty(2, B, 3, 3, dtype=torch.float64, device=dev)
+    lines = torch.empty(2, B, P, 3, dtype=torch.float64, device=dev)
+    ends = torch.empty(2, B, P, 4, dtype=torch.int32, device=dev)
+    valid = torch.empty(2, B, P, dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        _hip.call("cpn_epipolar_lines", intrinsics.data_ptr(), rel_pose.data_ptr(), gt_rel_pose.data_ptr(), points.data_ptr(), B, P,
+                  width, Fm.data_ptr(), lines.data_ptr(), ends.data_ptr(), valid.data_ptr(), _hip.stream_handle())
+    return Fm, lines, ends, valid
+
+
+def epipolar_panels(context_rgb: torch.Tensor, intrinsics: torch.Tensor, rel_pose: torch.Tensor, gt_rel_pose: torch.Tensor,
+                    points: Optional[torch.Tensor] = None, colors: Optional[torch.Tensor] = None, radius: int = 5,
+                    thickness: int = 10) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(pred, gt), each (B, S, 2 S, 3) fp32 in [0, 255]: inspect() of inspect_epipolar_geometry.py:75-120 for context_rgb
+    (B, 2, S, S, 3).  Left half: view 1 with a disc of `radius` at every point; right half: view 0 with the points' epipolar
+    lines of `thickness`, blended 0.4 colour + 0.6 image; under rel_pose and under gt_rel_pose.  points (P, 2) int32 (x, y)
+    and colors (P, 3) fp32 on the device; None takes the reference's nine points and colours.  2 launches, no host read."""
+    name = "epipolar_panels"
+    _device_f32(name, "context_rgb", context_rgb)
+    if context_rgb.dim() != 5 or context_rgb.shape[1] != 2 or context_rgb.shape[4] != 3 or context_rgb.shape[2] != context_rgb.shape[3]:
+        raise ValueError(f"{name}: context_rgb must be (B, 2, S, S, 3), got {tuple(context_rgb.shape)}")
+    dev, S = context_rgb.device, int(context_rgb.shape[2])
+    B = _check_geometry(name, intrinsics, rel_pose, gt_rel_pose)
+    if B != context_rgb.shape[0] or S < 1:
+        raise ValueError(f"{name}: {B} intrinsics for context_rgb of shape {tuple(context_rgb.shape)}")
+    if intrinsics.device != dev:
+        raise ValueError(f"{name}: images and intrinsics are on different devices")
+    if points is None:
+        points = _settings_on(dev, default_points(S), torch.int32)
+    P = _check_points(name, points, dev)
+    if colors is None:
+        if P != len(EPIPOLAR_COLORS):
+            raise ValueError(f"{name}: pass colors (P, 3) for {P} points")
+        colors = _settings_on(dev, EPIPOLAR_COLORS, torch.float32)
+    _device_f32(name, "colors", colors)
+    if tuple(colors.shape) != (P, 3) or colors.device != dev:
+        raise ValueError(f"{name}: colors must be ({P}, 3) on the images' device, got {tuple(colors.shape)}")
+    radius, thickness = int(radius), int(thickness)
+    if not (0 <= radius <= 255 and 1 <= thickness <= 255):
+        raise ValueError(f"{name}: need 0 <= radius <= 255 and 1 <= thickness <= 255, got {radius} and {thickness}")
+    _, _, ends, valid = epipolar_lines(intrinsics, rel_pose, gt_rel_pose, points, S)
+    out = torch.empty(2, B, S, 2 * S, 3, dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        _hip.call("cpn_epipolar_panels", context_rgb.data_ptr(), points.data_ptr(), colors.data_ptr(), ends.data_ptr(),
+                  valid.data_ptr(), B, S, P, radius, thickness, out.data_ptr(), _hip.stream_handle())
+    return out[0], out[1]
 
 
 def depth_colors(depth_ray: torch.Tensor) -> torch.Tensor:
@@ -174,10 +320,13 @@ def _image_shape(rgb: torch.Tensor, image_shape: Optional[Sequence[int]]) -> Tup
 
 
 @torch.no_grad()
-def image_summaries(model_input: Dict, model_output: Dict, image_shape: Optional[Sequence[int]] = None) -> Summary:
+def image_summaries(model_input: Dict, model_output: Dict, image_shape: Optional[Sequence[int]] = None, epipolar: bool = False,
+                    contour: bool = False) -> Summary:
     """summaries.py:106-235 for one batch, without its writer: model_output is the joined dict of `forward(val=True)` /
     `render_images` ('rgb', 'depth_ray', 'flow', 'rel_pose', 'gt_rel_pose', optionally 'at_wt'), model_input the loader's dict
-    on the device.  image_shape=(H, W) of the query image; None takes it as square.  Enqueues device work only."""
+    on the device.  image_shape=(H, W) of the query image; None takes it as square.  epipolar=True adds EPIPOLAR_TAGS after
+    IMAGE_TAGS (it reads model_input['context']['intrinsics']); contour=True draws the contour on the two masked images.
+    Enqueues device work only."""
     rgb = model_output["rgb"]
     H, W = _image_shape(rgb, image_shape)
     images: Dict[str, torch.Tensor] = {}
@@ -195,17 +344,22 @@ def image_summaries(model_input: Dict, model_output: Dict, image_shape: Optional
     images["query_images"] = make_grid(query)
 
     flow = model_output["flow"]
-    warped, _, overlay = flow_panels(ctx.contiguous(), (flow[0].contiguous(), flow[1].contiguous()))
+    warped, _, overlay = flow_panels(ctx.contiguous(), (flow[0].contiguous(), flow[1].contiguous()), contour=contour)
     view255 = (ctx + 1) * 127.5
     for d, suffix in ((0, ""), (1, "_flip")):
         panel = torch.cat((view255[:, 1 - d], warped[d], view255[:, d]), dim=-2)          # [source | warped | target]
         images["warped_img" + suffix] = make_grid(panel.permute(0, 3, 1, 2))
         images["masked_warped_img" + suffix] = make_grid(overlay[d].float().permute(0, 3, 1, 2))
+    rel, gt_rel = model_output["rel_pose"], model_output["gt_rel_pose"]
+    if epipolar:
+        pred, gt = epipolar_panels(ctx.contiguous(), model_input["context"]["intrinsics"].contiguous(), rel.contiguous(),
+                                   gt_rel.contiguous())
+        images["epipolar_GT"] = make_grid(gt.permute(0, 3, 1, 2))
+        images["epipolar_pred"] = make_grid(pred.permute(0, 3, 1, 2))
 
     S, h = int(ctx.shape[2]), int(flow[0].shape[2])
     scalars["flow_mean"] = (F.interpolate(flow[0][:1, :1], S, mode="bilinear") * (S / h)).mean()     # image 0, x component
     scalars["out_min"], scalars["out_max"] = predictions.min(), predictions.max()
-    rel, gt_rel = model_output["rel_pose"], model_output["gt_rel_pose"]
     m = torch.bmm(rel[:, :3, :3], gt_rel[:, :3, :3].transpose(1, 2))
     theta = torch.acos(((m[:, 0, 0] + m[:, 1, 1] + m[:, 2, 2] - 1) / 2).clamp(-1.0, 1.0))
     degrees = theta / np.pi * 180
@@ -230,14 +384,15 @@ class SummaryLog:
 
     `add` packs every image and scalar into ONE flat pinned buffer with one asynchronous copy and records an event; the
     entry is written once `lag` newer ones exist (its copy finished long ago) or at `flush`.  `host_reads` counts one per
-    written entry."""
+    written entry.  `epipolar` and `contour` are image_summaries' switches."""
 
-    def __init__(self, writer, prefix: str = "", lag: int = 1):
+    def __init__(self, writer, prefix: str = "", lag: int = 1, epipolar: bool = False, contour: bool = False):
         if lag < 0:
             raise ValueError(f"SummaryLog: lag must be >= 0, got {lag}")
         self.writer = writer
         self.prefix = prefix
         self.lag = int(lag)
+        self.epipolar, self.contour = bool(epipolar), bool(contour)
         self.host_reads = 0
         self._pending: deque = deque()
         self._free: Dict[int, List[torch.Tensor]] = {}
@@ -251,7 +406,7 @@ class SummaryLog:
 
     @torch.no_grad()
     def add(self, model_input: Dict, model_output: Dict, step: int, image_shape: Optional[Sequence[int]] = None) -> None:
-        summary = image_summaries(model_input, model_output, image_shape)
+        summary = image_summaries(model_input, model_output, image_shape, epipolar=self.epipolar, contour=self.contour)
         while len(self._pending) > max(self.lag - 1, 0):
             self._write(self._pending.popleft())
         layout = [(tag, True, tuple(t.shape)) for tag, t in summary.images.items()]

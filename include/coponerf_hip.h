@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define CPN_ABI_VERSION 12   /* cpn_attend_units (round 7), cpn_ssim_warp* (round 8), cpn_image_metrics* (round 9), summaries.hip (round 10), lpips.hip (round 11) and novel_views.hip (round 12) are additive - symbols added, none altered: the version stays */
+#define CPN_ABI_VERSION 12   /* cpn_attend_units (round 7), cpn_ssim_warp* (round 8), cpn_image_metrics* (round 9), summaries.hip (round 10), lpips.hip (round 11), novel_views.hip (round 12) and epipolar.hip (round 13) are additive - symbols added, none altered: the version stays */
 
 #define CPN_E_ARG   (-1)   /* bad argument (null pointer, size, alignment) */
 #define CPN_E_SHAPE (-2)   /* shape not supported by the compiled tiles    */
@@ -688,7 +688,7 @@ int cpn_image_metrics_scratch(int N, int H, int W);
 int cpn_image_metrics(const float* pred, const float* target, int N, int H, int W, float* partial, float* out, void* stream);
 
 /* ==== the training / validation log on the device: flow panels, depth colours, attention entropy (round 10) ==============
- * cpn_flow_panels replaces summary/summaries.py:163-207 (and :42-63, :74-100 inside it) minus the OpenCV contour: both
+ * cpn_flow_panels replaces summary/summaries.py:163-207 (and :42-63, :74-100 inside it) minus the OpenCV contour (cpn_mask_contour, round 13): both
  *   F.interpolate(mode="bilinear") * (S / h), both cycle checks torch.norm(flow + warp(flow2, flow)).le(10), both
  *   get_gt_correspondence_mask, the per-image loop of warp((rgb + 1) * 127.5, flow) -> .cpu().numpy() ->
  *   overlay_semantic_mask(color=[255, 102, 51], alpha=0.5), for both directions and all B in ONE launch.
@@ -760,6 +760,39 @@ int cpn_fit_images_u8(const uint8_t* img, int N, int B, int Hi, int Wi, int size
                       long long batch_stride, long long view_stride, void* stream);
 int cpn_camera_path(const float* rel_pose, const double* t, int B, int K, double sway, double turns, float* out, void* stream);
 int cpn_pack_frames(const float* rgb, const float* depth, const float* table, int B, int h, int w, uint8_t* out, void* stream);
+
+/* ==== the validation log's drawings: epipolar panels and the mask contour (round 13) =====================================
+ * The two OpenCV pieces of summary/summaries.py:img_summaries, as kernels.  The symbols are additive: the ABI version stays.
+ * cpn_epipolar_lines replaces two_view_geometry (summary/inspect_epipolar_geometry.py:13-43), the epiline of every point
+ *   and the end points of drawpointslines (:54-55), in float64 from the fp32 inputs as numpy forms them, in ONE launch.
+ *   intrinsics (B, 2, 4, 4) fp32, rel_pose and gt_rel_pose (B, 4, 4) fp32, points (P, 2) int32 (x, y).  Kind k = 0 is the
+ *   estimated pose, k = 1 the true one.  F (2, B, 3, 3) f64 = inv(K_view0[:3,:3])^T [t]x R inv(K_view1[:3,:3]) (inverses by
+ *   cofactors in float64, then ROUNDED TO fp32: what np.linalg.inv returns for an fp32 matrix, and so what the reference
+ *   multiplies; products left to right, terms in index order); lines (2, B, P, 3) f64 = F (x, y, 1) = (a, b, c), not scaled to
+ *   a^2 + b^2 = 1 as cv2.computeCorrespondEpilines does (the end points do not depend on the scale); ends (2, B, P, 4) int32
+ *   = (0, int(-c / b), W, int(-(c + a W) / b)), int() truncating toward zero; valid (2, B, P) bytes: 0 where b == 0, where a
+ *   value is not finite or where an end point does not fit an int32 (its ends are written as 0).  The reference raises there
+ *   and drops both images of the whole batch; here that one line is left out and everything else is drawn.
+ * cpn_epipolar_panels replaces drawpointslines and inspect (:46-57, :95-112): out (2, B, S, 2 S, 3) fp32 in [0, 255], one
+ *   thread per output pixel, ONE launch.  rgb (B, 2, S, S, 3) fp32 in [-1, 1].  Left half: (view 1 + 1) * 127.5 with the P
+ *   discs (colour unblended); right half: (view 0 + 1) * 127.5, and 0.4 colour + 0.6 original on a pixel of a valid line
+ *   (cv2.addWeighted, :105-106); every other pixel keeps its original value.  Later points and lines overwrite earlier ones.
+ *   colors (P, 3) fp32; ends / valid as cpn_epipolar_lines writes them for W = S.  Coverage is this library's definition,
+ *   not checked against OpenCV's rasteriser: a pixel lies on the disc of centre c iff (x - cx)^2 + (y - cy)^2 <= radius^2 in
+ *   integers, and on a line iff its distance to the SEGMENT between the two integer end points is <= thickness / 2 (a
+ *   capsule), decided without a square root: d = p1 - p0, w = p - p0, s = w.d; s <= 0: 4 |w|^2 <= T^2; s >= |d|^2:
+ *   4 |p - p1|^2 <= T^2; otherwise 4 (w x d)^2 <= T^2 |d|^2.  Exact in int64 when both |y| <= 2^15 and S <= 4096; beyond
+ *   that, up to the int32 range, the same expressions in float64.  0 <= radius, 1 <= thickness, both <= 255.
+ * cpn_mask_contour replaces the contour of overlay_semantic_mask (summaries.py:65-71: cv2.findContours / drawContours,
+ *   thickness 1): overlay (N, S, S, 3) bytes, mask (N, S, S) bytes (non-zero = valid), out (N, S, S, 3) bytes: (255, 102, 51)
+ *   on every invalid pixel with a valid or outside-the-image 4-neighbour (the border points of 8-connected border following),
+ *   the overlay's value elsewhere.  ONE launch for all N.
+ * No atomics in any of them: bit-reproducible, and an image's result does not depend on the batch around it.                 */
+int cpn_epipolar_lines(const float* intrinsics, const float* rel_pose, const float* gt_rel_pose, const int* points, int B, int P,
+                       int W, double* F, double* lines, int* ends, uint8_t* valid, void* stream);
+int cpn_epipolar_panels(const float* rgb, const int* points, const float* colors, const int* ends, const uint8_t* valid, int B,
+                        int S, int P, int radius, int thickness, float* out, void* stream);
+int cpn_mask_contour(const uint8_t* overlay, const uint8_t* mask, int N, int S, uint8_t* out, void* stream);
 
 #ifdef __cplusplus
 }
