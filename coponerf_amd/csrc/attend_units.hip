@@ -190,7 +190,7 @@ __global__ __launch_bounds__(AU_THREADS, 3) void attend_units_kernel(UnitArgs ar
             wt[row] = w;
             if (at_wt && half == 0) {
                 const int v = row / S, s = row - v * S;
-                at_wt[(((size_t)(b * V + v)) * R + r) * S + s] = w;
+                at_wt[sample_index(b, V, v, R, r, S, s)] = w;
             }
         }
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");      // this wave's weights are in LDS before any lane reads another's

@@ -264,17 +264,41 @@ namespace {
 
 constexpr int HC = 1664;
 
+// What a precision supplies to attend_hidden_bwd_ray, the ONE body of cpn_attend_hidden_bwd and cpn_attend_hidden_bwd_f32:
+//   q_t, qvec, elem   qa / qb / dqa / dqb / dqb_acc: halves, 8 per thread, or floats, 4 per thread
+//   PARTS             an 8-channel chunk of a hidden row is one half8 (hid, row stride 1664 halves), or the (hi, lo) pair
+//                     cpn_encode_hidden_f32 stored, 1664 halves apart in an hs row [hi_own | hi_other | lo_own | lo_other] of
+//                     3328; its value is hi + lo rounded to fp32
+//   DQB_SUM_ALWAYS    without dqb_acc the f32 kernel still ADDS its product to (+0) (a product of -0 leaves as +0); the fp16
+//                     kernel stores the product
+struct BwdF16 {
+    using q_t = __half; using qvec = half8; using elem = _Float16;
+    static constexpr int PARTS = 1;
+    static constexpr bool DQB_SUM_ALWAYS = false;
+};
+struct BwdF32 {
+    using q_t = float; using qvec = f32x4; using elem = float;
+    static constexpr int PARTS = 2;
+    static constexpr bool DQB_SUM_ALWAYS = true;
+};
 
 // One workgroup per ray.  T = V*S rows.
 //   dw[row]   = <hid[row], dhbar> + dw_ext[row]
 //   dl[row]   = w[row] * (dw[row] - sum_r w[r] dw[r]) / 11.31
-//   dqa[row]  = dl[row] * qb[row] ;  dqb[row] = dl[row] * qa[row]
-//   dhid[row] = w[row] * dhbar
-__global__ __launch_bounds__(256) void attend_hidden_bwd_kernel(
-    const __half* __restrict__ qa, const __half* __restrict__ qb, const __half* __restrict__ hid,
+//   dqa[row]  = dl[row] * qb[row] ;  dqb[row] = dl[row] * qa[row] (+ dqb_acc[row])
+//   dhid[row] = w[row] * dhbar                                      (fp16 only, and only if asked for)
+// Everything is fp32 from the loads on.  HBM-bound: a hidden row is read once.
+// Rounding, written out as the two kernels have always been compiled: the row dot is ONE chain of fused multiply-adds from 0
+// over the lane's 32 channels in (k, e) order; sum_r w dw fuses each product; dqa is a rounded product; dqb = fma(dl, qa, dqb_acc)
+// (then rounded to fp16 where the output is fp16).
+template <class P>
+__device__ __forceinline__ void attend_hidden_bwd_ray(
+    const typename P::q_t* __restrict__ qa, const typename P::q_t* __restrict__ qb, const __half* __restrict__ hid,
     const float* __restrict__ at_wt, const float* __restrict__ dhbar, const float* __restrict__ dw_ext, int V, int R,
-    int S, int ray0, __half* __restrict__ dqa, __half* __restrict__ dqb, __half* __restrict__ dhid,
-    const __half* __restrict__ dqb_acc) {
+    int S, int ray0, typename P::q_t* __restrict__ dqa, typename P::q_t* __restrict__ dqb, __half* __restrict__ dhid,
+    const typename P::q_t* __restrict__ dqb_acc) {
+    using qvec = typename P::qvec;
+    using elem = typename P::elem;
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     float* dh = reinterpret_cast<float*>(smem_raw);          // HC floats: dhbar of this ray
     float* wts = dh + HC;                                    // T
@@ -290,31 +314,39 @@ __global__ __launch_bounds__(256) void attend_hidden_bwd_kernel(
     for (int c = tid; c < HC; c += 256) dh[c] = dhbar[(size_t)lray * HC + c];
     for (int row = tid; row < T; row += 256) {
         const int v = row / S, s = row - v * S;
-        wts[row] = at_wt[(((size_t)(b * V + v)) * R + r) * S + s];
+        wts[row] = at_wt[sample_index(b, V, v, R, r, S, s)];
     }
     __syncthreads();
     // dw[row] = <hid[row, :], dhbar>: one wave per row, 16-byte loads (a lane owns the 8-channel chunks lane, lane + 64, ...
     // of the 208 in a row and keeps their dhbar values in registers), two rows in flight per wave.  (4-byte loads, one
     // row at a time and dhbar re-read from LDS per element ran this pass at 3 TB/s: 2.4 ms per call.)
     constexpr int NCH = HC / 8;                              // 208 chunks per row
+    constexpr int HID_LD = P::PARTS * HC;                    // row stride (halves)
     float dreg[4][8];
 #pragma unroll
     for (int k = 0; k < 4; ++k)
 #pragma unroll
         for (int e = 0; e < 8; ++e) dreg[k][e] = (lane + 64 * k < NCH) ? dh[(lane + 64 * k) * 8 + e] : 0.0f;
-    auto row_dot = [&](const half8 (&h)[4]) {
+    auto load_row = [&](int row, half8 (&h)[4][P::PARTS]) {
+        const __half* hp = hid + (row0 + min(row, T - 1)) * HID_LD;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {                        // chunk 208.. of the last group: re-read chunk lane (weight 0)
+            const int ch = (lane + 64 * k < NCH) ? lane + 64 * k : lane;
+#pragma unroll
+            for (int p = 0; p < P::PARTS; ++p) h[k][p] = __builtin_nontemporal_load(reinterpret_cast<const half8*>(hp + p * HC + ch * 8));
+        }
+    };
+    auto row_dot = [&](const half8 (&h)[4][P::PARTS]) {
         float acc = 0.f;
 #pragma unroll
         for (int k = 0; k < 4; ++k)
 #pragma unroll
-            for (int e = 0; e < 8; ++e) acc += (float)h[k][e] * dreg[k][e];
+            for (int e = 0; e < 8; ++e) {
+                float x = (float)h[k][0][e];
+                if constexpr (P::PARTS == 2) x += (float)h[k][1][e];
+                acc = __builtin_fmaf(dreg[k][e], x, acc);
+            }
         return wave_sum(acc);
-    };
-    auto load_row = [&](int row, half8 (&h)[4]) {
-        const __half* hp = hid + (row0 + min(row, T - 1)) * HC;
-#pragma unroll
-        for (int k = 0; k < 4; ++k)                          // chunk 208.. of the last group: re-read chunk lane (weight 0)
-            h[k] = __builtin_nontemporal_load(reinterpret_cast<const half8*>(hp + ((lane + 64 * k < NCH) ? lane + 64 * k : lane) * 8));
     };
     float part = 0.f;
     auto finish = [&](int row, float acc) {
@@ -322,14 +354,14 @@ __global__ __launch_bounds__(256) void attend_hidden_bwd_kernel(
             float dwv = acc;
             if (dw_ext) {
                 const int v = row / S, s = row - v * S;
-                dwv += dw_ext[(((size_t)(b * V + v)) * R + r) * S + s];
+                dwv += dw_ext[sample_index(b, V, v, R, r, S, s)];
             }
             dl[row] = dwv;
-            part += wts[row] * dwv;
+            part = __builtin_fmaf(wts[row], dwv, part);
         }
     };
     for (int row = wave; row < T; row += 8) {
-        half8 ha[4], hb[4];
+        half8 ha[4][P::PARTS], hb[4][P::PARTS];
         load_row(row, ha);
         load_row(row + 4, hb);
         finish(row, row_dot(ha));
@@ -340,29 +372,30 @@ __global__ __launch_bounds__(256) void attend_hidden_bwd_kernel(
     const float dot = (red[0] + red[1]) + (red[2] + red[3]);
     for (int row = tid; row < T; row += 256) dl[row] = wts[row] * (dl[row] - dot) / 11.31f;
     __syncthreads();
-    // dqa / dqb: thread = (row, 8-channel group)
-    for (int i = tid; i < T * 16; i += 256) {
-        const int row = i >> 4, g = i & 15;
-        const half8 a = *reinterpret_cast<const half8*>(qa + (row0 + row) * 128 + g * 8);
-        const half8 bq = *reinterpret_cast<const half8*>(qb + (row0 + row) * 128 + g * 8);
+    // dqa / dqb: thread = (row, group of QW channels)
+    constexpr int QW = sizeof(qvec) / sizeof(elem), G = 128 / QW;
+    for (int i = tid; i < T * G; i += 256) {
+        const int row = i / G, g = i % G;
+        const size_t off = (row0 + row) * 128 + g * QW;
+        const qvec a = *reinterpret_cast<const qvec*>(qa + off);
+        const qvec bq = *reinterpret_cast<const qvec*>(qb + off);
         const float d = dl[row];
-        half8 oa, ob;
-        if (dqb_acc) {                      // qb is shared with another attention round: its gradient is summed here
-            const half8 pq = *reinterpret_cast<const half8*>(dqb_acc + (row0 + row) * 128 + g * 8);
+        qvec oa, ob;
+        {
+#pragma clang fp contract(off)
 #pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                oa[e] = (_Float16)(d * (float)bq[e]);
-                ob[e] = (_Float16)((float)pq[e] + d * (float)a[e]);
-            }
-        } else {
+            for (int e = 0; e < QW; ++e) oa[e] = (elem)(d * (float)bq[e]);
+            if (dqb_acc || P::DQB_SUM_ALWAYS) { // qb is shared with another attention round: its gradient is summed here
+                const qvec pq = dqb_acc ? *reinterpret_cast<const qvec*>(dqb_acc + off) : qvec{};
 #pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                oa[e] = (_Float16)(d * (float)bq[e]);
-                ob[e] = (_Float16)(d * (float)a[e]);
+                for (int e = 0; e < QW; ++e) ob[e] = (elem)__builtin_fmaf(d, (float)a[e], (float)pq[e]);
+            } else {
+#pragma unroll
+                for (int e = 0; e < QW; ++e) ob[e] = (elem)(d * (float)a[e]);
             }
         }
-        *reinterpret_cast<half8*>(dqa + (row0 + row) * 128 + g * 8) = oa;
-        *reinterpret_cast<half8*>(dqb + (row0 + row) * 128 + g * 8) = ob;
+        *reinterpret_cast<qvec*>(dqa + off) = oa;
+        *reinterpret_cast<qvec*>(dqb + off) = ob;
     }
     // dhid = w[row] * dhbar : thread = 8 channels, rows streamed (skipped when the caller combines the hidden-activation
     // gradients of all consumers in cpn_hid_grad_combine instead of materialising one 7 GB tensor per consumer)
@@ -380,99 +413,20 @@ __global__ __launch_bounds__(256) void attend_hidden_bwd_kernel(
     }
 }
 
-// The same gradient for the reference-arithmetic training forward (RenderEngine.train_precision = "f32"): fp32 qa / qb /
-// dqa / dqb / dqb_acc and the hidden activations as the (hi, lo) fp16 pairs cpn_encode_hidden_f32 stored, hs row =
-// [hi_own | hi_other | lo_own | lo_other] (3328 halves).  Everything is fp32 from the loads on:
-//   dw[row] = <hi[row] + lo[row], dhbar> + dw_ext[row],  dl[row] = w[row] * (dw[row] - sum_r w[r] dw[r]) / 11.31,
-//   dqa[row] = dl[row] * qb[row],  dqb[row] = dl[row] * qa[row] (+ dqb_acc[row])
-// HBM-bound: the 6.5 KB hs row is read once (one wave per row, the hi and lo chunks of a lane side by side).
+__global__ __launch_bounds__(256) void attend_hidden_bwd_kernel(
+    const __half* __restrict__ qa, const __half* __restrict__ qb, const __half* __restrict__ hid,
+    const float* __restrict__ at_wt, const float* __restrict__ dhbar, const float* __restrict__ dw_ext, int V, int R,
+    int S, int ray0, __half* __restrict__ dqa, __half* __restrict__ dqb, __half* __restrict__ dhid,
+    const __half* __restrict__ dqb_acc) {
+    attend_hidden_bwd_ray<BwdF16>(qa, qb, hid, at_wt, dhbar, dw_ext, V, R, S, ray0, dqa, dqb, dhid, dqb_acc);
+}
+
+// for the reference-arithmetic training forward (RenderEngine.train_precision = "f32"); dhid cannot be asked for
 __global__ __launch_bounds__(256) void attend_hidden_bwd_f32_kernel(
     const float* __restrict__ qa, const float* __restrict__ qb, const __half* __restrict__ hs,
     const float* __restrict__ at_wt, const float* __restrict__ dhbar, const float* __restrict__ dw_ext, int V, int R,
     int S, int ray0, float* __restrict__ dqa, float* __restrict__ dqb, const float* __restrict__ dqb_acc) {
-    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-    float* dh = reinterpret_cast<float*>(smem_raw);          // HC floats: dhbar of this ray
-    float* wts = dh + HC;                                    // T
-    float* dl = wts + V * S;                                 // T
-    float* red = dl + V * S;                                 // 4
-    const int T = V * S;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const unsigned lray = blockIdx.x;
-    const size_t row0 = (size_t)lray * T;
-    const unsigned ray = (unsigned)ray0 + lray;
-    const int b = (int)(ray / (unsigned)R), r = (int)(ray % (unsigned)R);
-
-    for (int c = tid; c < HC; c += 256) dh[c] = dhbar[(size_t)lray * HC + c];
-    for (int row = tid; row < T; row += 256) {
-        const int v = row / S, s = row - v * S;
-        wts[row] = at_wt[(((size_t)(b * V + v)) * R + r) * S + s];
-    }
-    __syncthreads();
-    constexpr int NCH = HC / 8;                              // 208 chunks per half row
-    constexpr int HS_LD = 2 * HC;                            // hs row stride (halves)
-    float dreg[4][8];
-#pragma unroll
-    for (int k = 0; k < 4; ++k)
-#pragma unroll
-        for (int e = 0; e < 8; ++e) dreg[k][e] = (lane + 64 * k < NCH) ? dh[(lane + 64 * k) * 8 + e] : 0.0f;
-    auto load_row = [&](int row, half8 (&h)[4], half8 (&l)[4]) {
-        const __half* hp = hs + (row0 + min(row, T - 1)) * HS_LD;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {                        // chunk 208.. of the last group: re-read chunk lane (weight 0)
-            const int ch = (lane + 64 * k < NCH) ? lane + 64 * k : lane;
-            h[k] = __builtin_nontemporal_load(reinterpret_cast<const half8*>(hp + ch * 8));
-            l[k] = __builtin_nontemporal_load(reinterpret_cast<const half8*>(hp + HC + ch * 8));
-        }
-    };
-    auto row_dot = [&](const half8 (&h)[4], const half8 (&l)[4]) {
-        float acc = 0.f;
-#pragma unroll
-        for (int k = 0; k < 4; ++k)
-#pragma unroll
-            for (int e = 0; e < 8; ++e) acc += ((float)h[k][e] + (float)l[k][e]) * dreg[k][e];
-        return wave_sum(acc);
-    };
-    float part = 0.f;
-    auto finish = [&](int row, float acc) {
-        if (lane == 0 && row < T) {
-            float dwv = acc;
-            if (dw_ext) {
-                const int v = row / S, s = row - v * S;
-                dwv += dw_ext[(((size_t)(b * V + v)) * R + r) * S + s];
-            }
-            dl[row] = dwv;
-            part += wts[row] * dwv;
-        }
-    };
-    for (int row = wave; row < T; row += 8) {
-        half8 ha[4], la[4], hb[4], lb[4];
-        load_row(row, ha, la);
-        load_row(row + 4, hb, lb);
-        finish(row, row_dot(ha, la));
-        finish(row + 4, row_dot(hb, lb));
-    }
-    if (lane == 0) red[wave] = part;
-    __syncthreads();
-    const float dot = (red[0] + red[1]) + (red[2] + red[3]);
-    for (int row = tid; row < T; row += 256) dl[row] = wts[row] * (dl[row] - dot) / 11.31f;
-    __syncthreads();
-    // dqa / dqb: thread = (row, 4-channel group)
-    for (int i = tid; i < T * 32; i += 256) {
-        const int row = i >> 5, g = i & 31;
-        const size_t off = (row0 + row) * 128 + g * 4;
-        const f32x4 a = *reinterpret_cast<const f32x4*>(qa + off);
-        const f32x4 bq = *reinterpret_cast<const f32x4*>(qb + off);
-        const f32x4 pq = dqb_acc ? *reinterpret_cast<const f32x4*>(dqb_acc + off) : f32x4{0.f, 0.f, 0.f, 0.f};
-        const float d = dl[row];
-        f32x4 oa, ob;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            oa[e] = d * bq[e];
-            ob[e] = pq[e] + d * a[e];
-        }
-        *reinterpret_cast<f32x4*>(dqa + off) = oa;
-        *reinterpret_cast<f32x4*>(dqb + off) = ob;
-    }
+    attend_hidden_bwd_ray<BwdF32>(qa, qb, hs, at_wt, dhbar, dw_ext, V, R, S, ray0, dqa, dqb, nullptr, dqb_acc);
 }
 
 // d(pre-activation of the first encoder layer) from ALL consumers of `hid` in one pass:
@@ -495,7 +449,7 @@ __global__ __launch_bounds__(256) void hid_grad_combine_kernel(
     const int v = (int)(t % V); t /= V;                             // t = ray inside this launch
     const long long ray = ray0 + t;
     const int b = (int)(ray / R), r = (int)(ray % R);
-    const size_t widx = (((size_t)(b * V + v)) * R + r) * S + s;
+    const size_t widx = sample_index(b, V, v, R, r, S, s);
     const half8 h = *reinterpret_cast<const half8*>(hid + (size_t)row * 832 + c8 * 8);
     float acc[8];
     if (dkey) {

@@ -29,6 +29,13 @@ int cpn_stream_cus(void* stream);
 
 static inline unsigned cpn_cdiv(long long a, long long b) { return (unsigned)((a + b - 1) / b); }
 
+// Index of sample s of ray r as view v of batch element b sees it, in the (B V, R, S) arrays that travel per sample: at_wt,
+// dw_ext, the parked w1 / w2, and - times 2 or 6 at the call site - pixel_val, sec_grid and the point encodings.
+// (Here rather than in encode_geometry.h: rayout.hip, gemm_f16.hip and attend.hip have no use for the node tables.)
+__host__ __device__ __forceinline__ size_t sample_index(int b, int V, int v, int R, int r, int S, int s) {
+    return (((size_t)(b * V + v)) * R + r) * S + s;
+}
+
 typedef _Float16 half8 __attribute__((ext_vector_type(8)));
 typedef _Float16 half4 __attribute__((ext_vector_type(4)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));

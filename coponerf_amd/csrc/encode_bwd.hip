@@ -603,7 +603,7 @@ __global__ __launch_bounds__(256) void gather_tail_kernel(const __half* __restri
     const int v = (int)(t % (unsigned)V); t /= (unsigned)V;
     const unsigned ray = t + (unsigned)ray0;
     const int b = (int)(ray / (unsigned)R), r = (int)(ray - (unsigned)b * (unsigned)R);
-    const size_t sidx = (((size_t)(b * V + v)) * R + r) * S + s;
+    const size_t sidx = sample_index(b, V, v, R, r, S, s);
     half8 o;
 #pragma unroll
     for (int e = 0; e < 8; ++e) o[e] = (_Float16)0.0f;

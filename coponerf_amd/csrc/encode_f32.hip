@@ -6,11 +6,11 @@
 // exact-fp32 GEMM launches per 128-column block: 43.7 TFLOP per 256^2 x 64 image, 78 k rays/s); the algebra removes 85 % of that.
 //
 // Replaces, per sample (/root/reference models/CoPoNeRF.py:312, 370, 384-397): F.grid_sample x 8 + cat + query_encode_latent
-// (Conv2d 835 -> 832) + ReLU, and per ray (:450-461, 475-485) the joint softmax + weighted sum, evaluated on the hidden layer.
+// (Conv2d 835 -> 832) + ReLU.  (The mode's joint softmax + weighted sum per ray, cpn_attend_hidden_f32, is the f32 trait of the
+// one attention body in attend.hip.)
 //
 //   cpn_node_features_f32   the three coarse levels sampled at every table node, fp32 (node_features_kernel of encode.hip in fp32)
 //   cpn_encode_hidden_f32   hid = ReLU(sum_t a_t T32[node_t] + W[:, 768:835] . [gather_3 | tanh(pt/5)] + b) -> (hi, lo) fp16 pairs
-//   cpn_attend_hidden_f32   joint softmax of <qa, qb> / 11.31 over the 2 S samples of a ray, hbar = sum_s w_s (hi_s + lo_s), fp32
 //
 // gfx950 notes.  cpn_encode_hidden_f32 is a persistent kernel, one 512-thread workgroup per CU; a workgroup computes HALF of the
 // layer's channels (416) for its range of rows, so that its share of the K = 67 (+ bias) fp32 block - 111 KB; the whole block is
@@ -124,7 +124,7 @@ struct Producer {
                 if (ray < 0 || ray >= nraytot) { flive = false; ray = 0; }
             }
             const int bb = (int)(ray / R), r = (int)(ray - (long long)bb * R);
-            const size_t sidx = (((size_t)(bb * V + vv)) * R + r) * S + s;
+            const size_t sidx = sample_index(bb, V, vv, R, r, S, s);
             fown = j == 0;
             gc = *reinterpret_cast<const f32x2*>((fown ? pixel_val : sec_grid) + sidx * 2);
             const float* pe = pe6 + sidx * 6 + j * 3;
@@ -180,7 +180,6 @@ struct Producer {
 
 constexpr int EWAVES = 8;                // 7 owner waves (26 channel tiles of 16) + 1 producer wave
 constexpr int ECH = 416;                 // channels per workgroup: half of the layer
-constexpr int ETILES = ECH / 16;         // 26
 constexpr int WLD = 432;                 // LDS row stride of the weight block in floats (= 16 mod 32: the four k groups of an
                                          // A-operand read fall on disjoint bank halves)
 constexpr int EF32_LDS = KX * WLD * 4 + 2 * (int)sizeof(BatchLds);
@@ -288,85 +287,6 @@ __global__ __launch_bounds__(64 * EWAVES, 1) void encode_hidden_f32_kernel(
     }
 }
 
-constexpr int HCF = 1664;
-
-
-// one workgroup per ray: logits from (rows,128) fp32 operands, softmax over the V*S rows, hbar = sum_rows w (hi + lo);
-// LIST: the workgroup's ray is rays[ray0 + blockIdx.x] (its at_wt rows are skipped if that lies outside [0, nraytot))
-template <bool LIST>
-__global__ __launch_bounds__(256) void attend_hidden_f32_kernel(const float* __restrict__ qa, const float* __restrict__ qb,
-                                                                const __half* __restrict__ hs, int V, int R, int S, int ray0,
-                                                                float* __restrict__ hbar, float* __restrict__ at_wt,
-                                                                const int* __restrict__ rays, long long nraytot) {
-    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-    float* wts = reinterpret_cast<float*>(smem_raw);
-    float* red = wts + V * S;
-    const int T = V * S;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const long long lray = blockIdx.x;
-    const size_t row0 = (size_t)lray * T;
-    float lmax = -INFINITY;
-    for (int base = 0; base < T; base += 8) {                  // 32 lanes per row, 4 floats each
-        const int row = base + (tid >> 5);
-        const int rr = row < T ? row : T - 1;
-        const f32x4 a = *reinterpret_cast<const f32x4*>(qa + (row0 + rr) * 128 + (tid & 31) * 4);
-        const f32x4 b = *reinterpret_cast<const f32x4*>(qb + (row0 + rr) * 128 + (tid & 31) * 4);
-        float acc = a[0] * b[0] + a[1] * b[1] + a[2] * b[2] + a[3] * b[3];
-#pragma unroll
-        for (int o = 16; o > 0; o >>= 1) acc += __shfl_xor(acc, o);
-        if (row < T) {
-            const float logit = acc / 11.31f;
-            if ((tid & 31) == 0) wts[row] = logit;
-            lmax = fmaxf(lmax, logit);
-        }
-    }
-    lmax = wave_max(lmax);
-    if (lane == 0) red[wave] = lmax;
-    __syncthreads();
-    const float gmax = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-    float lsum = 0.f;
-    for (int row = tid; row < T; row += 256) {
-        const float e = __expf(wts[row] - gmax);
-        wts[row] = e;
-        lsum += e;
-    }
-    lsum = wave_sum(lsum);
-    if (lane == 0) red[4 + wave] = lsum;
-    __syncthreads();
-    const float inv = 1.0f / ((red[4] + red[5]) + (red[6] + red[7]));
-    for (int row = tid; row < T; row += 256) {
-        const float w = wts[row] * inv;
-        wts[row] = w;
-        if (at_wt) {
-            unsigned ray = (unsigned)ray0 + (unsigned)lray;
-            if constexpr (LIST) {
-                const int lr = rays[ray0 + lray];
-                if (lr < 0 || lr >= nraytot) continue;
-                ray = (unsigned)lr;
-            }
-            const int b = (int)(ray / (unsigned)R), r = (int)(ray % (unsigned)R);
-            const int v = row / S, s = row - v * S;
-            at_wt[(((size_t)(b * V + v)) * R + r) * S + s] = w;
-        }
-    }
-    __syncthreads();
-    if (tid < HCF / 8) {                                       // thread = 8 hidden channels, rows streamed
-        float acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-        const __half* hp = hs + row0 * 3328 + tid * 8;
-#pragma unroll 8
-        for (int row = 0; row < T; ++row) {
-            const half8 hi = __builtin_nontemporal_load(reinterpret_cast<const half8*>(hp + (size_t)row * 3328));
-            const half8 lo = __builtin_nontemporal_load(reinterpret_cast<const half8*>(hp + (size_t)row * 3328 + 1664));
-            const float w = wts[row];
-#pragma unroll
-            for (int e = 0; e < 8; ++e) acc[e] += w * ((float)hi[e] + (float)lo[e]);
-        }
-        float* o = hbar + (size_t)lray * HCF + tid * 8;
-        *reinterpret_cast<f32x4*>(o) = f32x4{acc[0], acc[1], acc[2], acc[3]};
-        *reinterpret_cast<f32x4*>(o + 4) = f32x4{acc[4], acc[5], acc[6], acc[7]};
-    }
-}
-
 }  // namespace
 
 extern "C" int cpn_node_features_f32(const float* map0, const float* map1, const float* map2, int H, int W, int nimg, float* feat,
@@ -421,22 +341,6 @@ int encode_hidden_f32(const float* tab, const float* map3, int H, int W, const f
     return 0;
 }
 
-template <bool LIST>
-int attend_hidden_f32(const float* qa, const float* qb, const uint16_t* hs, int B, int V, int R, int S, const int* rays, int ray0,
-                      int nrays, float* hbar, float* at_wt, void* stream) {
-    CPN_REQUIRE(qa && qb && hs && hbar && (!LIST || rays), CPN_E_ARG, "cpn_attend_hidden_f32: null pointer");
-    CPN_REQUIRE(B > 0 && V == 2 && R > 0 && S > 0 && V * S <= 4096, CPN_E_SHAPE, "cpn_attend_hidden_f32: bad shape");
-    CPN_REQUIRE(ray0 >= 0 && nrays > 0 && (LIST || (long long)ray0 + nrays <= (long long)B * R), CPN_E_ARG,
-                "cpn_attend_hidden_f32: ray range outside B*R");
-    CPN_REQUIRE(((uintptr_t)qa % 16) == 0 && ((uintptr_t)qb % 16) == 0 && ((uintptr_t)hs % 16) == 0 && ((uintptr_t)hbar % 16) == 0,
-                CPN_E_ARG, "cpn_attend_hidden_f32: operands must be 16-byte aligned");
-    const size_t lds = (size_t)(V * S + 8) * sizeof(float);
-    hipLaunchKernelGGL(attend_hidden_f32_kernel<LIST>, dim3(nrays), dim3(256), lds, (hipStream_t)stream, qa, qb, (const __half*)hs, V,
-                       R, S, ray0, hbar, at_wt, rays, (long long)B * R);
-    CPN_LAUNCH_CHECK("cpn_attend_hidden_f32");
-    return 0;
-}
-
 }  // namespace
 
 extern "C" int cpn_encode_hidden_f32(const float* tab, const float* map3, int H, int W, const float* pixel_val, const float* sec_grid,
@@ -449,14 +353,4 @@ extern "C" int cpn_encode_hidden_f32_rays(const float* tab, const float* map3, i
                                           const float* sec_grid, const float* pe6, const float* w80t, int B, int V, int R, int S,
                                           const int* rays, int ray0, int nrays, uint16_t* hs, void* stream) {
     return encode_hidden_f32<true>(tab, map3, H, W, pixel_val, sec_grid, pe6, w80t, B, V, R, S, rays, ray0, nrays, hs, stream);
-}
-
-extern "C" int cpn_attend_hidden_f32(const float* qa, const float* qb, const uint16_t* hs, int B, int V, int R, int S, int ray0,
-                                     int nrays, float* hbar, float* at_wt, void* stream) {
-    return attend_hidden_f32<false>(qa, qb, hs, B, V, R, S, nullptr, ray0, nrays, hbar, at_wt, stream);
-}
-
-extern "C" int cpn_attend_hidden_f32_rays(const float* qa, const float* qb, const uint16_t* hs, int B, int V, int R, int S,
-                                          const int* rays, int ray0, int nrays, float* hbar, float* at_wt, void* stream) {
-    return attend_hidden_f32<true>(qa, qb, hs, B, V, R, S, rays, ray0, nrays, hbar, at_wt, stream);
 }

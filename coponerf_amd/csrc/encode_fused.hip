@@ -226,7 +226,7 @@ __global__ __launch_bounds__(64 * WAVES, 1) void encode_fused_kernel(
             mid[u] = tile_row(r, urg[u], usb[u], S, R, ub[u], ray0, nrays);
             lid[u].live = lid[u].live && ulive[u];
             mid[u].live = mid[u].live && ulive[u];
-            sidx_l[u] = (((size_t)(ub[u] * V + uv[u])) * R + min(lid[u].r, R - 1)) * S + min(lid[u].s, S - 1);
+            sidx_l[u] = sample_index(ub[u], V, uv[u], R, min(lid[u].r, R - 1), S, min(lid[u].s, S - 1));
             trow0[u] = ((((long long)ub[u] * R + (long long)urg[u] * TG - ray0) * V + uv[u]) * S + (long long)usb[u] * TSW) * 2;
         }
         // hid stores: unconditional nt buffer stores (encode.hip, CPN_ENCODE_STORE 7) through ONE descriptor per iteration
@@ -313,7 +313,7 @@ __global__ __launch_bounds__(64 * WAVES, 1) void encode_fused_kernel(
 #pragma unroll
                 for (int e = 0; e < 4; ++e) xt[u][e] = (_Float16)0.0f;
                 if (g == 0 && mid[u].live) {
-                    const float* pe = pe6 + ((((size_t)(ub[u] * V + uv[u])) * R + mid[u].r) * S + mid[u].s) * 6 + j0 * 3;
+                    const float* pe = pe6 + sample_index(ub[u], V, uv[u], R, mid[u].r, S, mid[u].s) * 6 + j0 * 3;
                     xt[u][0] = (_Float16)pe[0]; xt[u][1] = (_Float16)pe[1]; xt[u][2] = (_Float16)pe[2];
                     xt[u][3] = (_Float16)1.0f;                // x bias (hi)
                 }

@@ -93,7 +93,7 @@ __device__ __forceinline__ RowRef row_of(int idx, int per, int S, bool s_pow2, i
     const int sm = rem - rr * S;
     const int r = rlo + rr;
     const int v = o.j ? (V - 1 - vi) : vi;
-    const size_t sidx = (((size_t)(b * V + v)) * R + r) * S + sm;
+    const size_t sidx = sample_index(b, V, v, R, r, S, sm);
     o.g = *reinterpret_cast<const float2*>((o.j ? sec_grid : pixel_val) + sidx * 2);
     o.row = ((((unsigned)(b * R + r - ray0)) * V + v) * S + sm) * 2 + o.j;
     return o;

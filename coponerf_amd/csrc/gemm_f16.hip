@@ -103,18 +103,13 @@ struct CombineArgs {
     int V, R, S, ray0;
     int accum;                                                                   // OUT_F32: C += (the product + bias), then the ReLU
 };
-#ifndef CPN_HID_READ_NT
-#define CPN_HID_READ_NT 1
-#endif
 template <int NT, bool OUT_F32, bool RELU, int DOT = 0>
 __global__ __launch_bounds__(512) void gemm_f16_kernel(const __half* __restrict__ A, int lda,
                                                              const __half* __restrict__ W, int ldw,
                                                              const float* __restrict__ bias,
                                                              void* __restrict__ Cv, int ldc, int M, int K32, int n_tiles,
                                                              int total_tiles, const __half* __restrict__ Q = nullptr,
-                                                             int ldq = 0, const __half* __restrict__ W2 = nullptr,
-                                                             int ldw2 = 0, const float* __restrict__ bias2 = nullptr,
-                                                             CombineArgs ca = CombineArgs{}) {
+                                                             int ldq = 0, CombineArgs ca = CombineArgs{}) {
     using C_ = Cfg<NT>;
     constexpr int A_AUX = 0;
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -358,7 +353,7 @@ __global__ __launch_bounds__(512) void gemm_f16_kernel(const __half* __restrict_
                     const int v = rem / ca.S, s0 = rem - v * ca.S;
                     const int ray = ca.ray0 + t;
                     const int b = ray / ca.R, rr = ray - b * ca.R;
-                    wbase = (((size_t)(b * ca.V + v)) * ca.R + rr) * ca.S + s0;
+                    wbase = sample_index(b, ca.V, v, ca.R, rr, ca.S, s0);
                 }
                 half8 hv[NI];
                 float wa[NI], wb_[NI];
@@ -479,8 +474,7 @@ int launch(const __half* A, int lda, const __half* W, int ldw, const float* bias
     const int num_cu = cpn_stream_cus((void*)stream);       // persistent grid: the CUs this stream may use
     dim3 grid((unsigned)std::min<long long>(total, num_cu));       // persistent: one workgroup per CU
     hipLaunchKernelGGL(kern, grid, dim3(512), lds, stream, A, lda, W, ldw, bias, C, ldc, M, K32, n_tiles, (int)total,
-                       (const __half*)nullptr, 0, (const __half*)nullptr, 0, (const float*)nullptr,
-                       CombineArgs{nullptr, nullptr, nullptr, nullptr, 0, 0, 0, 0, accum});
+                       (const __half*)nullptr, 0, CombineArgs{nullptr, nullptr, nullptr, nullptr, 0, 0, 0, 0, accum});
     CPN_LAUNCH_CHECK("cpn_gemm_f16");
     return 0;
 }
@@ -509,7 +503,7 @@ int launch_combine(const __half* A, int lda, const __half* W, int ldw, const __h
     const int num_cu = cpn_stream_cus((void*)stream);
     dim3 grid((unsigned)std::min<long long>(total, num_cu));
     hipLaunchKernelGGL(kern, grid, dim3(512), lds, stream, A, lda, W, ldw, (const float*)nullptr, (void*)out, ld, M, K32, n_tiles,
-                       (int)total, hid, ldh, (const __half*)nullptr, 0, (const float*)nullptr, ca);
+                       (int)total, hid, ldh, ca);
     CPN_LAUNCH_CHECK("cpn_gemm_f16_combine");
     return 0;
 }

@@ -10,14 +10,13 @@
 // Rays whose score passes a threshold are re-rendered in the reference's arithmetic (csrc/encode_f32.hip, the _rays entries).
 //
 //   cpn_logit_guard   one 256-thread workgroup per ray; reads the chunk's logits (4 bytes per sample) where cpn_attend_hidden
-//                     reads them and forms w exactly as it does (same max, __expf, sum order)
+//                     reads them and forms w with the code it uses (ray_softmax.h)
 //   cpn_select_rays   ascending list of the rays with score > tau and its count: a workgroup per tile of 4096 rays counts the
 //                     flags of all earlier tiles itself (no scratch, no atomics, one launch; <= 1 MB of L2-resident reads per
 //                     workgroup at 262 144 rays), then scans its own tile
-#include "common.h"
+#include "ray_softmax.h"
 
 namespace {
-
 
 // one workgroup of 256 threads per ray of the chunk; wts: V*S floats of LDS
 __global__ __launch_bounds__(256) void logit_guard_kernel(const float* __restrict__ logits, int V, int S, int ray0,
@@ -27,25 +26,9 @@ __global__ __launch_bounds__(256) void logit_guard_kernel(const float* __restric
     __shared__ float red[12];
     const int T = V * S;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const size_t row0 = (size_t)blockIdx.x * T;
-    // the softmax of attend.hip (attend_hidden_ray, HAVE_LOGITS) step for step: per-thread max over rows tid, tid + 256 ..,
-    // wave max, max of the four waves; exp and per-thread sums in the same row order, wave sums, (s0 + s1) + (s2 + s3)
-    float lmax = -INFINITY;
-    for (int row = tid; row < T; row += 256) {
-        const float logit = logits[row0 + row] / 11.31f;
-        wts[row] = logit;
-        lmax = fmaxf(lmax, logit);
-    }
-    lmax = wave_max(lmax);
-    if (lane == 0) red[wave] = lmax;
-    __syncthreads();
-    const float gmax = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-    float lsum = 0.f;
-    for (int row = tid; row < T; row += 256) lsum += __expf(wts[row] - gmax);
-    lsum = wave_sum(lsum);
-    if (lane == 0) red[4 + wave] = lsum;
-    __syncthreads();
-    const float inv = 1.0f / ((red[4] + red[5]) + (red[6] + red[7]));
+    // the weights of cpn_attend_hidden's `logits` mode bit for bit: the same two steps of ray_softmax.h
+    const float lmax = ray_logits_to_lds(logits + (size_t)blockIdx.x * T, wts, T);
+    const auto [gmax, inv] = ray_softmax_stats<true>(lmax, wts, red, T);
     float acc = 0.f;
     for (int row = tid; row < T; row += 256) {
         const float l = wts[row];

@@ -1,5 +1,7 @@
 // One row of the attention-weighted hidden sum, acc[e] += w * h[e] for the 8 channels of a 16-byte chunk - shared by
-// cpn_attend_hidden (attend.hip) and cpn_attend_units (attend_units.hip), which must produce the same bits.
+// cpn_attend_hidden (the fp16 trait of attend.hip's one body) and cpn_attend_units (attend_units.hip), which must produce the
+// same bits.  (The f32 trait's row, w * (hi + lo), is fused on every channel and written out beside it in attend.hip; the
+// workgroup softmax in front of both is ray_softmax.h.)
 // The rounding is WRITTEN OUT rather than left to -ffp-contract: channels 0 .. 5 are fused multiply-adds; channels 6 and 7 of the
 // rows below (T & ~3) - the rows cpn_attend_hidden has always taken four at a time - add a ROUNDED product (two roundings), the
 // remaining T & 3 rows fuse all eight.  That is how attend_hidden_kernel has been compiled since it was written (the vectoriser

@@ -219,7 +219,7 @@ __global__ __launch_bounds__(256) void ray_outputs_kernel(const float* __restric
     const int b = (int)(ray / R), r = (int)(ray - (long long)b * R);
     float ex[3] = {0.f, 0.f, 0.f};
     for (int v = 0; v < 2; ++v) {
-        const size_t base = (((size_t)b * 2 + v) * R + r) * S;
+        const size_t base = sample_index(b, 2, v, R, r, S, 0);
         float best = -INFINITY, sx = 0.f, sy = 0.f, sz = 0.f;
         int bi = 0x7fffffff;
         for (int s = lane; s < S; s += 64) {

@@ -165,18 +165,10 @@ class AttendHiddenF32Fn(Function):
         dh = dhbar.float().contiguous()
         dwc = None if dw is None else dw.float().contiguous()
         dqa, dqb = torch.empty_like(qa), torch.empty_like(qb)
-        share = ctx.qb_last is not None
-        acc = bp.dqb if (share and ctx.qb_last) else None
-        call("cpn_attend_hidden_bwd_f32", qa.data_ptr(), qb.data_ptr(), hs.data_ptr(), w.data_ptr(), dh.data_ptr(),
-             0 if dwc is None else dwc.data_ptr(), B, V, R, S, 0, nrays, dqa.data_ptr(), dqb.data_ptr(),
-             0 if acc is None else acc.data_ptr(), _stream())
+        dqb = bp.shared_qb_grad(ctx.qb_last, dqb, lambda acc: call(
+            "cpn_attend_hidden_bwd_f32", qa.data_ptr(), qb.data_ptr(), hs.data_ptr(), w.data_ptr(), dh.data_ptr(),
+            0 if dwc is None else dwc.data_ptr(), B, V, R, S, 0, nrays, dqa.data_ptr(), dqb.data_ptr(), acc, _stream()))
         bp.parts.append((w, dh))            # unscaled: KeyLayerF32Fn fixes the pass's scale
-        if share:
-            if ctx.qb_last:
-                bp.dqb, bp.dqb_done = None, True
-            elif not bp.dqb_done:
-                bp.dqb = dqb
-                dqb = None
         return dqa, dqb, None, None, None, None
 
 

@@ -65,6 +65,23 @@ class BackwardPass:
         """(w1, dh1, w2, dh2) of the parked parts for cpn_hid_grad_combine / cpn_gemm_f16_combine, 0 where there is none."""
         return ([t.data_ptr() for part in self.parts for t in part] + [0] * 4)[:4]
 
+    def shared_qb_grad(self, qb_last, dqb: torch.Tensor, launch, share: bool = True):
+        """The gradient of a qb (coords_embed) that two attention rounds share, for AttendHiddenFn / AttendHiddenF32Fn.backward.
+        launch(acc) runs the round's backward kernel, which writes `dqb` (+ acc, the data pointer of the other round's parked
+        gradient, or 0).  The round that runs first (qb_last False) parks its dqb here and returns None to autograd; the one
+        that runs last (True) has the parked tensor added inside the kernel and returns the sum.  qb_last None, or `share`
+        off: the round's own dqb."""
+        share = share and qb_last is not None
+        acc = self.dqb if (share and qb_last) else None
+        launch(0 if acc is None else acc.data_ptr())
+        if share:
+            if qb_last:
+                self.dqb, self.dqb_done = None, True
+            elif not self.dqb_done:         # (had the other round already run, nobody would pick the parked tensor up)
+                self.dqb = dqb
+                return None
+        return dqb
+
     def hand_over(self, name: str, grad: torch.Tensor) -> torch.Tensor:
         self.handed[name] = grad
         return grad
@@ -348,18 +365,11 @@ class AttendHiddenFn(Function):
         dh = dhbar.float().contiguous()
         dwc = None if dw is None else (dw.float() * bp.s).contiguous()
         dqa, dqb = torch.empty_like(qa), torch.empty_like(qb)
-        share = SHARE_QB_GRAD and ctx.qb_last is not None
-        acc = bp.dqb if (share and ctx.qb_last) else None
-        call("cpn_attend_hidden_bwd", qa.data_ptr(), qb.data_ptr(), hid2.data_ptr(), w.data_ptr(), dh.data_ptr(),
-             0 if dwc is None else dwc.data_ptr(), B, V, R, S, 0, nrays, dqa.data_ptr(), dqb.data_ptr(), 0,
-             0 if acc is None else acc.data_ptr(), _stream())
+        dqb = bp.shared_qb_grad(ctx.qb_last, dqb, lambda acc: call(
+            "cpn_attend_hidden_bwd", qa.data_ptr(), qb.data_ptr(), hid2.data_ptr(), w.data_ptr(), dh.data_ptr(),
+            0 if dwc is None else dwc.data_ptr(), B, V, R, S, 0, nrays, dqa.data_ptr(), dqb.data_ptr(), 0, acc, _stream()),
+            share=SHARE_QB_GRAD)
         bp.parts.append((w, dh))            # dhid = w (x) dhbar is formed by the producer of hid (cpn_hid_grad_combine)
-        if share:
-            if ctx.qb_last:
-                bp.dqb, bp.dqb_done = None, True
-            elif not bp.dqb_done:           # (had the other round already run, nobody would pick the parked tensor up)
-                bp.dqb = dqb
-                dqb = None
         return dqa, dqb, None, None, None, None
 
 

@@ -173,6 +173,35 @@ def test_bounds_admit_the_fp32_backward(case, with_ext):
     ref.assert_within("emulated dhid", dhid, want["dhid"], want["dhid_bound"])
 
 
+@pytest.mark.parametrize("case", ref.FWD_CASES, ids=ref.case_id)
+def test_bounds_without_the_fp16_terms_admit_the_fp32_arithmetic(case):
+    """What tests/test_gpu_attend_f64.py asks of the f32 kernels on every case: fp32 torch on make_inputs_f32 (hid = hi + lo
+    rounded to fp32, fp32 outputs) stays inside the bounds with f16_out=False, forward and - up to T = 2048 - backward."""
+    B, R, S, gain, ray0, nrays = case
+    T = V * S
+    x = ref.make_inputs_f32(case)
+    hid32 = x["hs"][:, :HC].float() + x["hs"][:, HC:].float()
+    hid = x["hs"][:, :HC].double() + x["hs"][:, HC:].double()
+    l = ((x["qa"] * x["qb"]).sum(1) / F_SCALE).view(nrays, T)
+    e = torch.exp(l - l.max(1, keepdim=True).values)
+    w = e * (1.0 / e.sum(1, keepdim=True))
+    hbar = (w.unsqueeze(-1) * hid32.view(nrays, T, HC)).sum(1)
+    fwd = ref.attend_fwd_ref(x["qa"], x["qb"], None, hid, B, R, S, ray0, nrays)
+    ref.assert_within("fp32 weights", w, fwd["w"], fwd["w_bound"])
+    want, bound = ref.hbar_ref(w, hid, nrays, S, f16_out=False)
+    ref.assert_within("fp32 hbar", hbar, want, bound)
+    if case not in ref.BWD_CASES:
+        return
+    ext = ref.from_global(x["dw_ext"], B, R, S, ray0, nrays)
+    dw = torch.bmm(hid32.view(nrays, T, HC), x["dhbar"].view(nrays, HC, 1)).squeeze(-1) + ext
+    dl = (w * (dw - (w * dw).sum(1, keepdim=True)) / F_SCALE).unsqueeze(-1)
+    dqa = (dl * x["qb"].view(nrays, T, 128)).view(-1, 128)
+    dqb = (x["acc"].view(nrays, T, 128) + dl * x["qa"].view(nrays, T, 128)).view(-1, 128)
+    want = ref.attend_bwd_ref(x["qa"], x["qb"], hid, w, x["dhbar"], ext, x["acc"], S, nrays, f16_out=False)
+    ref.assert_within("fp32 dqa", dqa, want["dqa"], want["dqa_bound"])
+    ref.assert_within("fp32 dqb", dqb, want["dqb"], want["dqb_bound"])
+
+
 @pytest.mark.parametrize("case", ref.COMBINE_CASES + ref.GEMM_CASES, ids=ref.case_id)
 def test_bounds_admit_the_fp32_combine(case):
     B, R, S, gain, ray0, nrays = case[:6]

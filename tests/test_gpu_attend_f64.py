@@ -1,5 +1,5 @@
 """The four kernels every sample of the default training path goes through - cpn_attend_hidden, cpn_attend_hidden_bwd,
-cpn_hid_grad_combine, cpn_gemm_f16_combine(_hs) - and the ray window of their fp32 siblings, each against its float64
+cpn_hid_grad_combine, cpn_gemm_f16_combine(_hs) - and their fp32 siblings on the same cases, each against its float64
 reference with an element-wise bound (tests/attend_ref.py; pinned and calibrated on the CPU by tests/test_attend_ref.py).
 No element is left out of any comparison; every global tensor holds NaN outside the ray window, every output starts as NaN
 and has 64 guard rows behind it.
@@ -7,7 +7,8 @@ and has 64 guard rows behind it.
 max err/bound of the first run on an MI355X, the worst over the cases of each kernel:
   cpn_attend_hidden            at_wt 0.009 (qa.qb mode), 0.095 (logits mode; the __expf term alone: 0.41); hbar 0.990
   cpn_attend_hidden_bwd        dqa 0.997, dqb 0.994, dhid 0.999 (all four ways; the fp16 rounding term dominates)
-  cpn_attend_hidden_f32        at_wt 0.018, hbar 0.136        cpn_attend_hidden_bwd_f32   dqa 0.015, dqb 0.323
+  cpn_attend_hidden_f32        at_wt 0.018, hbar 0.241        cpn_attend_hidden_bwd_f32   dqa 0.015, dqb 0.473
+                               (every forward / backward case since round 14; on WINDOW and RAGGED alone 0.136 and 0.323)
   cpn_hid_grad_combine         0.999 (both parts, one part, no dkey)
   cpn_gemm_f16_combine(_hs)    0.974 (K = 64), 0.943 (K = 128); the two entries give the same figures
 Where a ratio sits just under 1 the fp16 rounding of the output (half an ulp against u16 |want|) is what fills the bound; the
@@ -189,11 +190,13 @@ def test_attend_hidden_bwd_against_float64(case, variant, dev):
 # ------------------------------------------------------------------------------------------------------------------
 # (c) the fp32 siblings under a ray window
 # ------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("case", [ref.WINDOW, ref.RAGGED], ids=ref.case_id)
+@pytest.mark.parametrize("case", ref.FWD_CASES, ids=ref.case_id)
 def test_f32_attention_kernels_under_a_ray_window(case, dev):
-    """cpn_attend_hidden_f32 and cpn_attend_hidden_bwd_f32 with ray0 != 0 (test_attend_hidden_bwd_f32_against_float64_autograd
-    runs whole batches only): per element the tighter of that test's 1e-5 max|want| and the derived bound - the references of
-    the fp16 kernels with hid = hi + lo and without the fp16 rounding terms."""
+    """cpn_attend_hidden_f32 on every forward case and cpn_attend_hidden_bwd_f32 on every backward case - the f32 kernels are
+    the fp16 kernels' body under another trait, so they run at the edges of the same control flow (T = 6 < 8, a peaked ray, the
+    limits T = 2048 and, forward only, 4096) - against the derived bounds: the references of the fp16 kernels with
+    hid = hi + lo and without the fp16 rounding terms.  With ray0 != 0 (test_attend_hidden_bwd_f32_against_float64_autograd
+    runs whole batches only), on WINDOW and RAGGED, per element the tighter of the bound and that test's 1e-5 max|want|."""
     from coponerf_amd._hip import call
     B, R, S, gain, ray0, nrays = case
     rows = nrays * V * S
@@ -204,12 +207,19 @@ def test_f32_attention_kernels_under_a_ray_window(case, dev):
     wbuf = _out(B * V * R, S, torch.float32, dev)
     call("cpn_attend_hidden_f32", qa.data_ptr(), qb.data_ptr(), hs.data_ptr(), B, V, R, S, ray0, nrays, hbar.data_ptr(), wbuf.data_ptr(), _st())
     w = _take_global(wbuf, B, R, S, ray0, nrays, "f32 at_wt")
-    tighter = lambda bound, want: torch.minimum(bound, 1e-5 * want.abs().max().expand_as(bound))
+    if case in (ref.WINDOW, ref.RAGGED):
+        tighter = lambda bound, want: torch.minimum(bound, 1e-5 * want.abs().max().expand_as(bound))
+    else:
+        tighter = lambda bound, want: bound
     what = "f32 " + ref.case_id(case)
     fwd = ref.attend_fwd_ref(x["qa"], x["qb"], None, hid, B, R, S, ray0, nrays)
+    if case == ref.PEAKED:
+        assert float(fwd["w"].max()) > 0.3
     ref.assert_within(what + " at_wt", w, fwd["w"], tighter(fwd["w_bound"], fwd["w"]))
     want, bound = ref.hbar_ref(w, hid, nrays, S, f16_out=False)
     ref.assert_within(what + " hbar", _take(hbar, nrays, "f32 hbar"), want, tighter(bound, want))
+    if case not in ref.BWD_CASES:
+        return
     for with_ext in (True, False):
         dqa, dqb = _out(rows, 128, torch.float32, dev), _out(rows, 128, torch.float32, dev)
         call("cpn_attend_hidden_bwd_f32", qa.data_ptr(), qb.data_ptr(), hs.data_ptr(), wbuf.data_ptr(), dhbar.data_ptr(),
