@@ -209,7 +209,7 @@ int cpn_attend_units(int mode, const float* loc8, const float* coords9, const fl
 
 /* ---- K5: exact-fp32 per-ray linear layer (MFMA 16x16x4 f32)  Y = act_out( act_in(X) . W^T + bias + res ) --
  * replaces nn.Conv1d encode_latent (CoPoNeRF.py:468) and lightfield.ResnetFC (models/lightfield.py:131-167).
- *   X (M, ldx), W (N, ldw), bias (N) or NULL, res (M, ldr) or NULL, Y (M, ldy); N <= 128; K multiple of 4      */
+ *   X (M, ldx), W (N, ldw), bias (N) or NULL, res (M, ldr) or NULL, Y (M, ldy); N <= 128; K multiple of 16     */
 int cpn_linear_f32(const float* X, int ldx, const float* W, int ldw, const float* bias, const float* res, int ldr,
                    float* Y, int ldy, int M, int N, int K, int relu_in, int relu_out, void* stream);
 
@@ -261,7 +261,8 @@ int cpn_node_features_f32(const float* map0, const float* map1, const float* map
 /* first encoder layer on fp32 tables: per sample row (ray, view, sample, image j)
  *   hid = ReLU(sum_t a_t tab[node_t] + W[:, 768:835] . [bilinear(map3) 64 | tanh(pt/5) 3] + b)     (CoPoNeRF.py:384-397)
  * tab (nimg * nodes, 832) fp32 = node features . W[:, :768]^T, map3 (nimg, H, W, 64) fp32 NHWC, w80t (68, 832) fp32 = the
- * layer's columns 768..834 transposed (k-major) with the bias as row 67; output hs (nrays*V*S, 3328) fp16 (hi, lo) pairs  */
+ * layer's columns 768..834 transposed (k-major) with the bias as row 67; output hs (nrays*V*S, 3328) fp16 (hi, lo) pairs.
+ * hid must stay below the fp16 range (< 65 520): hi = fp16(hid) is inf beyond it and the pair no longer holds the value.   */
 int cpn_encode_hidden_f32(const float* tab, const float* map3, int H, int W, const float* pixel_val, const float* sec_grid,
                           const float* pe6, const float* w80t, int B, int V, int R, int S, int ray0, int nrays, uint16_t* hs,
                           void* stream);
