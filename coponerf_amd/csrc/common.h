@@ -41,8 +41,9 @@ typedef _Float16 half4 __attribute__((ext_vector_type(4)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
-// sum / maximum of a value over the 64 lanes of a wave, returned in every lane (xor butterfly, 32 .. 1)
-__device__ __forceinline__ float wave_sum(float v) {
+// sum / maximum of a value over the 64 lanes of a wave, returned in every lane (xor butterfly, 32 .. 1); float or double
+template <class T>
+__device__ __forceinline__ T wave_sum(T v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
     return v;
@@ -58,3 +59,29 @@ __device__ __forceinline__ float wave_max(float v) {
     for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
     return v;
 }
+
+namespace {          // internal linkage: the LDS scratch below belongs to the kernel of the unit that uses it
+
+// N values that each of the four waves of a 256-thread workgroup holds (the same in all lanes of a wave), summed over the
+// waves behind ONE barrier: wave w parks its values in LDS, every thread then reads (w0 + w1) + (w2 + w3).  Must be called
+// by all 256 threads, once per kernel and value type (a second use would need a barrier before it parks again).
+template <class T, int N>
+__device__ __forceinline__ void waves4_sum(T (&v)[N]) {
+    __shared__ T red[N][4];
+    if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+        for (int n = 0; n < N; ++n) red[n][threadIdx.x >> 6] = v[n];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int n = 0; n < N; ++n) v[n] = (red[n][0] + red[n][1]) + (red[n][2] + red[n][3]);
+}
+// N per-thread values summed over a 256-thread workgroup: wave_sum's butterfly in each wave, then waves4_sum
+template <class T, int N>
+__device__ __forceinline__ void block256_sum(T (&v)[N]) {
+#pragma unroll
+    for (int n = 0; n < N; ++n) v[n] = wave_sum(v[n]);
+    waves4_sum(v);
+}
+
+}  // namespace

@@ -15,20 +15,17 @@
 //   image_metrics_finish_kernel  one wave per image: its tiles' pairs in a fixed order, in float64 -> mse, psnr, ssim.
 // No atomics: two runs give the same bits, and an image's values do not depend on which other images share the launch.
 //
-// LDS: 6 x 26 x 42 + 5 x 26 x 32 floats = 42.9 KB -> 3 workgroups per CU (the layout of ssim_warp.hip's forward; the rows of a
-// wave are 42 or 32 floats apart, so the 32 lanes of one LDS pass read 32 consecutive banks).  Register and scratch use are
-// printed by -Rpass-analysis=kernel-resource-usage.
-#include "common.h"
+// The tile geometry, the LDS layout (42.9 KB -> 3 workgroups per CU) and the two window passes are ssim_window.h's, the
+// workgroup reduction common.h's, the float64 finish partial_sum.h's.  Register and scratch use are printed by
+// -Rpass-analysis=kernel-resource-usage.
+#include "partial_sum.h"
+#include "ssim_window.h"
 
 #include <math.h>
 
 namespace {
 
-constexpr int TW = 32, TH = 16, RAD = 5, WIN = 2 * RAD + 1;
-constexpr int RW = TW + 2 * RAD, RH = TH + 2 * RAD;
-constexpr int NT = 256;
-constexpr float SSIM_C1 = 0.01f * 0.01f, SSIM_C2 = 0.03f * 0.03f;       // (K1 L)^2, (K2 L)^2 at data_range L = 1
-
+// scipy's window: float64 weights, normalised in float64, rounded once (ssim_window.h: not the loss's fp32 window)
 struct Window {
     float g[WIN];
 };
@@ -54,7 +51,6 @@ __global__ __launch_bounds__(NT) void image_metrics_kernel(const float* __restri
     __shared__ float sx[3][RH * RW];
     __shared__ float sy[3][RH * RW];
     __shared__ float sh[5][RH * TW];
-    __shared__ float red[2][NT / 64];
     const int tid = threadIdx.x;
     const int n = blockIdx.z;
     const int tx0 = blockIdx.x * TW, ty0 = blockIdx.y * TH;
@@ -84,42 +80,15 @@ __global__ __launch_bounds__(NT) void image_metrics_kernel(const float* __restri
 
     float ss = 0.f;
     for (int c = 0; c < 3; ++c) {
-        for (int idx = tid; idx < RH * TW; idx += NT) {
-            const int r = idx / TW, col = idx - r * TW;
-            const float* const qx = &sx[c][r * RW + col];
-            const float* const qy = &sy[c][r * RW + col];
-            float m1 = 0.f, m2 = 0.f, e11 = 0.f, e22 = 0.f, e12 = 0.f;
-#pragma unroll
-            for (int k = 0; k < WIN; ++k) {
-                const float g = win.g[k], x = qx[k], y = qy[k];
-                m1 = __builtin_fmaf(g, x, m1);
-                m2 = __builtin_fmaf(g, y, m2);
-                e11 = __builtin_fmaf(g, x * x, e11);
-                e22 = __builtin_fmaf(g, y * y, e22);
-                e12 = __builtin_fmaf(g, x * y, e12);
-            }
-            sh[0][idx] = m1;
-            sh[1][idx] = m2;
-            sh[2][idx] = e11;
-            sh[3][idx] = e22;
-            sh[4][idx] = e12;
-        }
+        moment_rows(win.g, sx[c], sy[c], sh);
         __syncthreads();
         for (int p = tid; p < TH * TW; p += NT) {
             const int py = p / TW, px = p - py * TW;
             const int gy = ty0 + py, gx = tx0 + px;
             if (gy >= RAD && gy < H - RAD && gx >= RAD && gx < W - RAD) {          // skimage's crop
-                float m1 = 0.f, m2 = 0.f, e11 = 0.f, e22 = 0.f, e12 = 0.f;
-#pragma unroll
-                for (int k = 0; k < WIN; ++k) {
-                    const float g = win.g[k];
-                    const int o = (py + k) * TW + px;
-                    m1 = __builtin_fmaf(g, sh[0][o], m1);
-                    m2 = __builtin_fmaf(g, sh[1][o], m2);
-                    e11 = __builtin_fmaf(g, sh[2][o], e11);
-                    e22 = __builtin_fmaf(g, sh[3][o], e22);
-                    e12 = __builtin_fmaf(g, sh[4][o], e12);
-                }
+                float m[5];
+                window_cols(win.g, sh, py, px, m);
+                const float m1 = m[0], m2 = m[1], e11 = m[2], e22 = m[3], e12 = m[4];
                 const float vx = e11 - m1 * m1, vy = e22 - m2 * m2, vxy = e12 - m1 * m2;
                 const float ux = m1 + 0.5f, uy = m2 + 0.5f;                         // the means of p and t themselves
                 const float a1 = 2.0f * ux * uy + SSIM_C1, a2 = 2.0f * vxy + SSIM_C2;
@@ -129,40 +98,26 @@ __global__ __launch_bounds__(NT) void image_metrics_kernel(const float* __restri
         }
         __syncthreads();
     }
-    se = wave_sum(se);
-    ss = wave_sum(ss);
-    if ((tid & 63) == 0) {
-        red[0][tid >> 6] = se;
-        red[1][tid >> 6] = ss;
-    }
-    __syncthreads();
+    float v[2] = {se, ss};
+    block256_sum(v);
     if (tid == 0) {
         const size_t blk = ((size_t)n * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
-        partial[2 * blk + 0] = (red[0][0] + red[0][1]) + (red[0][2] + red[0][3]);
-        partial[2 * blk + 1] = (red[1][0] + red[1][1]) + (red[1][2] + red[1][3]);
+        partial[2 * blk + 0] = v[0];
+        partial[2 * blk + 1] = v[1];
     }
 }
 
-// one workgroup of 64 lanes per image; lane l sums tiles l, l + 64, .. in order, then a fixed tree
+// one workgroup of 64 lanes per image: sum_partials_f64 over its tiles' pairs
 __global__ __launch_bounds__(64) void image_metrics_finish_kernel(const float* __restrict__ partial, int nblk, int H, int W,
                                                                   float* __restrict__ out) {
     const int n = blockIdx.x, lane = threadIdx.x;
-    const float* const p = partial + (size_t)n * nblk * 2;
-    double se = 0.0, ss = 0.0;
-    for (int i = lane; i < nblk; i += 64) {
-        se += (double)p[2 * i];
-        ss += (double)p[2 * i + 1];
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        se += __shfl_xor(se, o);
-        ss += __shfl_xor(ss, o);
-    }
+    double s[2];                                                          // squared error, sum of S
+    sum_partials_f64<64>(partial + (size_t)n * nblk * 2, nblk, s);
     if (lane == 0) {
-        const double mse = se / (3.0 * (double)H * (double)W);
+        const double mse = s[0] / (3.0 * (double)H * (double)W);
         out[3 * n + 0] = (float)mse;
         out[3 * n + 1] = (float)(-10.0 * log(mse) / log(10.0));           // mse = 0: +inf, as the reference's mse2psnr
-        out[3 * n + 2] = (float)(ss / (3.0 * (double)(H - 2 * RAD) * (double)(W - 2 * RAD)));
+        out[3 * n + 2] = (float)(s[1] / (3.0 * (double)(H - 2 * RAD) * (double)(W - 2 * RAD)));
     }
 }
 

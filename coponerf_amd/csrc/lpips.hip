@@ -16,11 +16,11 @@
 //                        with 16-byte loads (a pixel's row is read in 256-byte segments) and keeps them in registers while the
 //                        two squared norms go round the 16 lanes, so every feature value is read once.  A workgroup owns 64
 //                        consecutive pixels of one image of one layer and writes ONE float.
-//   lpips_finish_kernel  one wave per image: its workgroups' floats layer by layer in a fixed order, in float64, each layer
-//                        divided by its pixel count, the layers added in order.
+//   lpips_finish_kernel  one wave per image: its workgroups' floats layer by layer in a fixed order, in float64
+//                        (partial_sum.h's sum_partials_f64), each layer divided by its pixel count, the layers added in order.
 // No atomics: two runs give the same bits; an image's workgroups and their order depend only on the maps' sizes, so its value
 // does not depend on N; a NaN reaches only the partials of its own image.
-#include "common.h"
+#include "partial_sum.h"
 
 #include <math.h>
 
@@ -217,22 +217,19 @@ __global__ __launch_bounds__(HEAD_NT) void lpips_head_kernel(HeadArgs A, float* 
     }
 }
 
-// one workgroup of 64 lanes per image; per layer lane l sums workgroups l, l + 64, .. in order, then a fixed tree
+// one workgroup of 64 lanes per image; per layer sum_partials_f64 over the image's workgroups
 __global__ __launch_bounds__(64) void lpips_finish_kernel(HeadArgs A, const float* __restrict__ partial, float* __restrict__ out,
                                                           float* __restrict__ per_layer) {
     const int n = blockIdx.x, lane = threadIdx.x;
     double total = 0.0;
     for (int k = 0; k < CPN_LPIPS_LAYERS; ++k) {
-        double s = 0.0;
+        double s[1] = {0.0};
         if (k < A.layers) {
-            const float* const p = partial + A.off[k] + (size_t)n * A.nblk[k];
-            for (int i = lane; i < A.nblk[k]; i += 64) s += (double)p[i];
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
-            s /= (double)A.P[k];
+            sum_partials_f64<64>(partial + A.off[k] + (size_t)n * A.nblk[k], A.nblk[k], s);
+            s[0] /= (double)A.P[k];
         }
-        total += s;
-        if (per_layer && lane == 0) per_layer[n * CPN_LPIPS_LAYERS + k] = (float)s;
+        total += s[0];
+        if (per_layer && lane == 0) per_layer[n * CPN_LPIPS_LAYERS + k] = (float)s[0];
     }
     if (lane == 0) out[n] = (float)total;
 }

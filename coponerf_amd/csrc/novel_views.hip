@@ -11,8 +11,9 @@
 //   camera_path_kernel        cpn_camera_path: one thread per (pose, pair).  exp(t log R_rel) and t t_rel in float64 from the
 //                             estimated rel_pose where it lies - on the device -, fp32 stores.
 //   pack_frames_kernel        cpn_pack_frames: one thread per output byte of a frame: the render's fp32 rgb to uint8 and, beside
-//                             it, the `jet` panel of depth_ray / 10 (cpn_depth_jet's lookup rule), written into the output tensor.
+//                             it, the `jet` panel of depth_ray / 10 (jet.h's lookup rule), written into the output tensor.
 #include "common.h"
+#include "jet.h"
 
 #include <math.h>
 
@@ -20,7 +21,6 @@ namespace {
 
 constexpr int NT = 256;
 constexpr int MAX_TAPS = 1024;                             // per axis: inputs up to 500 x the output side
-constexpr int JET_N = 256;
 
 // The resample rule of one axis (ATen's antialiased bilinear kernel, upsample_bilinear2d_aa): output i of n_out reads the taps
 // j in [lo, hi) of n_in with weights max(0, 1 - |j + 0.5 - c| / sup) over their sum, c = (i + 0.5) n_in / n_out and
@@ -170,13 +170,8 @@ __global__ __launch_bounds__(NT) void pack_frames_kernel(const float* __restrict
         out[i] = to_byte((rgb[(row * w + x) * 3 + ch] + 1.0f) * 127.5f);
         return;
     }
-    const float d = (depth[row * w + (x - w)] / 10.0f) * (float)JET_N;
-    float v = 0.f;                                         // NaN: the colour map's `bad` entry
-    if (d == d) {
-        const int idx = d < 0.f ? 0 : (d >= (float)JET_N ? JET_N - 1 : (int)d);
-        v = table[3 * idx + ch];
-    }
-    out[i] = to_byte(v * 255.0f);
+    const int idx = jet_index(depth[row * w + (x - w)]);
+    out[i] = to_byte(idx >= 0 ? table[3 * idx + ch] * 255.0f : 0.f);      // NaN: the colour map's `bad` entry
 }
 
 }  // namespace

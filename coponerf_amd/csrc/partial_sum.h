@@ -1,5 +1,6 @@
-// The two fixed-order sums of partial results that keep the training gradients bit-reproducible, once each: the reducers of
-// ufc_wgrad.hip and ufc_strided_bwd.hip (sum_partials_16x64), of wgrad_f32.hip and wgrad_tall.hip (sum_slabs_f32x4).
+// The fixed-order sums of partial results, once each.  Two keep the training gradients bit-reproducible: the reducers of
+// ufc_wgrad.hip and ufc_strided_bwd.hip (sum_partials_16x64), of wgrad_f32.hip and wgrad_tall.hip (sum_slabs_f32x4).  The third
+// is the float64 finish of the image-side units (sum_partials_f64: image_metrics.hip, ssim_warp.hip, lpips.hip, summaries.hip).
 #pragma once
 #include "common.h"
 
@@ -38,6 +39,24 @@ __device__ __forceinline__ void sum_partials_16x64(int n_out, long long n_part, 
 #pragma unroll
     for (int q = 0; q < 16; ++q) v += sh[q][j];
     store(i, v);
+}
+
+// The float64 finish of n float partials of N values each, partial i holding its values at p[N i .. N i + N - 1] (image
+// metrics, SSIM-warp, LPIPS, attention entropy).  Called by a workgroup of NT threads, for value k:
+//   thread t adds p[N i + k] for i = t, t + NT, t + 2 NT, ... in ascending order, each widened to double, starting from 0.0;
+//   wave_sum's butterfly (xor 32, 16, .. 1) then adds the 64 lanes of each wave.
+// s[k] is returned in every lane of a wave.  NT = 64: the sum itself; NT = 256: four wave sums that block256_sum's second
+// half (waves4_sum) finishes as (0 + 1) + (2 + 3).
+template <int NT, int N>
+__device__ __forceinline__ void sum_partials_f64(const float* __restrict__ p, int n, double (&s)[N]) {
+#pragma unroll
+    for (int k = 0; k < N; ++k) s[k] = 0.0;
+    for (int i = threadIdx.x; i < n; i += NT) {
+#pragma unroll
+        for (int k = 0; k < N; ++k) s[k] += (double)p[N * i + k];          // N n < 2^31: the entry points check it
+    }
+#pragma unroll
+    for (int k = 0; k < N; ++k) s[k] = wave_sum(s[k]);
 }
 
 // Element i of the sum of nslab slabs of n4 16-byte vectors each, in slab order: part[i] + part[n4 + i] + part[2 n4 + i] ...

@@ -21,20 +21,16 @@
 //   ssim_upsample_adjoint_kernel  one thread per low-resolution cell: gathers its footprint (border clamping included).
 // No atomics anywhere: loss and dflow are bit-reproducible.
 //
-// LDS of the forward: 6 x 26 x 42 + 5 x 26 x 32 floats = 42.9 KB -> 3 workgroups per CU = 3 waves per SIMD (98 VGPRs, no scratch:
-// -Rpass-analysis=kernel-resource-usage); the 42 x 42 x 15 form of all channels at once (106 KB) would hold one workgroup.  The
-// backward: 23.1 KB, 126 VGPRs, 4 waves per SIMD.  At 4 pairs of 256 x 256 the four launches take 53 + 5 + 24 + 10 us of a
-// 89 ms step: what they replace cost 3 ms as ~180 launches, mostly on the host.
-#include "common.h"
+// The tile geometry, the forward's LDS layout and the window passes (the forward's rows, both column passes) are
+// ssim_window.h's, the workgroup reduction common.h's, the float64 finish partial_sum.h's.  The forward runs 3 waves per SIMD
+// without scratch (-Rpass-analysis=kernel-resource-usage); the 42 x 42 x 15 form of all channels at once (106 KB) would
+// hold one workgroup.  The backward: 23.1 KB, 4 waves per SIMD.  At 4 pairs of 256 x 256 the four launches take
+// 53 + 5 + 24 + 10 us of a 89 ms step: what they replace cost 3 ms as ~180 launches, mostly on the host.
 #include "flow_warp.h"
+#include "partial_sum.h"
+#include "ssim_window.h"
 
 namespace {
-
-constexpr int TW = 32, TH = 16, RAD = 5, WIN = 2 * RAD + 1;
-constexpr int RW = TW + 2 * RAD, RH = TH + 2 * RAD;
-constexpr int NT = 256;
-constexpr float SSIM_C1 = 0.01f * 0.01f, SSIM_C2 = 0.03f * 0.03f;
-
 
 __global__ __launch_bounds__(NT) void ssim_warp_fwd_kernel(const float* __restrict__ rgb, const float* __restrict__ flow0,
                                                            const float* __restrict__ flow1, const uint8_t* __restrict__ mask,
@@ -45,7 +41,6 @@ __global__ __launch_bounds__(NT) void ssim_warp_fwd_kernel(const float* __restri
     __shared__ float sy[3][RH * RW];
     __shared__ float sh[5][RH * TW];
     __shared__ float swin[WIN];
-    __shared__ float red[2][NT / 64];
     const int tid = threadIdx.x;
     const int item = blockIdx.z, b = item >> 1, d = item & 1;
     const int tx0 = blockIdx.x * TW, ty0 = blockIdx.y * TH;
@@ -95,42 +90,15 @@ __global__ __launch_bounds__(NT) void ssim_warp_fwd_kernel(const float* __restri
 
     float num = 0.f, den = 0.f;
     for (int c = 0; c < 3; ++c) {
-        for (int idx = tid; idx < RH * TW; idx += NT) {
-            const int r = idx / TW, col = idx - r * TW;
-            const float* const px = &sx[c][r * RW + col];
-            const float* const py = &sy[c][r * RW + col];
-            float m1 = 0.f, m2 = 0.f, e11 = 0.f, e22 = 0.f, e12 = 0.f;
-#pragma unroll
-            for (int k = 0; k < WIN; ++k) {
-                const float g = swin[k], x = px[k], y = py[k];
-                m1 = __builtin_fmaf(g, x, m1);
-                m2 = __builtin_fmaf(g, y, m2);
-                e11 = __builtin_fmaf(g, x * x, e11);
-                e22 = __builtin_fmaf(g, y * y, e22);
-                e12 = __builtin_fmaf(g, x * y, e12);
-            }
-            sh[0][idx] = m1;
-            sh[1][idx] = m2;
-            sh[2][idx] = e11;
-            sh[3][idx] = e22;
-            sh[4][idx] = e12;
-        }
+        moment_rows(swin, sx[c], sy[c], sh);
         __syncthreads();
         for (int p = tid; p < TH * TW; p += NT) {
             const int py = p / TW, px = p - py * TW;
             const int gy = ty0 + py, gx = tx0 + px;
             if (gy < H && gx < W) {
-                float mu1 = 0.f, mu2 = 0.f, e11 = 0.f, e22 = 0.f, e12 = 0.f;
-#pragma unroll
-                for (int k = 0; k < WIN; ++k) {
-                    const float g = swin[k];
-                    const int o = (py + k) * TW + px;
-                    mu1 = __builtin_fmaf(g, sh[0][o], mu1);
-                    mu2 = __builtin_fmaf(g, sh[1][o], mu2);
-                    e11 = __builtin_fmaf(g, sh[2][o], e11);
-                    e22 = __builtin_fmaf(g, sh[3][o], e22);
-                    e12 = __builtin_fmaf(g, sh[4][o], e12);
-                }
+                float m[5];
+                window_cols(swin, sh, py, px, m);
+                const float mu1 = m[0], mu2 = m[1], e11 = m[2], e22 = m[3], e12 = m[4];
                 const float mu1mu2 = mu1 * mu2, mu1sq = mu1 * mu1, mu2sq = mu2 * mu2;
                 const float s1 = e11 - mu1sq, s2 = e22 - mu2sq, s12 = e12 - mu1mu2;
                 const float a1 = 2.0f * mu1mu2 + SSIM_C1, a2 = 2.0f * s12 + SSIM_C2;
@@ -152,44 +120,30 @@ __global__ __launch_bounds__(NT) void ssim_warp_fwd_kernel(const float* __restri
         }
         __syncthreads();
     }
-    num = wave_sum(num);
-    den = wave_sum(den);
-    if ((tid & 63) == 0) {
-        red[0][tid >> 6] = num;
-        red[1][tid >> 6] = den;
-    }
-    __syncthreads();
+    float v[2] = {num, den};
+    block256_sum(v);
     if (tid == 0) {
         const size_t blk = ((size_t)item * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
-        partial[2 * blk + 0] = (red[0][0] + red[0][1]) + (red[0][2] + red[0][3]);
-        partial[2 * blk + 1] = (red[1][0] + red[1][1]) + (red[1][2] + red[1][3]);
+        partial[2 * blk + 0] = v[0];
+        partial[2 * blk + 1] = v[1];
     }
 }
 
-// one workgroup of 64 lanes per direction; lane l sums blocks l, l + 64, .. of every pair's item in order, then a fixed tree
+// one workgroup of 64 lanes per direction: sum_partials_f64 over the blocks of each pair's item, the pairs added in order
 __global__ __launch_bounds__(64) void ssim_warp_finish_kernel(const float* __restrict__ partial, int B, int nblk,
                                                               float* __restrict__ sums, float* __restrict__ loss,
                                                               float* __restrict__ inv3den) {
     const int d = blockIdx.x, lane = threadIdx.x;
     double tn = 0.0, td = 0.0;
     for (int b = 0; b < B; ++b) {
-        const float* const p = partial + (size_t)(2 * b + d) * nblk * 2;
-        double n = 0.0, m = 0.0;
-        for (int i = lane; i < nblk; i += 64) {
-            n += (double)p[2 * i];
-            m += (double)p[2 * i + 1];
-        }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            n += __shfl_xor(n, o);
-            m += __shfl_xor(m, o);
-        }
+        double s[2];                                                      // num, den of item 2 b + d
+        sum_partials_f64<64>(partial + (size_t)(2 * b + d) * nblk * 2, nblk, s);
         if (lane == 0) {
-            sums[(2 * b + d) * 2 + 0] = (float)n;
-            sums[(2 * b + d) * 2 + 1] = (float)m;
+            sums[(2 * b + d) * 2 + 0] = (float)s[0];
+            sums[(2 * b + d) * 2 + 1] = (float)s[1];
         }
-        tn += n;
-        td += m;
+        tn += s[0];
+        td += s[1];
     }
     if (lane == 0) {
         const float fn = (float)tn, fd = (float)td;
@@ -260,15 +214,9 @@ __global__ __launch_bounds__(NT) void ssim_warp_bwd_kernel(const float* __restri
             if (!in[j]) continue;
             const int p = tid + j * NT, py = p / TW, px = p - py * TW;
             const int gy = ty0 + py, gx = tx0 + px;
-            float ga = 0.f, gb = 0.f, gc = 0.f;
-#pragma unroll
-            for (int k = 0; k < WIN; ++k) {
-                const float g = swin[k];
-                const int o = (py + k) * TW + px;
-                ga = __builtin_fmaf(g, sh[0][o], ga);
-                gb = __builtin_fmaf(g, sh[1][o], gb);
-                gc = __builtin_fmaf(g, sh[2][o], gc);
-            }
+            float gm[3];                                                   // G * A, G * B, G * C
+            window_cols(swin, sh, py, px, gm);
+            const float ga = gm[0], gb = gm[1], gc = gm[2];
             const WarpTaps& t = tp[j];
             const float v00 = (t.vy0 && t.vx0) ? src[((size_t)t.y0 * W + t.x0) * 3 + c] : 0.f;
             const float v01 = (t.vy0 && t.vx1) ? src[((size_t)t.y0 * W + t.x1) * 3 + c] : 0.f;

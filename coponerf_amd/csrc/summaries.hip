@@ -9,13 +9,17 @@
 //                             zero-padded taps of the OTHER direction's upsampled flow - each of them four low-resolution taps,
 //                             so no S x S flow is ever stored - the cycle norm, the validity mask, the four taps of the source
 //                             view scaled to [0, 255], and the overlay of summaries.py:42-63 in integers.
-//   depth_jet_kernel          one thread per depth value: matplotlib's index arithmetic on a float32 array, a table lookup.
+//   depth_jet_kernel          one thread per depth value: matplotlib's index arithmetic on a float32 array (jet.h), a table
+//                             lookup.
 //   attention_entropy_kernel  one wave per row of at_wt, 8 rows after one another per wave, 4 waves per workgroup: the row's
-//                             -sum w log(w + 1e-5) by the shared wave reduction, the workgroup's 32 rows as one float.
-//   attention_entropy_finish_kernel   the workgroups' partials in a fixed order, in float64 -> the mean over the rows.
+//                             -sum w log(w + 1e-5) by the shared wave reduction, the workgroup's 32 rows as one float
+//                             (common.h's waves4_sum).
+//   attention_entropy_finish_kernel   the workgroups' partials in a fixed order, in float64 (partial_sum.h's
+//                             sum_partials_f64 with 256 threads) -> the mean over the rows.
 // No atomics: every result is bit-reproducible, and an image's panels do not depend on the batch around it.
-#include "common.h"
 #include "flow_warp.h"
+#include "jet.h"
+#include "partial_sum.h"
 
 #include <math.h>
 
@@ -25,7 +29,6 @@ constexpr int NT = 256;
 constexpr int PTW = 32, PTH = NT / PTW;                   // flow panels: the tile of one workgroup
 constexpr int ENT_WAVES = NT / 64, ENT_ROWS = 8;          // entropy: rows per wave, one after another
 constexpr int ENT_BLOCK_ROWS = ENT_WAVES * ENT_ROWS;
-constexpr int JET_N = 256;
 
 // np.asarray(float32 image, dtype=np.uint8) on values that `warp` of a [0, 255] image can produce: truncation.  Four weights
 // that sum to 1 + an ulp can carry 255 slightly past 255; that and a NaN (which numpy leaves undefined) are kept in range.
@@ -88,10 +91,9 @@ __global__ __launch_bounds__(NT) void depth_jet_kernel(const float* __restrict__
                                                        float* __restrict__ out) {
     const long long i = (long long)blockIdx.x * NT + threadIdx.x;
     if (i >= n) return;
-    const float x = (depth[i] / 10.0f) * (float)JET_N;
+    const int idx = jet_index(depth[i]);
     float r = 0.f, g = 0.f, bl = 0.f;                      // NaN: the colour map's `bad` entry
-    if (x == x) {
-        const int idx = x < 0.f ? 0 : (x >= (float)JET_N ? JET_N - 1 : (int)x);
+    if (idx >= 0) {
         r = table[3 * idx + 0];
         g = table[3 * idx + 1];
         bl = table[3 * idx + 2];
@@ -104,10 +106,9 @@ __global__ __launch_bounds__(NT) void depth_jet_kernel(const float* __restrict__
 
 __global__ __launch_bounds__(NT) void attention_entropy_kernel(const float* __restrict__ w, long long rows, int S, int nan_to_zero,
                                                                float* __restrict__ partial) {
-    __shared__ float red[ENT_WAVES];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const long long r0 = ((long long)blockIdx.x * ENT_WAVES + wave) * ENT_ROWS;
-    float acc = 0.f;
+    float acc[1] = {0.f};                                  // the wave's rows: the same in every lane
     for (int k = 0; k < ENT_ROWS; ++k) {
         const long long r = r0 + k;
         if (r >= rows) break;                              // the same for every lane of the wave
@@ -119,24 +120,19 @@ __global__ __launch_bounds__(NT) void attention_entropy_kernel(const float* __re
         }
         e = -wave_sum(e);
         if (nan_to_zero && e != e) e = 0.f;                // wrapper.py:129
-        acc += e;
+        acc[0] += e;
     }
-    if (lane == 0) red[wave] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) partial[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+    waves4_sum(acc);
+    if (threadIdx.x == 0) partial[blockIdx.x] = acc[0];
 }
 
-// one workgroup: thread t sums partials t, t + 256, .. in order, then a fixed tree
+// one workgroup: sum_partials_f64 with 256 threads, then the four wave sums as (0 + 1) + (2 + 3)
 __global__ __launch_bounds__(NT) void attention_entropy_finish_kernel(const float* __restrict__ partial, int nblk, long long rows,
                                                                       float* __restrict__ out) {
-    __shared__ double red[ENT_WAVES];
-    double s = 0.0;
-    for (int i = threadIdx.x; i < nblk; i += NT) s += (double)partial[i];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) out[0] = (float)(((red[0] + red[1]) + (red[2] + red[3])) / (double)rows);
+    double s[1];
+    sum_partials_f64<NT>(partial, nblk, s);
+    waves4_sum(s);
+    if (threadIdx.x == 0) out[0] = (float)(s[0] / (double)rows);
 }
 
 }  // namespace

@@ -2,8 +2,11 @@
 
 Every user leaves its partial results in caller-owned scratch that survives the call.  Each test calls the entry, reads the
 partials back in the layout stated beside the entry's `*_scratch` function, replays the documented order on the host in
-float32 (numpy: one rounding per add) and requires the entry's result to be the same bits.  This holds even where the
-producing kernel is not bit-reproducible, because the sums are taken over the partials that very run produced."""
+float32 (numpy: one rounding per add; float64 for sum_partials_f64, the finish of the image-side units) and requires the
+entry's result to be the same bits.  This holds even where the producing kernel is not bit-reproducible, because the sums
+are taken over the partials that very run produced."""
+import ctypes
+
 import numpy as np
 import pytest
 import torch
@@ -45,6 +48,21 @@ def replay_slabs(parts):
     for q in range(1, parts.shape[0]):
         s += parts[q]
     return s
+
+
+def replay_f64(parts, nt=64):
+    """sum_partials_f64 for parts (n, ...) and a workgroup of nt threads: thread t adds partials t, t + nt, ... in ascending
+    order from 0.0 in float64, then the xor butterfly 32, 16, .. 1 adds the 64 lanes of each wave.  Returns the nt / 64 wave
+    sums, (nt / 64, ...)."""
+    parts = np.ascontiguousarray(parts, dtype=np.float32).astype(np.float64)
+    lanes = np.zeros((nt,) + parts.shape[1:], np.float64)
+    for i in range(parts.shape[0]):
+        lanes[i % nt] += parts[i]
+    v = lanes.reshape((nt // 64, 64) + parts.shape[1:])
+    for o in (32, 16, 8, 4, 2, 1):
+        v = v + v[:, np.arange(64) ^ o]
+    assert all(np.array_equal(v[:, 0], v[:, l], equal_nan=True) for l in range(64))     # every lane holds the sum
+    return v[:, 0]
 
 
 def _same_bits(got, want):
@@ -168,3 +186,88 @@ def test_tall_wgrad_slab_order(dev, scale):
         want = want * (np.float32(1.0) / np.float32(scale))              # the kernel's own two roundings: 1 / scale, then the product
     assert want.dtype == np.float32
     assert _same_bits(dW, want)
+
+
+# ---------------------------------------------------------------------- sum_partials_f64: the image-side units' finishes
+# 9 tiles of 16 x 32: one trip of the strided loop for nine lanes, none for the rest; 72 tiles: a second trip for lanes 0 .. 7
+@pytest.mark.parametrize("N,H,W", [(2, 41, 75), (1, 144, 256)])
+def test_image_metrics_finish_order(dev, N, H, W):
+    """The mse and ssim columns (psnr goes through the device's log: tests/test_gpu_metrics.py holds it)."""
+    from coponerf_amd import _hip
+    from coponerf_amd._hip import call
+    from tests import metrics_ref as mr
+    pred, target = (torch.from_numpy(a).to(dev) for a in mr.make_case("textured", N, H, W))
+    ntile = -(-H // 16) * -(-W // 32)
+    part = torch.zeros(_hip.lib().cpn_image_metrics_scratch(N, H, W), device=dev)
+    assert part.numel() == N * ntile * 2 and ntile == (9 if H == 41 else 72)
+    out = torch.empty(N, 3, device=dev)
+    call("cpn_image_metrics", pred.data_ptr(), target.data_ptr(), N, H, W, part.data_ptr(), out.data_ptr(), _st())
+    s = replay_f64(part.cpu().numpy().reshape(N, ntile, 2).transpose(1, 0, 2))[0]        # (N, [squared error, sum of S])
+    assert float(np.abs(s).min()) > 0.0
+    assert _same_bits(out[:, 0], s[:, 0] / (3.0 * H * W))
+    assert _same_bits(out[:, 2], s[:, 1] / (3.0 * (H - 10) * (W - 10)))
+
+
+def test_ssim_warp_finish_order(dev):
+    """The per-item `sums` (loss and 1 / (3 den) add fp32 divisions: tests/test_gpu_ssim_warp.py holds them).  72 blocks."""
+    from coponerf_amd import _hip, losses
+    from coponerf_amd._hip import call
+    from tests import ssim_ref as R
+    B, H, W, s = 1, 144, 256, 4
+    rgb, f0, f1 = (t.to(dev) for t in R.case(B, H, W, s))
+    ys, xs = torch.meshgrid(torch.arange(H), torch.arange(W), indexing="ij")
+    mask = (((ys + xs) % 3) != 0)[None, None].expand(B, 2, H, W).contiguous().to(dev)
+    win = losses.gaussian_window().to(dev)
+    nblk = _hip.lib().cpn_ssim_warp_blocks(H, W)
+    assert nblk == 72
+    coords, maps = torch.empty(2 * B, 2, H, W, device=dev), torch.empty(2 * B, 9, H, W, device=dev)
+    part = torch.zeros(2 * B, nblk, 2, device=dev)
+    sums, loss, inv = torch.empty(2 * B, 2, device=dev), torch.empty(2, device=dev), torch.empty(2, device=dev)
+    call("cpn_ssim_warp", rgb.data_ptr(), f0.data_ptr(), f1.data_ptr(), mask.data_ptr(), win.data_ptr(), B, H, W, H // s, W // s,
+         coords.data_ptr(), maps.data_ptr(), part.data_ptr(), sums.data_ptr(), loss.data_ptr(), inv.data_ptr(), _st())
+    want = replay_f64(part.cpu().numpy().transpose(1, 0, 2))[0]                           # (item, [num, den])
+    assert float(np.abs(want).min()) > 0.0
+    assert _same_bits(sums, want)
+
+
+def test_lpips_head_finish_order(dev):
+    """C = 64, N = 2, a 65 x 64 map (65 workgroups per image: a second trip for lane 0) and a 5 x 7 map (one) in one call:
+    per_layer is each layer's sum over its pixel count, out their sum in layer order."""
+    from coponerf_amd import _hip
+    from coponerf_amd._hip import call
+    from tests import lpips_ref as lr
+    N, C, shapes = 2, 64, ((65, 64), (5, 7))
+    maps, lins = zip(*[lr.make_maps(N, C, h, w, seed=40 + k) for k, (h, w) in enumerate(shapes)])
+    maps, lins = [m.to(dev) for m in maps], [l.to(dev) for l in lins]
+    ints, ptrs = ctypes.c_int * 2, ctypes.c_void_p * 2
+    hs, ws, cs = ints(*[h for h, _ in shapes]), ints(*[w for _, w in shapes]), ints(C, C)
+    nblk = [-(-(h * w) // 64) for h, w in shapes]
+    n = _hip.lib().cpn_lpips_head_scratch(N, 2, hs, ws)
+    assert nblk == [65, 1] and n == N * sum(nblk)
+    part, out, per = torch.zeros(n, device=dev), torch.empty(N, device=dev), torch.empty(N, 5, device=dev)
+    call("cpn_lpips_head", ptrs(*[m.data_ptr() for m in maps]), ptrs(*[l.data_ptr() for l in lins]), cs, hs, ws, 2, N,
+         part.data_ptr(), out.data_ptr(), per.data_ptr(), _st())
+    p, off = part.cpu().numpy(), 0
+    want, total = np.zeros((N, 5)), np.zeros(N)
+    for k, (h, w) in enumerate(shapes):                                                   # layer k: N x nblk[k] floats
+        want[:, k] = replay_f64(p[off:off + N * nblk[k]].reshape(N, nblk[k]).T)[0] / float(h * w)
+        total = total + want[:, k]
+        off += N * nblk[k]
+    assert float(want[:, :2].min()) > 0.0
+    assert _same_bits(per, want) and _same_bits(out, total)
+
+
+# one workgroup; 257: thread 0 of the finish's 256 makes a second trip.  Then the four wave sums as (0 + 1) + (2 + 3).
+@pytest.mark.parametrize("rows,S", [(5, 37), (8200, 8)])
+def test_attention_entropy_finish_order(dev, rows, S):
+    from coponerf_amd import _hip
+    from coponerf_amd._hip import call
+    w = torch.softmax(torch.randn(rows, S, generator=torch.Generator().manual_seed(9)), dim=-1).to(dev)
+    nblk = _hip.lib().cpn_attention_entropy_blocks(rows)
+    assert nblk == (1 if rows == 5 else 257)
+    part, out = torch.zeros(nblk, device=dev), torch.empty(1, device=dev)
+    call("cpn_attention_entropy", w.data_ptr(), rows, S, 0, part.data_ptr(), out.data_ptr(), _st())
+    v = replay_f64(part.cpu().numpy(), nt=256)
+    want = ((v[0] + v[1]) + (v[2] + v[3])) / float(rows)
+    assert want > 0.0
+    assert _same_bits(out, want)
