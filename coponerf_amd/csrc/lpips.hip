@@ -18,6 +18,17 @@
 //                        consecutive pixels of one image of one layer and writes ONE float.
 //   lpips_finish_kernel  one wave per image: its workgroups' floats layer by layer in a fixed order, in float64
 //                        (partial_sum.h's sum_partials_f64), each layer divided by its pixel count, the layers added in order.
+//   lpips_head_bwd_kernel  the head's adjoint with respect to the prediction maps, on the forward's grid and with its access
+//                        pattern: a workgroup owns the same 64 pixels, a lane the same channels; both maps are read once, the
+//                        two sums (sum f^2, sum u f) go round the 16 lanes, and the lane stores its channels of df with 16-byte
+//                        stores.  One launch for all layers and images, no scratch buffer.  A pixel whose prediction vector is all
+//                        zeros gets df = 0 (include/coponerf_hip.h: this library's rule; autograd gives NaN there).
+//   lpips_stem_bwd_kernel   the stem's adjoint with respect to pred, on the forward's 8 x 32 tiles.  Phase 1 walks the tile and
+//                        its 1-pixel halo with 16 lanes per pixel: a lane reads its 4 channels of dy and of the stem's output
+//                        (the ReLU mask) with 16-byte loads, multiplies by its 108 weights (registers, as in the forward) and
+//                        the 27 sums over the 64 channels go round the 16 lanes into LDS (27 floats per pixel, an odd stride:
+//                        phase 2 reads without bank conflicts).  Phase 2, one thread per pixel: the nine taps of each input
+//                        channel in (ky, kx) order, the division by the scale, the clamp's mask.
 // No atomics: two runs give the same bits; an image's workgroups and their order depend only on the maps' sizes, so its value
 // does not depend on N; a NaN reaches only the partials of its own image.
 #include "partial_sum.h"
@@ -128,6 +139,35 @@ struct HeadArgs {
 // the package's normalize_tensor adds its eps = 1e-10 to an fp32 tensor: the fp32 value of 1e-10
 constexpr float LPIPS_EPS = 1e-10f;
 
+// One pixel's vectors of both maps in the 16 lanes of its group (lane j: channels 4 (j + 16 i) .. + 3; zeros for a pixel past
+// the end) and their squared norms, in every lane of the group.  Shared by the head and its adjoint: the same loads, the same sums.
+template <int NV>
+__device__ __forceinline__ void head_load(const float* __restrict__ fp, const float* __restrict__ ft, int C, int P, int pix, int j,
+                                          f32x4 (&a)[NV], f32x4 (&b)[NV], float& sa, float& sb) {
+    // zeros first, the loads over them under the guard: written as if / else over arrays that arrive by reference, the compiler
+    // keeps two of the vectors in scratch memory through the pixel loop (48 bytes per lane); in this form both kernels use none
+#pragma unroll
+    for (int i = 0; i < NV; ++i) a[i] = b[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+    if (pix < P) {                                          // the same in all 16 lanes of a group; the shuffles below are outside
+        const float* const qa = fp + (size_t)pix * C + 4 * j;
+        const float* const qb = ft + (size_t)pix * C + 4 * j;
+#pragma unroll
+        for (int i = 0; i < NV; ++i) a[i] = *reinterpret_cast<const f32x4*>(qa + 4 * GROUP * i);
+#pragma unroll
+        for (int i = 0; i < NV; ++i) b[i] = *reinterpret_cast<const f32x4*>(qb + 4 * GROUP * i);
+    }
+    sa = 0.0f, sb = 0.0f;
+#pragma unroll
+    for (int i = 0; i < NV; ++i)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            sa = __builtin_fmaf(a[i][e], a[i][e], sa);
+            sb = __builtin_fmaf(b[i][e], b[i][e], sb);
+        }
+    sa = group16_sum(sa);
+    sb = group16_sum(sb);
+}
+
 // sum over one pixel's channels of w (a - b)^2 for the pixels g, g + 16, .. of a workgroup's 64, in every lane of the group
 template <int NV>
 __device__ __forceinline__ float head_pixels(const float* __restrict__ fp, const float* __restrict__ ft,
@@ -140,27 +180,8 @@ __device__ __forceinline__ float head_pixels(const float* __restrict__ fp, const
     for (int s = 0; s < HEAD_PIX / GROUPS; ++s) {
         const int pix = pix0 + g + GROUPS * s;
         f32x4 a[NV], b[NV];
-        if (pix < P) {                                      // the same in all 16 lanes of a group; the shuffles below are outside
-            const float* const qa = fp + (size_t)pix * C + 4 * j;
-            const float* const qb = ft + (size_t)pix * C + 4 * j;
-#pragma unroll
-            for (int i = 0; i < NV; ++i) a[i] = *reinterpret_cast<const f32x4*>(qa + 4 * GROUP * i);
-#pragma unroll
-            for (int i = 0; i < NV; ++i) b[i] = *reinterpret_cast<const f32x4*>(qb + 4 * GROUP * i);
-        } else {
-#pragma unroll
-            for (int i = 0; i < NV; ++i) a[i] = b[i] = f32x4{0.f, 0.f, 0.f, 0.f};
-        }
-        float sa = 0.0f, sb = 0.0f;
-#pragma unroll
-        for (int i = 0; i < NV; ++i)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                sa = __builtin_fmaf(a[i][e], a[i][e], sa);
-                sb = __builtin_fmaf(b[i][e], b[i][e], sb);
-            }
-        sa = group16_sum(sa);
-        sb = group16_sum(sb);
+        float sa, sb;
+        head_load<NV>(fp, ft, C, P, pix, j, a, b, sa, sb);
         const float ra = 1.0f / (sqrtf(sa) + LPIPS_EPS), rb = 1.0f / (sqrtf(sb) + LPIPS_EPS);
         float v = 0.0f;                                     // a pixel past the end gives w * 0 * 0
 #pragma unroll
@@ -178,15 +199,22 @@ __device__ __forceinline__ float head_pixels(const float* __restrict__ fp, const
     return group16_sum(acc);
 }
 
+// workgroup blk of the head's grid: layer k, image n, the image's b-th run of 64 pixels
+__device__ __forceinline__ void head_block(const HeadArgs& A, int blk, int& k, int& n, int& b) {
+    k = 0;
+#pragma unroll
+    for (int q = 1; q < CPN_LPIPS_LAYERS; ++q) k += (q < A.layers && blk >= A.off[q]) ? 1 : 0;
+    const int rem = blk - A.off[k];
+    n = rem / A.nblk[k];
+    b = rem - n * A.nblk[k];
+}
+
 __global__ __launch_bounds__(HEAD_NT) void lpips_head_kernel(HeadArgs A, float* __restrict__ partial) {
     __shared__ float red[GROUPS];
     const int tid = threadIdx.x, g = tid >> 4, j = tid & 15;
     const int blk = blockIdx.x;
-    int k = 0;
-#pragma unroll
-    for (int q = 1; q < CPN_LPIPS_LAYERS; ++q) k += (q < A.layers && blk >= A.off[q]) ? 1 : 0;
-    const int rem = blk - A.off[k];
-    const int n = rem / A.nblk[k], b = rem - n * A.nblk[k];
+    int k, n, b;
+    head_block(A, blk, k, n, b);
     const int C = A.C[k], P = A.P[k];
     const float* const fp = A.feat[k] + (size_t)n * P * C;
     const float* const ft = A.feat[k] + (size_t)(A.N + n) * P * C;
@@ -254,6 +282,142 @@ long long head_blocks(int N, int layers, const int* h, const int* w, HeadArgs* A
     return total;
 }
 
+// ------------------------------------------------------------------------------------------------------- head, adjoint
+struct HeadBwdArgs {
+    HeadArgs A;
+    float* dfeat[CPN_LPIPS_LAYERS];                         // (N, h, w, C) per layer
+};
+
+// df of the pixels g, g + 16, .. of a workgroup's 64 (include/coponerf_hip.h has the formula); coef = 2 g_n / P
+template <int NV>
+__device__ __forceinline__ void head_bwd_pixels(const float* __restrict__ fp, const float* __restrict__ ft,
+                                                const float* __restrict__ lin, float* __restrict__ df, int C, int P, int pix0,
+                                                int g, int j, float coef) {
+    f32x4 wv[NV];
+#pragma unroll
+    for (int i = 0; i < NV; ++i) wv[i] = *reinterpret_cast<const f32x4*>(lin + 4 * (j + GROUP * i));
+#pragma unroll 1
+    for (int s = 0; s < HEAD_PIX / GROUPS; ++s) {
+        const int pix = pix0 + g + GROUPS * s;
+        f32x4 a[NV], b[NV];
+        float sa, sb;
+        head_load<NV>(fp, ft, C, P, pix, j, a, b, sa, sb);
+        const float na = sqrtf(sa);
+        const float ra = 1.0f / (na + LPIPS_EPS), rb = 1.0f / (sqrtf(sb) + LPIPS_EPS);
+        float dot = 0.0f;
+#pragma unroll
+        for (int i = 0; i < NV; ++i)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+#pragma clang fp contract(off)
+                const float d = a[i][e] * ra - b[i][e] * rb;                    // the forward's difference, bit for bit
+                const float u = (wv[i][e] * d) * coef;
+                b[i][e] = u;                                                    // the target's value is spent
+                dot = __builtin_fmaf(u, a[i][e], dot);
+            }
+        dot = group16_sum(dot);
+        const float k2 = dot * ra * ra / na;
+        if (pix < P) {
+            float* const q = df + (size_t)pix * C + 4 * j;
+#pragma unroll
+            for (int i = 0; i < NV; ++i) {
+                f32x4 r;
+#pragma unroll
+                for (int e = 0; e < 4; ++e)                 // na == 0: every channel of the pixel is 0, and so is its gradient
+                    r[e] = na == 0.0f ? 0.0f : __builtin_fmaf(-k2, a[i][e], ra * b[i][e]);
+                *reinterpret_cast<f32x4*>(q + 4 * GROUP * i) = r;
+            }
+        }
+    }
+}
+
+__global__ __launch_bounds__(HEAD_NT) void lpips_head_bwd_kernel(HeadBwdArgs B, const float* __restrict__ gout) {
+    const HeadArgs& A = B.A;
+    const int tid = threadIdx.x, g = tid >> 4, j = tid & 15;
+    int k, n, b;
+    head_block(A, blockIdx.x, k, n, b);
+    const int C = A.C[k], P = A.P[k];
+    const float* const fp = A.feat[k] + (size_t)n * P * C;
+    const float* const ft = A.feat[k] + (size_t)(A.N + n) * P * C;
+    const float* const lin = A.lin[k];
+    float* const df = B.dfeat[k] + (size_t)n * P * C;
+    const int pix0 = b * HEAD_PIX;
+    const float coef = 2.0f * gout[n] / (float)P;
+    switch (C / 64) {                                       // the same in every lane of the workgroup
+        case 1: head_bwd_pixels<1>(fp, ft, lin, df, C, P, pix0, g, j, coef); break;
+        case 2: head_bwd_pixels<2>(fp, ft, lin, df, C, P, pix0, g, j, coef); break;
+        case 3: head_bwd_pixels<3>(fp, ft, lin, df, C, P, pix0, g, j, coef); break;
+        case 4: head_bwd_pixels<4>(fp, ft, lin, df, C, P, pix0, g, j, coef); break;
+        case 5: head_bwd_pixels<5>(fp, ft, lin, df, C, P, pix0, g, j, coef); break;
+        case 6: head_bwd_pixels<6>(fp, ft, lin, df, C, P, pix0, g, j, coef); break;
+        case 7: head_bwd_pixels<7>(fp, ft, lin, df, C, P, pix0, g, j, coef); break;
+        default: head_bwd_pixels<MAXV>(fp, ft, lin, df, C, P, pix0, g, j, coef); break;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------------- stem, adjoint
+constexpr int TAPS = 27;                                    // (ci, ky, kx); an odd LDS stride per pixel
+
+__global__ __launch_bounds__(NT) void lpips_stem_bwd_kernel(const float* __restrict__ dy, const float* __restrict__ yout,
+                                                            const float* __restrict__ pred, const float* __restrict__ w, int H,
+                                                            int W, float* __restrict__ dpred) {
+    __shared__ float sv[RH * RW * TAPS];                    // per pixel of the tile + halo: sum_co w[co][k] dy'[co], k < 27
+    const int tid = threadIdx.x;
+    const int img = blockIdx.z;
+    const int tx0 = blockIdx.x * TW, ty0 = blockIdx.y * TH;
+    const size_t img0 = (size_t)img * H * W;
+
+    const int cg = tid & 15, slot = tid >> 4;               // channels 4 cg .. 4 cg + 3; pixels slot, slot + 16, ..
+    float wr[4][TAPS];
+#pragma unroll
+    for (int q = 0; q < 4; ++q)
+#pragma unroll
+        for (int k = 0; k < TAPS; ++k) wr[q][k] = w[(4 * cg + q) * TAPS + k];
+
+#pragma unroll 1
+    for (int idx0 = 0; idx0 < RH * RW; idx0 += NT / 16) {
+        const int idx = idx0 + slot;                        // the same in all 16 lanes of a group; the shuffles are outside
+        const int ry = idx / RW, rx = idx - ry * RW;
+        const int gy = ty0 + ry - 1, gx = tx0 + rx - 1;
+        const bool in = idx < RH * RW && gy >= 0 && gy < H && gx >= 0 && gx < W;
+        f32x4 d = {0.f, 0.f, 0.f, 0.f};                     // a tap outside the image is absent
+        if (in) {
+            const size_t o = (img0 + (size_t)gy * W + gx) * STEM_C + 4 * cg;
+            d = *reinterpret_cast<const f32x4*>(dy + o);
+            const f32x4 yo = *reinterpret_cast<const f32x4*>(yout + o);
+#pragma unroll
+            for (int q = 0; q < 4; ++q) d[q] = yo[q] > 0.0f ? d[q] : 0.0f;     // the ReLU's mask, from its output
+        }
+#pragma unroll
+        for (int k = 0; k < TAPS; ++k) {
+            float v = wr[0][k] * d[0];
+            v = __builtin_fmaf(wr[1][k], d[1], v);
+            v = __builtin_fmaf(wr[2][k], d[2], v);
+            v = __builtin_fmaf(wr[3][k], d[3], v);
+            v = group16_sum(v);
+            if (cg == (k & 15) && idx < RH * RW) sv[idx * TAPS + k] = v;
+        }
+    }
+    __syncthreads();
+
+    const int py = tid / TW, px = tid - py * TW;            // one thread per pixel of the tile
+    const int gy = ty0 + py, gx = tx0 + px;
+    if (gy >= H || gx >= W) return;
+    const size_t o = (img0 + (size_t)gy * W + gx) * 3;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        const float scale = c == 0 ? 0.458f : (c == 1 ? 0.448f : 0.450f);
+        float acc = 0.0f;
+#pragma unroll
+        for (int ky = 0; ky < 3; ++ky)
+#pragma unroll
+            for (int kx = 0; kx < 3; ++kx)                  // output (y, x) fed input (y - ky + 1, x - kx + 1) through w[.., ky, kx]
+                acc += sv[((py - ky + 2) * RW + px - kx + 2) * TAPS + (c * 3 + ky) * 3 + kx];
+        const float p = pred[o + c];
+        dpred[o + c] = (p >= -1.0f && p <= 1.0f) ? acc / scale : 0.0f;          // torch.clamp's mask; false for a NaN
+    }
+}
+
 }  // namespace
 
 extern "C" int cpn_lpips_stem(const float* pred, const float* target, const float* w, const float* bias, int N, int H, int W,
@@ -299,5 +463,46 @@ extern "C" int cpn_lpips_head(const float* const* host_feat, const float* const*
     CPN_LAUNCH_CHECK("cpn_lpips_head");
     hipLaunchKernelGGL(lpips_finish_kernel, dim3(N), dim3(64), 0, (hipStream_t)stream, A, (const float*)partial, out, per_layer);
     CPN_LAUNCH_CHECK("cpn_lpips_head (finish)");
+    return 0;
+}
+
+extern "C" int cpn_lpips_head_bwd(const float* const* host_feat, const float* const* host_lin, const int* host_C, const int* host_h,
+                                  const int* host_w, int layers, int N, const float* g, float* const* host_dfeat, void* stream) {
+    CPN_REQUIRE(host_feat && host_lin && host_C && host_h && host_w && g && host_dfeat, CPN_E_ARG, "cpn_lpips_head_bwd: null pointer");
+    CPN_REQUIRE(layers >= 1 && layers <= CPN_LPIPS_LAYERS, CPN_E_SHAPE, "cpn_lpips_head_bwd: 1 .. %d layers, got %d", CPN_LPIPS_LAYERS,
+                layers);
+    HeadBwdArgs B = {};
+    const long long total = head_blocks(N, layers, host_h, host_w, &B.A);
+    CPN_REQUIRE(total > 0, CPN_E_SHAPE, "cpn_lpips_head_bwd: %d images and these map sizes are not one launch (need N >= 1, h, w >= 1)",
+                N);
+    for (int k = 0; k < layers; ++k) {
+        CPN_REQUIRE(host_feat[k] && host_lin[k] && host_dfeat[k], CPN_E_ARG, "cpn_lpips_head_bwd: null pointer in layer %d", k);
+        CPN_REQUIRE((((uintptr_t)host_feat[k] | (uintptr_t)host_lin[k] | (uintptr_t)host_dfeat[k]) & 15) == 0, CPN_E_ARG,
+                    "cpn_lpips_head_bwd: layer %d is not 16-byte aligned", k);
+        CPN_REQUIRE(host_C[k] >= 64 && host_C[k] <= 512 && host_C[k] % 64 == 0, CPN_E_SHAPE,
+                    "cpn_lpips_head_bwd: C must be a multiple of 64 up to 512, layer %d has %d", k, host_C[k]);
+        B.A.feat[k] = host_feat[k];
+        B.A.lin[k] = host_lin[k];
+        B.A.C[k] = host_C[k];
+        B.dfeat[k] = host_dfeat[k];
+    }
+    B.A.layers = layers;
+    B.A.N = N;
+    hipLaunchKernelGGL(lpips_head_bwd_kernel, dim3((unsigned)total), dim3(HEAD_NT), 0, (hipStream_t)stream, B, g);
+    CPN_LAUNCH_CHECK("cpn_lpips_head_bwd");
+    return 0;
+}
+
+extern "C" int cpn_lpips_stem_bwd(const float* dy, const float* y, const float* pred, const float* w, int N, int H, int W,
+                                  float* dpred, void* stream) {
+    CPN_REQUIRE(dy && y && pred && w && dpred, CPN_E_ARG, "cpn_lpips_stem_bwd: null pointer");
+    CPN_REQUIRE((((uintptr_t)dy | (uintptr_t)y) & 15) == 0, CPN_E_ARG, "cpn_lpips_stem_bwd: dy and y must be 16-byte aligned");
+    CPN_REQUIRE(N > 0 && H >= 16 && W >= 16, CPN_E_SHAPE, "cpn_lpips_stem_bwd: N >= 1 and H, W >= 16 as in cpn_lpips_stem (got %d, %d x %d)",
+                N, H, W);
+    CPN_REQUIRE(N <= 65535 && H <= 32768 && W <= 32768, CPN_E_SHAPE,
+                "cpn_lpips_stem_bwd: %d images of %d x %d are too many for one launch", N, H, W);
+    const dim3 grid(cpn_cdiv(W, TW), cpn_cdiv(H, TH), N);
+    hipLaunchKernelGGL(lpips_stem_bwd_kernel, grid, dim3(NT), 0, (hipStream_t)stream, dy, y, pred, w, H, W, dpred);
+    CPN_LAUNCH_CHECK("cpn_lpips_stem_bwd");
     return 0;
 }

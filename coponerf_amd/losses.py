@@ -4,6 +4,9 @@
   cycle_loss  0.01 x masked Huber of the two reprojections (loss_function.py:122-130)               LossConfig.cycle
   pose_loss   geodesic rotation distance + translation distance (loss_function.py:74-86, 132-134)  LossConfig.pose
   ssim_loss   the flow-warp SSIM of both directions (loss_function.py:19-60, 109-120)              LossConfig.ssim
+  lpips_loss  weight x mean LPIPS of the rendered 32 x 32 patches against the true ones              LossConfig.lpips
+              (not in the reference's loss: its loaders draw the patches with lpips=True, loss_function.py:11 imports `lpips`
+              and never calls it; the definition here is this package's)
 
 The cycle and pose terms are stock ops on (B, R, 2) and (B, 3, 3) tensors.  The SSIM term is csrc/ssim_warp.hip: 2 launches
 forward and 2 backward for both directions of every pair, differentiable in the two flows.  Nothing here reads a device value
@@ -26,10 +29,15 @@ WINDOW_SIZE, WINDOW_SIGMA = 11, 1.5
 
 @dataclasses.dataclass(frozen=True)
 class LossConfig:
-    """Which terms join the image loss: the reference's `--cycle --pose --ssim` switches."""
+    """Which terms join the image loss: the reference's `--cycle --pose --ssim` switches, and the patch LPIPS term's weight."""
     cycle: bool = False
     pose: bool = False
     ssim: bool = False
+    lpips: float = 0.0                                # weight of the patch LPIPS term; the reference has none to copy
+
+    def __post_init__(self):
+        if not self.lpips >= 0:                         # a negative weight, or NaN
+            raise ValueError(f"LossConfig: lpips is a weight >= 0 (0 switches the term off), got {self.lpips}")
 
 
 def gaussian_window(size: int = WINDOW_SIZE, sigma: float = WINDOW_SIGMA) -> torch.Tensor:
@@ -140,8 +148,50 @@ def image_loss(out_rgb: torch.Tensor, gt_rgb: torch.Tensor) -> torch.Tensor:
     return (zero(gt_rgb) - zero(out_rgb)).abs().mean()
 
 
-def loss_terms(cfg: LossConfig, model_input: Dict, out: Dict, gt_rgb: torch.Tensor) -> Dict[str, torch.Tensor]:
-    """The terms `cfg` switches on, by the reference's names; the step's loss is their sum (wrapper.py:109-123)."""
+def patch_from_rays(rgb: torch.Tensor, uv: torch.Tensor, patch: int) -> torch.Tensor:
+    """rgb (B, R, 3) and uv (B, R, 2) pixel coordinates (x, y) of R = patch^2 rays that cover a patch x patch window, in ANY
+    order -> (B, 3, patch, patch).  Ray r goes to row y - min y, column x - min x of its own pair: the result does not depend
+    on the order of the rays (TrainStep sorts them by tile).  Stock ops on B patch^2 elements, differentiable in rgb.
+    PRECONDITION: the rays of every pair do cover such a window (what mask = 1 says).  The host cannot check that without
+    reading uv back; for rays that do not, the index is clamped into the patch, so the result is a meaningless image (rays
+    overwrite each other, pixels stay 0) and never an out-of-range write."""
+    B, R, _ = rgb.shape
+    if R != patch * patch or tuple(uv.shape) != (B, R, 2):
+        raise ValueError(f"patch_from_rays: {patch} x {patch} patches need rgb (B, {patch * patch}, 3) and uv (B, {patch * patch}, 2), "
+                         f"got {tuple(rgb.shape)} and {tuple(uv.shape)}")
+    x, y = uv[..., 0].floor().long(), uv[..., 1].floor().long()
+    idx = (y - y.min(1, keepdim=True).values) * patch + (x - x.min(1, keepdim=True).values)      # (B, R): a permutation
+    idx = idx.clamp(0, R - 1)                                                   # no effect on a window; see the precondition
+    out = torch.zeros_like(rgb).scatter(1, idx[..., None].expand(-1, -1, 3), rgb)
+    return out.view(B, patch, patch, 3).permute(0, 3, 1, 2)
+
+
+def lpips_patch_loss(perceptual, rgb: torch.Tensor, gt_rgb: torch.Tensor, uv: torch.Tensor, mask,
+                     patch: Optional[int] = None) -> torch.Tensor:
+    """mean over the pairs with mask == 1 of perceptual.differentiable(patch of rgb, patch of gt_rgb); rgb, gt_rgb (B, 1, R, 3)
+    or (B, R, 3), uv likewise with 2.  mask (B,) lives on the HOST (shards.BatchAssembler drew it there): which pairs are
+    patches decides shapes, and a device mask would have to be read back.  No patch pair: an exact zero without a graph.
+    patch=None: the side whose square is the ray count (32 for the reference's 1 024 rays; BatchAssembler insists on
+    rays == patch^2)."""
+    if not torch.is_tensor(mask) or mask.is_cuda:
+        raise ValueError("lpips_patch_loss: query['mask'] must be a host tensor - keep it on the host, where the loader drew it "
+                         "(a device mask would cost a read-back every step)")
+    rows = [b for b, m in enumerate(mask.reshape(-1).tolist()) if m]
+    if not rows:
+        return torch.zeros((), dtype=torch.float32, device=rgb.device)
+    B = rgb.shape[0]
+    flat = lambda t: t.reshape(B, -1, t.shape[-1])
+    rgb, gt_rgb, uv = flat(rgb), flat(gt_rgb), flat(uv)
+    if patch is None:
+        patch = math.isqrt(rgb.shape[1])
+    if len(rows) != B:
+        rgb, gt_rgb, uv = (torch.stack([t[b] for b in rows]) for t in (rgb, gt_rgb, uv))      # rows are host integers
+    return perceptual.differentiable(patch_from_rays(rgb, uv, patch), patch_from_rays(gt_rgb.detach(), uv, patch)).mean()
+
+
+def loss_terms(cfg: LossConfig, model_input: Dict, out: Dict, gt_rgb: torch.Tensor, perceptual=None) -> Dict[str, torch.Tensor]:
+    """The terms `cfg` switches on, by the reference's names; the step's loss is their sum (wrapper.py:109-123).
+    perceptual: the lpips.LPIPS of the `lpips` term."""
     terms = {"img_loss": image_loss(out["rgb"], gt_rgb)}
     if cfg.ssim:
         flow: Sequence[torch.Tensor] = out["flow"]
@@ -156,4 +206,11 @@ def loss_terms(cfg: LossConfig, model_input: Dict, out: Dict, gt_rgb: torch.Tens
         rel, gt = out["rel_pose"], out["gt_rel_pose"]
         terms["pose_loss"] = W_POSE * (_geodesic(rel[:, :3, :3], gt[:, :3, :3])
                                        + torch.norm(rel[:, :3, 3] - gt[:, :3, 3], dim=-1).mean())
+    if cfg.lpips > 0:
+        q = model_input["query"]
+        if perceptual is None:
+            raise ValueError("LossConfig.lpips > 0 needs the network: TrainStep(..., perceptual=LPIPS...)")
+        if "mask" not in q:
+            raise ValueError("LossConfig.lpips > 0 needs query['mask'] (shards.BatchAssembler(lpips=True) makes it)")
+        terms["lpips_loss"] = cfg.lpips * lpips_patch_loss(perceptual, out["rgb"], gt_rgb, q["uv"], q["mask"])
     return terms

@@ -24,6 +24,13 @@ the result is sum_k d_k.
   csrc/lpips.hip  cpn_lpips_head   the whole distance head, all five layers and all images: two launches
 
 `forward` runs under `torch.no_grad()`, reads nothing on the host and touches no global backend flag.
+
+  LPIPS.differentiable(p, t) -> (N,)   the same distance as a training term: the gradient flows to p only.
+                                       The stem and the head are autograd Functions over cpn_lpips_stem / cpn_lpips_stem_bwd and
+                                       cpn_lpips_head / cpn_lpips_head_bwd; between them the library's convolutions and pools
+                                       run under autograd on the N predictions (data gradients only: the weights are buffers)
+                                       and under no_grad on the N targets.  A pixel of a tapped map whose channels are all 0
+                                       gets gradient 0 (this package's rule; float64 autograd of normalize_tensor gives NaN).
 """
 from __future__ import annotations
 
@@ -138,6 +145,11 @@ class LPIPS(torch.nn.Module):
         """relu1_1 (2N, 64, H, W), in the channels_last memory the stem leaves it in (or any other) -> the five tapped maps as
         contiguous (2N, h, w, C).  The convolutions run in NCHW: one copy of relu1_1 on the way in, one channels-last copy of
         every tapped map on the way out."""
+        return [f.permute(0, 2, 3, 1).contiguous() for f in self._trunk_nchw(x)]
+
+    def _trunk_nchw(self, x: torch.Tensor) -> List[torch.Tensor]:
+        """The five tapped maps as the convolutions leave them, (n, C, h, w) contiguous.  Runs under autograd as it stands: every
+        in-place ReLU acts on a convolution's fresh output."""
         x = x.contiguous()
         taps = []
         for j, block in enumerate(BLOCKS):
@@ -147,7 +159,7 @@ class LPIPS(torch.nn.Module):
                 if i == 0:
                     continue                                # conv1_1 is the stem kernel's
                 x = F.relu_(F.conv2d(x, getattr(self, f"w{i}"), getattr(self, f"b{i}"), padding=1))
-            taps.append(x.permute(0, 2, 3, 1).contiguous())
+            taps.append(x)
         return taps
 
     def stem(self, p: torch.Tensor, t: torch.Tensor) -> torch.Tensor:
@@ -162,8 +174,7 @@ class LPIPS(torch.nn.Module):
         """taps[k] (2N, h_k, w_k, C_k) fp32, predictions first -> (N,), and (N, 5) with per_layer."""
         return lpips_head(taps, [getattr(self, f"lin{k}") for k in range(len(taps))], N, per_layer)
 
-    @torch.no_grad()
-    def forward(self, p: torch.Tensor, t: torch.Tensor, per_layer: bool = False):
+    def _check(self, p: torch.Tensor, t: torch.Tensor) -> None:
         if not (torch.is_tensor(p) and torch.is_tensor(t)):
             raise TypeError("LPIPS: p and t must be tensors")
         if not (p.is_cuda and t.is_cuda):
@@ -177,28 +188,48 @@ class LPIPS(torch.nn.Module):
         N, _, H, W = p.shape
         if H < MIN_SIDE or W < MIN_SIDE:
             raise ValueError(f"LPIPS: four 2 x 2 pools need H, W >= {MIN_SIDE}, got {H} x {W}")
+
+    @torch.no_grad()
+    def forward(self, p: torch.Tensor, t: torch.Tensor, per_layer: bool = False):
+        self._check(p, t)
         with torch.cuda.device(p.device):
             x = self.stem(self._channels_last(p), self._channels_last(t))
-            return self.head(self.trunk(x), N, per_layer)
+            return self.head(self.trunk(x), p.shape[0], per_layer)
+
+    # ------------------------------------------------------------------------------------------------ as a training term
+    def differentiable(self, p: torch.Tensor, t: torch.Tensor) -> torch.Tensor:
+        """forward's inputs, checks and values (within its float64 bounds; not its bits: the library may pick another
+        algorithm for N images than for 2N) with a gradient to p.  t gets none.  Reads nothing on the host."""
+        self._check(p, t)
+        with torch.cuda.device(p.device):
+            yp, yt = _Stem.apply(self._channels_last(p), self._channels_last(t.detach()), self.stem_weight, self.stem_bias)
+            taps_p = self._trunk_nchw(yp.permute(0, 3, 1, 2))
+            with torch.no_grad():
+                taps_t = self._trunk_nchw(yt.permute(0, 3, 1, 2))
+            return _Head.apply([getattr(self, f"lin{k}") for k in range(LAYERS)], taps_t, *taps_p)
+
+
+def _head_args(who: str, taps: List[torch.Tensor], lins: List[torch.Tensor], N: int):
+    """The checks and the host arrays the head and its adjoint share: (layers, device, the pointer-array type, (C, h, w) int arrays)."""
+    L = len(taps)
+    if not 1 <= L <= LAYERS or len(lins) != L:
+        raise ValueError(f"{who}: 1 .. {LAYERS} maps and as many lin weights, got {L} and {len(lins)}")
+    dev = taps[0].device
+    for k, (f, l) in enumerate(zip(taps, lins)):
+        if not (f.is_cuda and l.is_cuda) or f.device != dev or l.device != dev:
+            raise RuntimeError(f"{who} runs on one HIP device only (coponerf_amd has no non-HIP compute path)")
+        if f.dtype != torch.float32 or l.dtype != torch.float32 or f.dim() != 4 or f.shape[0] != 2 * N or not f.is_contiguous():
+            raise ValueError(f"{who}: map {k} must be a contiguous fp32 (2N, h, w, C), got {tuple(f.shape)} {f.dtype}")
+        if tuple(l.shape) != (f.shape[3],) or not l.is_contiguous():
+            raise ValueError(f"{who}: lin {k} must be ({f.shape[3]},), got {tuple(l.shape)}")
+    ints = ctypes.c_int * L
+    return L, dev, ctypes.c_void_p * L, tuple(ints(*[f.shape[d] for f in taps]) for d in (3, 1, 2))
 
 
 def lpips_head(taps: List[torch.Tensor], lins: List[torch.Tensor], N: int, per_layer: bool = False):
     """csrc/lpips.hip's distance head alone: taps[k] (2N, h_k, w_k, C_k) contiguous fp32 on the device, predictions first,
     lins[k] (C_k).  Returns (N,) fp32, and the (N, 5) per-layer terms with per_layer.  Two launches, no host read."""
-    L = len(taps)
-    if not 1 <= L <= LAYERS or len(lins) != L:
-        raise ValueError(f"lpips_head: 1 .. {LAYERS} maps and as many lin weights, got {L} and {len(lins)}")
-    dev = taps[0].device
-    for k, (f, l) in enumerate(zip(taps, lins)):
-        if not (f.is_cuda and l.is_cuda) or f.device != dev or l.device != dev:
-            raise RuntimeError("lpips_head runs on one HIP device only (coponerf_amd has no non-HIP compute path)")
-        if f.dtype != torch.float32 or l.dtype != torch.float32 or f.dim() != 4 or f.shape[0] != 2 * N or not f.is_contiguous():
-            raise ValueError(f"lpips_head: map {k} must be a contiguous fp32 (2N, h, w, C), got {tuple(f.shape)} {f.dtype}")
-        if tuple(l.shape) != (f.shape[3],) or not l.is_contiguous():
-            raise ValueError(f"lpips_head: lin {k} must be ({f.shape[3]},), got {tuple(l.shape)}")
-    ints = ctypes.c_int * L
-    ptrs = ctypes.c_void_p * L
-    hs, ws, cs = ints(*[f.shape[1] for f in taps]), ints(*[f.shape[2] for f in taps]), ints(*[f.shape[3] for f in taps])
+    L, dev, ptrs, (cs, hs, ws) = _head_args("lpips_head", taps, lins, N)
     n = _hip.lib().cpn_lpips_head_scratch(N, L, hs, ws)
     if n <= 0:
         raise ValueError(f"lpips_head: {N} images with maps {[tuple(f.shape[1:3]) for f in taps]} are not one launch")
@@ -209,3 +240,70 @@ def lpips_head(taps: List[torch.Tensor], lins: List[torch.Tensor], N: int, per_l
         _hip.call("cpn_lpips_head", ptrs(*[f.data_ptr() for f in taps]), ptrs(*[l.data_ptr() for l in lins]), cs, hs, ws, L, N,
                   partial.data_ptr(), out.data_ptr(), layers.data_ptr() if per_layer else None, _hip.stream_handle())
     return (out, layers) if per_layer else out
+
+
+class _Stem(torch.autograd.Function):
+    """cpn_lpips_stem on (N, H, W, 3) channels-last images -> relu1_1 of the predictions and of the targets, both (N, H, W, 64)
+    halves of the kernel's one output.  Differentiable in the predictions (cpn_lpips_stem_bwd)."""
+
+    @staticmethod
+    def forward(ctx, p, t, weight, bias):
+        N, H, W, _ = p.shape
+        out = torch.empty(2 * N, H, W, 64, dtype=torch.float32, device=p.device)
+        _hip.call("cpn_lpips_stem", p.data_ptr(), t.data_ptr(), weight.data_ptr(), bias.data_ptr(), N, H, W, out.data_ptr(),
+                  _hip.stream_handle())
+        yp, yt = out[:N], out[N:]
+        ctx.save_for_backward(p, yp, weight)
+        ctx.mark_non_differentiable(yt)
+        return yp, yt
+
+    @staticmethod
+    def backward(ctx, dyp, _dyt):
+        p, yp, weight = ctx.saved_tensors
+        N, H, W, _ = p.shape
+        dy = dyp.contiguous()
+        dp = torch.empty_like(p)
+        with torch.cuda.device(p.device):
+            _hip.call("cpn_lpips_stem_bwd", dy.data_ptr(), yp.data_ptr(), p.data_ptr(), weight.data_ptr(), N, H, W, dp.data_ptr(),
+                      _hip.stream_handle())
+        return dp, None, None, None
+
+
+class _Head(torch.autograd.Function):
+    """(N,) distances of the tapped maps as the convolutions leave them: taps_p[k], taps_t[k] (N, C_k, h_k, w_k).  Forward: one
+    channels-last (2N, h, w, C) buffer per layer, filled by one copy per half, and cpn_lpips_head; backward: cpn_lpips_head_bwd,
+    its channels-last result copied to the convolutions' layout.  Differentiable in taps_p only."""
+
+    @staticmethod
+    def forward(ctx, lins, taps_t, *taps_p):
+        N = taps_p[0].shape[0]
+        both = []
+        for fp, ft in zip(taps_p, taps_t):
+            f = torch.empty(2 * N, fp.shape[2], fp.shape[3], fp.shape[1], dtype=torch.float32, device=fp.device)
+            f[:N].copy_(fp.permute(0, 2, 3, 1))
+            f[N:].copy_(ft.permute(0, 2, 3, 1))
+            both.append(f)
+        ctx.save_for_backward(*both, *lins)
+        return lpips_head(both, list(lins), N)
+
+    @staticmethod
+    def backward(ctx, g):
+        L = len(ctx.saved_tensors) // 2
+        both, lins = ctx.saved_tensors[:L], ctx.saved_tensors[L:]
+        return (None, None) + tuple(d.permute(0, 3, 1, 2).contiguous() for d in lpips_head_bwd(both, lins, g))
+
+
+def lpips_head_bwd(taps: List[torch.Tensor], lins: List[torch.Tensor], g: torch.Tensor) -> List[torch.Tensor]:
+    """csrc/lpips.hip's adjoint of the distance head alone: taps and lins as lpips_head takes them, g (N,) the gradient of
+    every image's distance.  Returns the gradients of the prediction halves, (N, h_k, w_k, C_k) fp32.  One launch, no host read.
+    A pixel whose prediction vector is all zeros gets 0 (include/coponerf_hip.h)."""
+    N = g.shape[0]
+    L, dev, ptrs, (cs, hs, ws) = _head_args("lpips_head_bwd", taps, lins, N)
+    g = g.contiguous()
+    if not g.is_cuda or g.device != dev or g.dtype != torch.float32 or g.dim() != 1:
+        raise ValueError(f"lpips_head_bwd: g must be fp32 (N,) on {dev}, got {g.dtype} {tuple(g.shape)} on {g.device}")
+    grads = [torch.empty(N, *f.shape[1:], dtype=torch.float32, device=dev) for f in taps]
+    with torch.cuda.device(dev):
+        _hip.call("cpn_lpips_head_bwd", ptrs(*[f.data_ptr() for f in taps]), ptrs(*[l.data_ptr() for l in lins]), cs, hs, ws, L, N,
+                  g.data_ptr(), ptrs(*[d.data_ptr() for d in grads]), _hip.stream_handle())
+    return grads

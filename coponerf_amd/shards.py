@@ -110,11 +110,22 @@ def crop_window(Hs: int, Ws: int) -> Tuple[int, int, int]:
 
 
 class BatchAssembler:
-    """Pinned uint8 staging for `batch` samples + the device tensors of the model's input dict."""
+    """Pinned uint8 staging for `batch` samples + the device tensors of the model's input dict.
 
-    def __init__(self, batch: int, Hs: int, Ws: int, rays: int, device: torch.device):
+    lpips=True is the loaders' `lpips=True` (realestate10k_dataio.py:364-385, acid_dataio.py:340-345): per sample one bit
+    decides between a `patch` x `patch` window of the query image, row-major, with query['mask'] = 1, and scattered rays with
+    mask = 0 (losses.LossConfig.lpips trains against the patches).  The mask is drawn on the host and stays there."""
+
+    def __init__(self, batch: int, Hs: int, Ws: int, rays: int, device: torch.device, lpips: bool = False, patch: int = 32):
         self.B, self.Hs, self.Ws, self.R, self.dev = batch, Hs, Ws, rays, device
         self.y0, self.x0, self.side = crop_window(Hs, Ws)
+        self.lpips, self.patch = bool(lpips), int(patch)
+        if self.lpips:
+            if rays != self.patch * self.patch:         # the reference hard-codes 1 024 rays for both branches
+                raise ValueError(f"BatchAssembler(lpips=True): rays must be patch^2 = {self.patch * self.patch}, got {rays}")
+            if not 0 < self.patch < self.side:
+                raise ValueError(f"BatchAssembler(lpips=True): a {self.patch} x {self.patch} patch does not fit a crop of side {self.side}")
+        self.mask = torch.zeros(batch, dtype=torch.int64) if self.lpips else None
         pin = device.type == "cuda"
         self.frames = torch.empty(batch, 3, Hs, Ws, 3, dtype=torch.uint8, pin_memory=pin)
         self.ray_pix = torch.empty(batch, rays, dtype=torch.int32, pin_memory=pin)
@@ -136,6 +147,15 @@ class BatchAssembler:
             self.frames[b, j].numpy()[...] = shard.frames[fid]                  # mmap page cache -> pinned staging, one copy
             self.small[b, j, :16] = torch.from_numpy(np.asarray(shard.c2w[fid]).reshape(16).copy())
             self.small[b, j, 16:] = torch.from_numpy(sample_intrinsics(shard.intrinsics[fid], self.Hs, self.Ws).reshape(16))
+        if self.lpips and int(rng.integers(0, 2)):                              # dataio.py:366-377: a patch, row-major
+            P = self.patch
+            x0, y0 = int(rng.integers(0, S - P)), int(rng.integers(0, S - P))
+            pix = (y0 + np.arange(P))[:, None] * S + (x0 + np.arange(P))[None, :]
+            self.ray_pix[b] = torch.from_numpy(pix.reshape(-1).astype(np.int32))
+            self.mask[b] = 1
+            return
+        if self.lpips:
+            self.mask[b] = 0
         self.ray_pix[b] = torch.from_numpy(rng.permutation(S * S)[:self.R].astype(np.int32))          # dataio.py:385-390
 
     def to_model_input(self) -> Tuple[Dict, Dict]:
@@ -155,5 +175,7 @@ class BatchAssembler:
         uv = torch.stack((pix % S, pix // S), dim=-1).float().view(B, 1, R, 2)               # (x = column, y = row)
         mat = lambda j, k: small[:, j, 16 * k:16 * k + 16].reshape(B, 1, 4, 4)
         query = {"rgb": qrgb, "cam2world": mat(2, 0), "intrinsics": mat(2, 1), "uv": uv}
+        if self.lpips:
+            query["mask"] = self.mask.clone()                                   # (B,) int64 on the HOST: fill() drew it there
         context = {"rgb": ctx, "cam2world": torch.cat((mat(0, 0), mat(1, 0)), 1), "intrinsics": torch.cat((mat(0, 1), mat(1, 1)), 1)}
         return {"query": query, "context": context}, query

@@ -43,12 +43,15 @@ class _LazyFlag:
 class TrainStep:
     def __init__(self, model: torch.nn.Module, lr: float = 5e-5 * 4, clip_grad: float = 1.0,
                  bucket_bytes: int = 64 << 20, group=None, force_collectives: bool = False, exchange: bool = True,
-                 loss: LossConfig = LossConfig()):
-        """loss: which terms join the image loss (losses.LossConfig: the reference's --cycle / --pose / --ssim).
+                 loss: LossConfig = LossConfig(), perceptual=None):
+        """loss: which terms join the image loss (losses.LossConfig: the reference's --cycle / --pose / --ssim, and the weight
+        of the patch LPIPS term).  perceptual: the lpips.LPIPS that term runs (on the model's device); the first step raises
+        if the weight is positive without it, or without query['mask'].
         exchange=False: never exchange gradients, even inside an initialised process group (every rank for itself: the
         single-GPU step measured beside the N-rank one, bench.py `ms_per_step_without_exchange`)."""
         self.model = model
         self.loss_cfg = loss
+        self.perceptual = perceptual
         self.exchange_enabled = bool(exchange)
         self.params = [p for p in model.parameters()]
         # train.py:102-105 (both groups share lr); where the parameters live on the GPU the update of all 636 tensors is ONE
@@ -140,7 +143,7 @@ class TrainStep:
                 self._adapt_grad_scale(bool(self._pending.popleft()))
         e0 = self._ev() if timed else None
         out = self.model(model_input, val=False)
-        terms = loss_terms(self.loss_cfg, model_input, out, gt_rgb)
+        terms = loss_terms(self.loss_cfg, model_input, out, gt_rgb, self.perceptual)
         loss = terms["img_loss"]
         for name, term in terms.items():                                          # wrapper.py:109-123: the sum of the terms
             if name != "img_loss":

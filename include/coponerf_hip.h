@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define CPN_ABI_VERSION 12   /* cpn_attend_units (round 7), cpn_ssim_warp* (round 8), cpn_image_metrics* (round 9), summaries.hip (round 10), lpips.hip (round 11), novel_views.hip (round 12) and epipolar.hip (round 13) are additive - symbols added, none altered: the version stays */
+#define CPN_ABI_VERSION 12   /* cpn_attend_units (round 7), cpn_ssim_warp* (round 8), cpn_image_metrics* (round 9), summaries.hip (round 10), lpips.hip (round 11), novel_views.hip (round 12), epipolar.hip (round 13) and cpn_lpips_*_bwd (round 14) are additive - symbols added, none altered: the version stays */
 
 #define CPN_E_ARG   (-1)   /* bad argument (null pointer, size, alignment) */
 #define CPN_E_SHAPE (-2)   /* shape not supported by the compiled tiles    */
@@ -734,6 +734,34 @@ int cpn_lpips_stem(const float* pred, const float* target, const float* w, const
 int cpn_lpips_head_scratch(int N, int layers, const int* host_h, const int* host_w);
 int cpn_lpips_head(const float* const* host_feat, const float* const* host_lin, const int* host_C, const int* host_h,
                    const int* host_w, int layers, int N, float* partial, float* out, float* per_layer, void* stream);
+
+/* ==== LPIPS as a training term: the adjoints of the two kernels above (round 14) ========================================
+ * For 32 x 32-patch LPIPS fine-tuning (the reference's loaders draw the patches with lpips=True and its loss never uses
+ * them).  Gradients flow to the PREDICTION only; targets carry none.  The symbols are additive: the ABI version stays.
+ * cpn_lpips_head_bwd: the adjoint of cpn_lpips_head with respect to the prediction maps, all layers and images in ONE launch.
+ *   host_feat, host_lin, host_C, host_h, host_w, layers, N: as cpn_lpips_head takes them (same limits, same alignment).
+ *   g (N) fp32: the gradient of each image's distance.  host_dfeat[k] (N, h_k, w_k, C_k) fp32, channels last, 16-byte aligned:
+ *   written whole.  Per layer with P = h w pixels and per pixel, f the prediction's vector and t the target's:
+ *     s = sqrt(sum_c f_c^2), r = 1 / (s + 1e-10f), a = f r, b likewise from t, q_c = lin_c (a_c - b_c), u_c = q_c (2 g_n / P),
+ *     df_j = r u_j - ((sum_c u_c f_c) r r / s) f_j.
+ *   THE RULE AT s == 0 IS THIS LIBRARY'S: df = 0 for the whole pixel.  (Autograd of normalize_tensor gives NaN there, from
+ *   the root's derivative at 0; the ReLU in front of every tapped map passes no gradient to a pixel whose channels are all
+ *   0, and a NaN would poison the data gradient of the convolution behind it.)  A zero vector in the target alone is no
+ *   special case (b = 0).  16 lanes per pixel, 16-byte loads, every feature value of both maps read once, both sums round the
+ *   16 lanes.  No atomics: bit-reproducible, and image n's gradient does not depend on N.
+ * cpn_lpips_stem_bwd: the adjoint of cpn_lpips_stem with respect to pred, ONE launch.  dy (N, H, W, 64) fp32: the gradient
+ *   of relu1_1 of the predictions; y (N, H, W, 64): cpn_lpips_stem's own output for them (the first N images of its `out`);
+ *   pred (N, H, W, 3) and w (64, 3, 3, 3) as the forward took them; dy, y 16-byte aligned.  dpred (N, H, W, 3) fp32:
+ *     dpred[ci](y, x) = [-1 <= pred <= 1] (1 / scale_ci) sum_{ky, kx} sum_co w[co, ci, ky, kx] dy'[co](y - ky + 1, x - kx + 1),
+ *   dy' = dy where y_out > 0 and 0 elsewhere (a NaN y_out gives 0); taps outside the image are absent; the round trip
+ *   through [0, 1] has derivative 1; the clamp's mask is torch's: inclusive bounds, exactly 0 outside them and for a NaN
+ *   pred.  Per (ci, ky, kx) the 64 channels are 4 FMAs in a lane (channels 4 j .. 4 j + 3 in order) and a butterfly round 16
+ *   lanes; the nine taps are then added in (ky, kx) order and the sum divided by scale_ci: a fixed order, bit-reproducible.
+ *   H, W >= 16 as in the forward (CPN_E_SHAPE otherwise).                                                                  */
+int cpn_lpips_head_bwd(const float* const* host_feat, const float* const* host_lin, const int* host_C, const int* host_h,
+                       const int* host_w, int layers, int N, const float* g, float* const* host_dfeat, void* stream);
+int cpn_lpips_stem_bwd(const float* dy, const float* y, const float* pred, const float* w, int N, int H, int W, float* dpred,
+                       void* stream);
 
 /* ==== novel views from two photos: fit the photos, the camera path, the frames (round 12) ================================
  * What a caller of test.py does by hand around forward(val=True).  The symbols are additive: the ABI version stays.
