@@ -13,6 +13,7 @@
 //   pack_frames_kernel        cpn_pack_frames: one thread per output byte of a frame: the render's fp32 rgb to uint8 and, beside
 //                             it, the `jet` panel of depth_ray / 10 (jet.h's lookup rule), written into the output tensor.
 #include "common.h"
+#include "byte_pack.h"
 #include "jet.h"
 
 #include <math.h>
@@ -152,11 +153,6 @@ __global__ __launch_bounds__(NT) void camera_path_kernel(const float* __restrict
     o[15] = 1.f;
 }
 
-
-__device__ __forceinline__ uint8_t to_byte(float v) {      // v in grey levels; NaN -> 0
-    if (!(v == v)) return 0;
-    return (uint8_t)rintf(fminf(fmaxf(v, 0.f), 255.f));
-}
 
 // out (B, h, wo, 3) bytes, wo = w or 2 w: [rgb | jet(depth / 10)]
 __global__ __launch_bounds__(NT) void pack_frames_kernel(const float* __restrict__ rgb, const float* __restrict__ depth,

@@ -1,6 +1,7 @@
 // The fixed-order sums of partial results, once each.  Two keep the training gradients bit-reproducible: the reducers of
 // ufc_wgrad.hip and ufc_strided_bwd.hip (sum_partials_16x64), of wgrad_f32.hip and wgrad_tall.hip (sum_slabs_f32x4).  The third
 // is the float64 finish of the image-side units (sum_partials_f64: image_metrics.hip, ssim_warp.hip, lpips.hip, summaries.hip).
+// The fourth adds the block counts of the stream compaction (sum_counts_256: point_cloud.hip) in the same thread order.
 #pragma once
 #include "common.h"
 
@@ -57,6 +58,16 @@ __device__ __forceinline__ void sum_partials_f64(const float* __restrict__ p, in
     }
 #pragma unroll
     for (int k = 0; k < N; ++k) s[k] = wave_sum(s[k]);
+}
+
+// The sum of n integer block counts by a workgroup of 256 threads, sum_partials_f64's walk on integers: thread t adds
+// p[t], p[t + 256], p[t + 512], ... in ascending order, block256_sum adds the threads.  One pass of the walk covers 256 counts.
+// Returned in every thread; must be called by all 256 threads, once per kernel (waves4_sum's LDS).
+__device__ __forceinline__ int sum_counts_256(const int* __restrict__ p, int n) {
+    int s[1] = {0};
+    for (int i = threadIdx.x; i < n; i += 256) s[0] += p[i];
+    block256_sum(s);
+    return s[0];
 }
 
 // Element i of the sum of nslab slabs of n4 16-byte vectors each, in slab order: part[i] + part[n4 + i] + part[2 n4 + i] ...

@@ -261,7 +261,7 @@ def pack_frames(rgb: torch.Tensor, out: torch.Tensor, depth: Optional[torch.Tens
 @torch.no_grad()
 def render_path(model, model_input: Dict, t, sway: float = 0.0, depth: bool = False,
                 window: Optional[Sequence[int]] = None, return_rgb: bool = False, turns: float = 2.0,
-                announce: bool = True) -> Dict[str, torch.Tensor]:
+                announce: bool = True, return_depth: bool = False) -> Dict[str, torch.Tensor]:
     """Views along camera_path(rel_pose, t, sway, turns) of the pair in model_input (prepare_pair's dict, or any dict
     forward(val=True) takes: with val=True the geometry uses the estimated pose, not the context poses).
 
@@ -273,8 +273,10 @@ def render_path(model, model_input: Dict, t, sway: float = 0.0, depth: bool = Fa
     window=(y0, x0, h, w) renders that rectangle of the pixel grid only (tiles); None the whole size x size image.
     Returns a dict of device tensors: `frames` (K, B, h, w, 3) uint8, or (K, B, h, 2 w, 3) with depth=True (the right half is
     the `jet` panel of depth_ray / 10); `poses` (K, B, 4, 4); `rel_pose` (B, 4, 4) as get_z estimated it; with
-    return_rgb=True also `rgb` (K, B, h * w, 3) fp32 as forward returned it.  Nothing is read on the host here; forward's own
-    contractual copy of `pixel_val` to pinned host memory stays (asynchronous, on a stream of its own)."""
+    return_rgb=True also `rgb` (K, B, h * w, 3) fp32 as forward returned it; with return_depth=True also `depth` (K, B, h * w)
+    fp32, forward's `depth_ray`, and `valid` (K, B, h * w) uint8, 1 where forward's `valid_mask` is not zero (the ray meets
+    at least one of the two views) - what coponerf_amd.point_cloud starts from.  Nothing is read on the host here; forward's
+    own contractual copy of `pixel_val` to pinned host memory stays (asynchronous, on a stream of its own)."""
     ctx, qry = model_input["context"], model_input["query"]
     S = int(ctx["rgb"].shape[2])
     B = int(ctx["rgb"].shape[0])
@@ -297,6 +299,8 @@ def render_path(model, model_input: Dict, t, sway: float = 0.0, depth: bool = Fa
               for k in range(K)]
     frames = torch.empty(K, B, h, 2 * w if depth else w, 3, dtype=torch.uint8, device=dev)
     rgbs = torch.empty(K, B, R, 3, dtype=torch.float32, device=dev) if return_rgb else None
+    depths = torch.empty(K, B, R, dtype=torch.float32, device=dev) if return_depth else None
+    valids = torch.empty(K, B, R, dtype=torch.uint8, device=dev) if return_depth else None
     for k in range(K):
         if announce and k + 1 < K:
             model.prepare_next(inputs[k + 1], z, rel_pose, flow)
@@ -305,7 +309,12 @@ def render_path(model, model_input: Dict, t, sway: float = 0.0, depth: bool = Fa
         pack_frames(rgb, frames[k], out["depth_ray"].contiguous() if depth else None)
         if return_rgb:
             rgbs[k].copy_(rgb.view(B, R, 3))
+        if return_depth:
+            depths[k].copy_(out["depth_ray"].view(B, R))
+            valids[k].copy_(out["valid_mask"].view(B, R) != 0)
     result = {"frames": frames, "poses": poses, "rel_pose": rel_pose}
     if return_rgb:
         result["rgb"] = rgbs
+    if return_depth:
+        result["depth"], result["valid"] = depths, valids
     return result

@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define CPN_ABI_VERSION 12   /* cpn_attend_units (round 7), cpn_ssim_warp* (round 8), cpn_image_metrics* (round 9), summaries.hip (round 10), lpips.hip (round 11), novel_views.hip (round 12), epipolar.hip (round 13) and cpn_lpips_*_bwd (round 14) are additive - symbols added, none altered: the version stays */
+#define CPN_ABI_VERSION 12   /* cpn_attend_units (round 7), cpn_ssim_warp* (round 8), cpn_image_metrics* (round 9), summaries.hip (round 10), lpips.hip (round 11), novel_views.hip (round 12), epipolar.hip (round 13), cpn_lpips_*_bwd (round 14) and point_cloud.hip (round 15) are additive - symbols added, none altered: the version stays */
 
 #define CPN_E_ARG   (-1)   /* bad argument (null pointer, size, alignment) */
 #define CPN_E_SHAPE (-2)   /* shape not supported by the compiled tiles    */
@@ -822,6 +822,44 @@ int cpn_epipolar_lines(const float* intrinsics, const float* rel_pose, const flo
 int cpn_epipolar_panels(const float* rgb, const int* points, const float* colors, const int* ends, const uint8_t* valid, int B,
                         int S, int P, int radius, int thickness, float* out, void* stream);
 int cpn_mask_contour(const uint8_t* overlay, const uint8_t* mask, int N, int S, uint8_t* out, void* stream);
+
+/* ==== a fused coloured point cloud from the depth of K rendered views (round 15) ========================================
+ * What a caller does by hand with depth_ray (models/CoPoNeRF.py:509-540: the z-depth, in the query camera, of the 3-D point of
+ * the ray's strongest sample, clamped to [0, 10]) to get geometry out of two photos.  The symbols are additive: the ABI
+ * version stays.  The validity rule and the vote rule below are THIS LIBRARY'S definitions, not the reference's.
+ * Shared by the first two: the pixel grid is the window (y0, x0, h, w) of an S x S image, pixel (r, c) of it is
+ *   (u, v) = (x0 + c, y0 + r) and its ray ((u - cx) / fx, (v - cy) / fy, 1): batch_project_to_other_img's convention, no
+ *   half-pixel offset.  intrinsics (B, 4, 4) fp32 (fx, fy, cx, cy = entries 0, 5, 2, 6), one camera model per pair for all K
+ *   views; poses (K, B, 4, 4) fp32, camera to reference, rigid (cpn_camera_path's output); the inverse is [R^T | -R^T t].
+ *   depth (K, B, h w) fp32; a depth is VALID iff it is finite and 0 < d < 10 - both clamp ends count as saturated.  float64
+ *   from the fp32 inputs, one rounding per operation, sums left to right, ONE rounding to fp32 at the store.
+ *   1 <= K <= 255, K B h w < 2^31, the window inside the grid (CPN_E_SHAPE otherwise).  One launch each, no atomics.
+ * cpn_depth_points: xyz (K, B, h w, 3) fp32 = pose . (d . ray), the point in the reference frame; three NaN where d is invalid.
+ * cpn_depth_votes: forward-backward consistency (the fusion rule of multi-view stereo).  For a valid pixel p of view a with
+ *   X = pose_a . (d_a . ray(p)) and every other view b in ascending order:  Y = pose_b^-1 X, not consistent if Y_z <= 0;
+ *   q = (fx Y_x / Y_z + cx, fy Y_y / Y_z + cy); in window coordinates (q_x - x0, q_y - y0) the four bilinear taps
+ *   (floor, floor + 1 per axis) must lie inside the window and all be valid, else not consistent;
+ *   d_b = bilinear(depth_b, q) (rows blended after columns), X' = pose_b . (d_b . ray(q)), Y' = pose_a^-1 X', not consistent
+ *   if Y'_z <= 0; p' = proj(Y');  consistent iff |p' - p|_2 <= px_tol and |Y'_z - d_a| <= rel_tol d_a.
+ *   votes (K, B, h w) bytes = the number of consistent b, 0 for an invalid pixel; depth_fused (K, B, h w) fp32 =
+ *   (d_a + sum of Y'_z over the consistent b, in view order) / (1 + votes), NaN where d_a is invalid.  px_tol, rel_tol >= 0.
+ * cpn_compact_points: deterministic stream compaction in TWO launches.  keep (K, B, h w) bytes (non-zero = selected), xyz
+ *   (K, B, h w, 3) fp32, rgb (K, B, h w, 3) fp32 in [-1, 1] -> per pair b, with cap = K h w: out_xyz (B, cap, 3) fp32, out_rgb
+ *   (B, cap, 3) bytes by cpn_pack_frames' rule (rint(min(max((x + 1) * 127.5, 0), 255)), NaN -> 0) and count (B) int32: the
+ *   selected points in ascending (view, row, column) order; rows count[b] and beyond are left untouched.  A workgroup owns
+ *   CPN_COMPACT_TILE consecutive elements of a pair; the first launch writes its count to scratch
+ *   (cpn_compact_points_scratch(K, B, h, w) ints, 0 for a shape the kernels do not take), the second adds the counts before
+ *   its own with 256 threads, CPN_COMPACT_FINISH counts per pass in a fixed order, and writes.  No atomics: two runs give the
+ *   same bytes.  B <= 65535 here.                                                                                          */
+#define CPN_COMPACT_TILE 1024
+#define CPN_COMPACT_FINISH 256
+int cpn_depth_points(const float* depth, const float* poses, const float* intrinsics, int K, int B, int S, int y0, int x0, int h,
+                     int w, float* xyz, void* stream);
+int cpn_depth_votes(const float* depth, const float* poses, const float* intrinsics, int K, int B, int S, int y0, int x0, int h,
+                    int w, double px_tol, double rel_tol, uint8_t* votes, float* depth_fused, void* stream);
+int cpn_compact_points_scratch(int K, int B, int h, int w);
+int cpn_compact_points(const uint8_t* keep, const float* xyz, const float* rgb, int K, int B, int h, int w, int* scratch,
+                       float* out_xyz, uint8_t* out_rgb, int* count, void* stream);
 
 #ifdef __cplusplus
 }
