@@ -1,0 +1,435 @@
+// Two photos in, their dense correspondences out (coponerf_amd/matches.py): the consumer of the two flows get_z returns.
+//
+//   match_fields_kernel       cpn_match_fields: one thread per (direction, pair, pixel) of the S x S grid (32 x 8 tiles; item =
+//                             d B + b): the match q = p + up_flow(p), the cycle error cycle_masks thresholds (flow_warp.h's fp32
+//                             sequence, the four taps of the other direction's flow formed as F.interpolate forms them), the
+//                             in-image test and the signed Sampson residual of the pair under rel_pose in float64.
+//   matches_count_kernel /    cpn_compact_matches: compact.h's two launches over a pair's (direction, row, column) sequence; a
+//   matches_write_kernel      kept match writes (x0, y0, x1, y1) - view 0's point first - and (cycle, epi).
+//   refine_pose_kernel        cpn_refine_pose: ONE workgroup of 256 threads per pair, all Gauss-Newton iterations inside it.
+//                             Per pass thread t walks the matches t, t + 256, .. in ascending order and keeps 30 float64 sums
+//                             (21 of H, 6 of g, the cost, the weights, the finite matches) in registers; the butterfly of
+//                             wave_sum, then LDS and (w0 + w1) + (w2 + w3) in thread 0, which solves the damped 6 x 6 system by
+//                             Cholesky, updates R and t and leaves E and the six dE_k in LDS for the next pass.  Two barriers a
+//                             pass, no partials in HBM, no inter-workgroup synchronisation.  Pass `iters` only measures.
+//
+// The residual is float64 from the fp32 inputs, one rounding per operation (-ffp-contract=off), sums left to right:
+// tests/matches_ref.py restates all three in numpy.
+#include "common.h"
+#include "compact.h"
+#include "flow_warp.h"
+
+#include <math.h>
+
+namespace {
+
+constexpr int NT = 256;
+constexpr int PTW = 32, PTH = NT / PTW;                    // match fields: the tile of one workgroup
+constexpr int NSUM = 30;                                   // refinement: H (21), g (6), cost, sum of weights, finite matches
+
+struct Cam {
+    double fx, fy, cx, cy;
+};
+__device__ __forceinline__ Cam load_cam(const float* __restrict__ Kb) {
+    return Cam{(double)Kb[0], (double)Kb[5], (double)Kb[2], (double)Kb[6]};
+}
+
+// E = [t]x R, row-major
+__device__ __forceinline__ void essential(const double* R, const double* t, double* E) {
+    for (int j = 0; j < 3; ++j) {
+        E[0 + j] = t[1] * R[6 + j] - t[2] * R[3 + j];
+        E[3 + j] = t[2] * R[0 + j] - t[0] * R[6 + j];
+        E[6 + j] = t[0] * R[3 + j] - t[1] * R[0 + j];
+    }
+}
+
+// The pieces of the Sampson residual of the pixel pair (x0, y0) of view 0 and (x1, y1) of view 1
+struct Sampson {
+    double a0, a1, b0, b1;          // the normalised points (third component 1)
+    double g[4];                    // (E b)_0 / fx0, (E b)_1 / fy0, (E^T a)_0 / fx1, (E^T a)_1 / fy1
+    double n, D;
+};
+template <class Mat>
+__device__ __forceinline__ Sampson sampson(const Mat& E, const Cam& k0, const Cam& k1, double x0, double y0, double x1, double y1) {
+    Sampson s;
+    s.a0 = (x0 - k0.cx) / k0.fx;
+    s.a1 = (y0 - k0.cy) / k0.fy;
+    s.b0 = (x1 - k1.cx) / k1.fx;
+    s.b1 = (y1 - k1.cy) / k1.fy;
+    const double eb0 = (E[0] * s.b0 + E[1] * s.b1) + E[2];
+    const double eb1 = (E[3] * s.b0 + E[4] * s.b1) + E[5];
+    const double eb2 = (E[6] * s.b0 + E[7] * s.b1) + E[8];
+    const double ea0 = (E[0] * s.a0 + E[3] * s.a1) + E[6];
+    const double ea1 = (E[1] * s.a0 + E[4] * s.a1) + E[7];
+    s.n = (s.a0 * eb0 + s.a1 * eb1) + eb2;
+    s.g[0] = eb0 / k0.fx;
+    s.g[1] = eb1 / k0.fy;
+    s.g[2] = ea0 / k1.fx;
+    s.g[3] = ea1 / k1.fy;
+    s.D = ((s.g[0] * s.g[0] + s.g[1] * s.g[1]) + s.g[2] * s.g[2]) + s.g[3] * s.g[3];
+    return s;
+}
+__device__ __forceinline__ bool finite64(double v) { return fabs(v) <= 1.79769313486231570815e308; }      // false for NaN
+// the residual n / sqrt(D) counts iff D > 0 and n, D and the quotient are finite
+__device__ __forceinline__ bool residual_ok(const Sampson& s, double r) {
+    return s.D > 0.0 && finite64(s.D) && finite64(s.n) && finite64(r);
+}
+
+__global__ __launch_bounds__(NT) void match_fields_kernel(const float* __restrict__ flow0, const float* __restrict__ flow1,
+                                                          const float* __restrict__ intrinsics, const float* __restrict__ rel_pose,
+                                                          int B, int S, int h, float fs, float rs, float* __restrict__ q,
+                                                          float* __restrict__ cycle, float* __restrict__ epi,
+                                                          uint8_t* __restrict__ inside) {
+    const int tid = threadIdx.x;
+    const int gx = blockIdx.x * PTW + (tid & (PTW - 1)), gy = blockIdx.y * PTH + tid / PTW;
+    if (gx >= S || gy >= S) return;
+    const int item = blockIdx.z, d = item / B, b = item - d * B;
+    const float* const own = (d ? flow1 : flow0) + (size_t)b * 2 * h * h;
+    const float* const oth = (d ? flow0 : flow1) + (size_t)b * 2 * h * h;
+
+    float ux, uy, ix, iy;
+    up_flow(own, h, h, fs, rs, gx, gy, ux, uy);
+    warp_coord(S, S, gx, gy, ux, uy, ix, iy);
+    const WarpTaps t = warp_taps(ix, iy, S, S);
+    const float wt[4] = {t.wx0 * t.wy0, t.wx1 * t.wy0, t.wx0 * t.wy1, t.wx1 * t.wy1};
+    const bool ok[4] = {t.vy0 && t.vx0, t.vy0 && t.vx1, t.vy1 && t.vx0, t.vy1 && t.vx1};
+    const int tx[4] = {t.x0, t.x1, t.x0, t.x1}, ty[4] = {t.y0, t.y0, t.y1, t.y1};
+    // warp(up_other, up_own): grid_sample's sum over the taps in its order (cpn_flow_panels' expression)
+    float cx = 0.f, cy = 0.f;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        if (ok[k]) {
+            float ox, oy;
+            up_flow(oth, h, h, fs, rs, tx[k], ty[k], ox, oy);
+            cx += ox * wt[k];
+            cy += oy * wt[k];
+        }
+    }
+    const float ex = ux + cx, ey = uy + cy;
+    const float norm = sqrtf(ex * ex + ey * ey);
+    const float mx = ux + (float)gx, my = uy + (float)gy, hi = (float)(S - 1);
+    const bool in = mx >= 0.f && mx <= hi && my >= 0.f && my <= hi;
+
+    // the pair as (view 0's point, view 1's point)
+    const double px = (double)gx, py = (double)gy, qx = (double)mx, qy = (double)my;
+    const Cam k0 = load_cam(intrinsics + ((size_t)b * 2 + 0) * 16), k1 = load_cam(intrinsics + ((size_t)b * 2 + 1) * 16);
+    double R[9], tr[3], E[9];
+    for (int r = 0; r < 3; ++r) {
+        for (int c = 0; c < 3; ++c) R[3 * r + c] = (double)rel_pose[(size_t)b * 16 + 4 * r + c];
+        tr[r] = (double)rel_pose[(size_t)b * 16 + 4 * r + 3];
+    }
+    essential(R, tr, E);
+    const Sampson s = d ? sampson(E, k0, k1, qx, qy, px, py) : sampson(E, k0, k1, px, py, qx, qy);
+    const double res = s.n / sqrt(s.D);
+    const float e32 = residual_ok(s, res) ? (float)res : __builtin_nanf("");
+
+    const size_t at = ((size_t)item * S + gy) * S + gx;
+    q[2 * at + 0] = mx;
+    q[2 * at + 1] = my;
+    cycle[at] = norm;
+    epi[at] = e32;
+    inside[at] = in ? 1 : 0;
+}
+
+// ---- compaction (compact.h): what a kept match writes
+__global__ __launch_bounds__(NT) void matches_count_kernel(const uint8_t* __restrict__ keep, int B, int SS, int cap,
+                                                           int* __restrict__ counts) {
+    const int b = blockIdx.y;
+    const int n = compact_tile_count(cap, [&](int j) { return keep[seq_source(j, b, B, SS)] != 0; });
+    if (threadIdx.x == 0) counts[(size_t)b * gridDim.x + blockIdx.x] = n;
+}
+
+__global__ __launch_bounds__(NT) void matches_write_kernel(const uint8_t* __restrict__ keep, const float* __restrict__ q,
+                                                           const float* __restrict__ cycle, const float* __restrict__ epi, int B,
+                                                           int S, int cap, const int* __restrict__ counts, float* __restrict__ xy,
+                                                           float* __restrict__ err, int* __restrict__ count) {
+    const int b = blockIdx.y, SS = S * S;
+    const int at = compact_tile_rows(
+        counts + (size_t)b * gridDim.x, cap, [&](int j) { return keep[seq_source(j, b, B, SS)] != 0; },
+        [&](int j, int row) {
+            const int d = j / SS, p = j - d * SS, gy = p / S, gx = p - gy * S;
+            const size_t in = (size_t)seq_source(j, b, B, SS), o = (size_t)b * cap + (size_t)row;
+            const float px = (float)gx, py = (float)gy, qx = q[2 * in + 0], qy = q[2 * in + 1];
+            xy[4 * o + 0] = d ? qx : px;
+            xy[4 * o + 1] = d ? qy : py;
+            xy[4 * o + 2] = d ? px : qx;
+            xy[4 * o + 3] = d ? py : qy;
+            err[2 * o + 0] = cycle[in];
+            err[2 * o + 1] = epi[in];
+        });
+    if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) count[b] = at;
+}
+
+// ---- refinement
+// what thread 0 keeps for the pair between the passes, and what every thread reads in a pass
+struct RefineState {
+    double R[9], t[3];
+    double E[9], dE[6][9];          // E = [t]x R; dE_k = [t]x [e_k]x R (k < 3), [e_(k-3)]x R (k >= 3)
+    double red[NSUM][4];            // the four wave sums of a pass
+    int go;                         // another pass follows
+};
+
+// rows of [e_k]x R
+__device__ __forceinline__ void cross_rows(const double* R, int k, double* M) {
+    const int k1 = (k + 1) % 3, k2 = (k + 2) % 3;
+    for (int j = 0; j < 3; ++j) {
+        M[3 * k + j] = 0.0;
+        M[3 * k1 + j] = -R[3 * k2 + j];
+        M[3 * k2 + j] = R[3 * k1 + j];
+    }
+}
+__device__ void set_matrices(RefineState& st) {
+    essential(st.R, st.t, st.E);
+    for (int k = 0; k < 3; ++k) {
+        cross_rows(st.R, k, st.dE[3 + k]);
+        essential(st.dE[3 + k], st.t, st.dE[k]);
+    }
+}
+
+// delta = -A^-1 g by Cholesky (A = L L^T, lower); false where a pivot is not positive or a value not finite
+__device__ bool solve6(double (&A)[6][6], const double (&g)[6], double (&x)[6]) {
+    for (int j = 0; j < 6; ++j) {
+        double s = A[j][j];
+        for (int k = 0; k < j; ++k) s -= A[j][k] * A[j][k];
+        if (!(s > 0.0) || !finite64(s)) return false;
+        const double l = sqrt(s);
+        A[j][j] = l;
+        for (int i = j + 1; i < 6; ++i) {
+            double v = A[i][j];
+            for (int k = 0; k < j; ++k) v -= A[i][k] * A[j][k];
+            A[i][j] = v / l;
+        }
+    }
+    double y[6];
+    for (int i = 0; i < 6; ++i) {
+        double v = -g[i];
+        for (int k = 0; k < i; ++k) v -= A[i][k] * y[k];
+        y[i] = v / A[i][i];
+    }
+    for (int i = 5; i >= 0; --i) {
+        double v = y[i];
+        for (int k = i + 1; k < 6; ++k) v -= A[k][i] * x[k];
+        x[i] = v / A[i][i];
+    }
+    for (int i = 0; i < 6; ++i)
+        if (!finite64(x[i])) return false;
+    return true;
+}
+
+// R <- exp([w]x) R (Rodrigues; the identity below 1e-12), t <- (t + dt) / |t + dt|; false (state untouched) where not finite
+__device__ bool apply_step(RefineState& st, const double (&x)[6]) {
+    const double th = sqrt((x[0] * x[0] + x[1] * x[1]) + x[2] * x[2]);
+    double Q[9] = {1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0};
+    if (th >= 1e-12) {
+        const double k0 = x[0] / th, k1 = x[1] / th, k2 = x[2] / th, s = sin(th), c = 1.0 - cos(th);
+        const double K[9] = {0.0, -k2, k1, k2, 0.0, -k0, -k1, k0, 0.0};
+        for (int i = 0; i < 3; ++i)
+            for (int j = 0; j < 3; ++j) {
+                const double kk = (K[3 * i] * K[j] + K[3 * i + 1] * K[3 + j]) + K[3 * i + 2] * K[6 + j];
+                Q[3 * i + j] = (Q[3 * i + j] + s * K[3 * i + j]) + c * kk;
+            }
+    }
+    double Rn[9], tn[3];
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j) Rn[3 * i + j] = (Q[3 * i] * st.R[j] + Q[3 * i + 1] * st.R[3 + j]) + Q[3 * i + 2] * st.R[6 + j];
+    for (int i = 0; i < 3; ++i) tn[i] = st.t[i] + x[3 + i];
+    const double len = sqrt((tn[0] * tn[0] + tn[1] * tn[1]) + tn[2] * tn[2]);
+    if (!(len > 0.0) || !finite64(len)) return false;
+    for (int i = 0; i < 9; ++i)
+        if (!finite64(Rn[i])) return false;
+    for (int i = 0; i < 9; ++i) st.R[i] = Rn[i];
+    for (int i = 0; i < 3; ++i) st.t[i] = tn[i] / len;
+    return true;
+}
+
+__global__ __launch_bounds__(NT) void refine_pose_kernel(const float* __restrict__ xy, const int* __restrict__ count,
+                                                         const float* __restrict__ intrinsics, const float* __restrict__ rel_pose,
+                                                         int N, int iters, double scale_px, float* __restrict__ pose,
+                                                         double* __restrict__ stats) {
+    __shared__ RefineState st;
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const float* const P = rel_pose + (size_t)b * 16;
+    int n = count[b];
+    n = n < 0 ? 0 : (n > N ? N : n);
+    double len0 = 0.0, cost0 = 0.0;
+    if (tid == 0) {
+        bool fin = true;
+        double t0[3];
+        for (int r = 0; r < 3; ++r) {
+            for (int c = 0; c < 3; ++c) {
+                st.R[3 * r + c] = (double)P[4 * r + c];
+                fin = fin && finite64(st.R[3 * r + c]);
+            }
+            t0[r] = (double)P[4 * r + 3];
+            fin = fin && finite64(t0[r]);
+        }
+        len0 = sqrt((t0[0] * t0[0] + t0[1] * t0[1]) + t0[2] * t0[2]);
+        st.go = (fin && len0 > 0.0 && finite64(len0) && n > 0 && iters > 0) ? 1 : 0;
+        if (st.go) {
+            for (int r = 0; r < 3; ++r) st.t[r] = t0[r] / len0;
+            set_matrices(st);
+        }
+    }
+    __syncthreads();
+    if (!st.go) {                                          // nothing to do: rel_pose as it came, status 2
+        if (tid < 16) pose[(size_t)b * 16 + tid] = P[tid];
+        if (tid < 8) stats[(size_t)b * 8 + tid] = tid == 7 ? 2.0 : 0.0;
+        return;
+    }
+    const Cam k0 = load_cam(intrinsics + ((size_t)b * 2 + 0) * 16), k1 = load_cam(intrinsics + ((size_t)b * 2 + 1) * 16);
+    const float* const rows = xy + (size_t)b * N * 4;
+    int done = 0, status = 0;
+
+    for (int pass = 0;; ++pass) {
+        double acc[NSUM];
+#pragma unroll
+        for (int k = 0; k < NSUM; ++k) acc[k] = 0.0;
+        for (int i = tid; i < n; i += NT) {
+            const float* const m = rows + (size_t)i * 4;
+            const Sampson s = sampson(st.E, k0, k1, (double)m[0], (double)m[1], (double)m[2], (double)m[3]);
+            const double sd = sqrt(s.D), r = s.n / sd;
+            if (!residual_ok(s, r)) continue;               // weight 0, not counted
+            double J[6];
+#pragma unroll
+            for (int k = 0; k < 6; ++k) {
+                const double* const dE = st.dE[k];
+                const double db0 = (dE[0] * s.b0 + dE[1] * s.b1) + dE[2];
+                const double db1 = (dE[3] * s.b0 + dE[4] * s.b1) + dE[5];
+                const double db2 = (dE[6] * s.b0 + dE[7] * s.b1) + dE[8];
+                const double da0 = (dE[0] * s.a0 + dE[3] * s.a1) + dE[6];
+                const double da1 = (dE[1] * s.a0 + dE[4] * s.a1) + dE[7];
+                const double dn = (s.a0 * db0 + s.a1 * db1) + db2;
+                const double dD = 2.0 * (((s.g[0] * (db0 / k0.fx) + s.g[1] * (db1 / k0.fy)) + s.g[2] * (da0 / k1.fx)) +
+                                         s.g[3] * (da1 / k1.fy));
+                J[k] = dn / sd - (s.n * dD) / ((2.0 * s.D) * sd);
+            }
+            const double z = r / scale_px, u = 1.0 + z * z, w = 1.0 / (u * u);
+            int at = 0;
+#pragma unroll
+            for (int j = 0; j < 6; ++j) {
+                const double wj = w * J[j];
+#pragma unroll
+                for (int k = j; k < 6; ++k) acc[at++] += wj * J[k];
+                acc[21 + j] += wj * r;
+            }
+            acc[27] += ((r * r) / 2.0) / u;
+            acc[28] += w;
+            acc[29] += 1.0;
+        }
+#pragma unroll
+        for (int k = 0; k < NSUM; ++k) acc[k] = wave_sum(acc[k]);
+        if (lane == 0) {
+#pragma unroll
+            for (int k = 0; k < NSUM; ++k) st.red[k][wave] = acc[k];
+        }
+        __syncthreads();
+        if (tid == 0) {
+            double sum[NSUM];
+            for (int k = 0; k < NSUM; ++k) sum[k] = (st.red[k][0] + st.red[k][1]) + (st.red[k][2] + st.red[k][3]);
+            if (pass == 0) cost0 = sum[27];
+            bool more = pass < iters;
+            if (more) {
+                double A[6][6], g[6], x[6];
+                int at = 0;
+                for (int j = 0; j < 6; ++j) {
+                    for (int k = j; k < 6; ++k) A[j][k] = A[k][j] = sum[at++];
+                    g[j] = sum[21 + j];
+                }
+                double trace = 0.0;
+                for (int j = 0; j < 6; ++j) trace += A[j][j];
+                for (int j = 0; j < 6; ++j) A[j][j] = A[j][j] + 1e-3 * A[j][j];
+                const double pin = trace / 6.0;            // the gauge: the residual cannot see the length of t
+                for (int i = 0; i < 3; ++i)
+                    for (int j = 0; j < 3; ++j) A[3 + i][3 + j] = A[3 + i][3 + j] + pin * (st.t[i] * st.t[j]);
+                more = solve6(A, g, x) && apply_step(st, x);
+                if (more) {
+                    set_matrices(st);
+                    ++done;
+                } else {
+                    status = 1;                            // the pair keeps its state and stops
+                }
+            }
+            st.go = more ? 1 : 0;
+            if (!more) {
+                float* const o = pose + (size_t)b * 16;
+                double dR = 0.0, dt = 0.0;
+                for (int r = 0; r < 3; ++r) {
+                    for (int c = 0; c < 3; ++c) {
+                        o[4 * r + c] = (float)st.R[3 * r + c];
+                        const double e = st.R[3 * r + c] - (double)P[4 * r + c];
+                        dR += e * e;
+                    }
+                    o[4 * r + 3] = (float)(len0 * st.t[r]);
+                    const double e = st.t[r] - (double)P[4 * r + 3] / len0;
+                    dt += e * e;
+                    o[12 + r] = 0.0f;
+                }
+                o[15] = 1.0f;
+                // |R - R0|_F = 2 sqrt(2) sin(angle / 2), |t - t0| = 2 sin(angle / 2): exact down to the smallest angles
+                const double deg = 57.29577951308232;
+                double* const so = stats + (size_t)b * 8;
+                so[0] = cost0;
+                so[1] = sum[27];
+                so[2] = sum[28];
+                so[3] = sum[29];
+                so[4] = 2.0 * asin(fmin(sqrt(dR) / 2.8284271247461903, 1.0)) * deg;
+                so[5] = 2.0 * asin(fmin(sqrt(dt) / 2.0, 1.0)) * deg;
+                so[6] = (double)done;
+                so[7] = (double)status;
+            }
+        }
+        __syncthreads();
+        if (!st.go) return;
+    }
+}
+
+bool grid_ok(int B, int S) { return B >= 1 && B <= 32767 && S >= 1 && S <= 16384 && 2LL * B * S * S < (1LL << 31); }
+
+}  // namespace
+
+extern "C" int cpn_match_fields(const float* flow0, const float* flow1, const float* intrinsics, const float* rel_pose, int B, int S,
+                                int h, float* q, float* cycle, float* epi, uint8_t* inside, void* stream) {
+    CPN_REQUIRE(flow0 && flow1 && intrinsics && rel_pose && q && cycle && epi && inside, CPN_E_ARG, "cpn_match_fields: null pointer");
+    CPN_REQUIRE(grid_ok(B, S) && h >= 1 && S % h == 0, CPN_E_SHAPE,
+                "cpn_match_fields: need 1 <= B <= 32767, S a multiple of h >= 1, S <= 16384 and 2 B S S < 2^31 (got B %d, S %d, h %d)", B,
+                S, h);
+    const float fs = (float)((double)S / (double)h);       // the Python float S / h, rounded when it meets the fp32 tensor
+    const float rs = (float)h / (float)S;                  // ATen's area_pixel_compute_scale in fp32
+    const dim3 grid(cpn_cdiv(S, PTW), cpn_cdiv(S, PTH), 2 * B);
+    hipLaunchKernelGGL(match_fields_kernel, grid, dim3(NT), 0, (hipStream_t)stream, flow0, flow1, intrinsics, rel_pose, B, S, h, fs, rs,
+                       q, cycle, epi, inside);
+    CPN_LAUNCH_CHECK("cpn_match_fields");
+    return 0;
+}
+
+extern "C" int cpn_compact_matches_scratch(int B, int S) {
+    if (!grid_ok(B, S)) return 0;
+    return (int)((long long)B * cpn_cdiv(2LL * S * S, CPN_COMPACT_TILE));
+}
+
+extern "C" int cpn_compact_matches(const uint8_t* keep, const float* q, const float* cycle, const float* epi, int B, int S,
+                                   int* scratch, float* xy, float* err, int* count, void* stream) {
+    CPN_REQUIRE(keep && q && cycle && epi && scratch && xy && err && count, CPN_E_ARG, "cpn_compact_matches: null pointer");
+    CPN_REQUIRE(grid_ok(B, S), CPN_E_SHAPE, "cpn_compact_matches: need 1 <= B <= 32767, 1 <= S <= 16384 and 2 B S S < 2^31 (got B %d, S %d)",
+                B, S);
+    const int SS = S * S, cap = 2 * SS;
+    const dim3 grid(cpn_cdiv(cap, CPN_COMPACT_TILE), B);
+    hipLaunchKernelGGL(matches_count_kernel, grid, dim3(NT), 0, (hipStream_t)stream, keep, B, SS, cap, scratch);
+    CPN_LAUNCH_CHECK("cpn_compact_matches (count)");
+    hipLaunchKernelGGL(matches_write_kernel, grid, dim3(NT), 0, (hipStream_t)stream, keep, q, cycle, epi, B, S, cap, (const int*)scratch,
+                       xy, err, count);
+    CPN_LAUNCH_CHECK("cpn_compact_matches (write)");
+    return 0;
+}
+
+extern "C" int cpn_refine_pose(const float* xy, const int* count, const float* intrinsics, const float* rel_pose, int B, int N,
+                               int iters, double scale_px, float* pose, double* stats, void* stream) {
+    CPN_REQUIRE(xy && count && intrinsics && rel_pose && pose && stats, CPN_E_ARG, "cpn_refine_pose: null pointer");
+    CPN_REQUIRE(B >= 1 && N >= 1, CPN_E_SHAPE, "cpn_refine_pose: need B >= 1 pairs of N >= 1 rows (got B %d, N %d)", B, N);
+    CPN_REQUIRE(iters >= 0 && scale_px > 0.0 && scale_px <= 1.79769313486231570815e308, CPN_E_ARG,
+                "cpn_refine_pose: need iters >= 0 and a finite scale_px > 0 (got %d, %g)", iters, scale_px);
+    hipLaunchKernelGGL(refine_pose_kernel, dim3(B), dim3(NT), 0, (hipStream_t)stream, xy, count, intrinsics, rel_pose, N, iters,
+                       scale_px, pose, stats);
+    CPN_LAUNCH_CHECK("cpn_refine_pose");
+    return 0;
+}

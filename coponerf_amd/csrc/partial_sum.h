@@ -1,7 +1,7 @@
 // The fixed-order sums of partial results, once each.  Two keep the training gradients bit-reproducible: the reducers of
 // ufc_wgrad.hip and ufc_strided_bwd.hip (sum_partials_16x64), of wgrad_f32.hip and wgrad_tall.hip (sum_slabs_f32x4).  The third
 // is the float64 finish of the image-side units (sum_partials_f64: image_metrics.hip, ssim_warp.hip, lpips.hip, summaries.hip).
-// The fourth adds the block counts of the stream compaction (sum_counts_256: point_cloud.hip) in the same thread order.
+// The fourth adds the block counts of the stream compaction (sum_counts_256: compact.h) in the same thread order.
 #pragma once
 #include "common.h"
 

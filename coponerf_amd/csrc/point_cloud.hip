@@ -6,14 +6,14 @@
 //                             a vote where it lands within px_tol pixels and rel_tol . d_a of where it started.
 //   compact_count_kernel /    cpn_compact_points: a workgroup owns CPN_COMPACT_TILE consecutive elements of a pair's (view, row,
 //   compact_write_kernel      column) sequence.  The first launch counts the selected ones per workgroup; the second adds the counts
-//                             of the workgroups before its own (sum_counts_256), ranks its own elements by wave ballots and
-//                             writes.  No atomics: an element's output row depends on the mask alone.
+//                             of the workgroups before its own, ranks its own elements by wave ballots and writes: compact.h,
+//                             shared with matches.hip.  No atomics: an element's output row depends on the mask alone.
 //
 // The geometry is float64 from the fp32 inputs, one rounding per operation (-ffp-contract=off), sums left to right, and one
 // rounding to fp32 at the store: tests/point_cloud_ref.py restates it in numpy.
 #include "common.h"
 #include "byte_pack.h"
-#include "partial_sum.h"
+#include "compact.h"
 
 #include <math.h>
 
@@ -21,8 +21,7 @@ namespace {
 
 constexpr int NT = 256;
 constexpr int TILE = CPN_COMPACT_TILE;
-constexpr int SUB = TILE / NT;                             // elements per thread of a compaction workgroup
-static_assert(CPN_COMPACT_FINISH == NT && TILE % NT == 0, "the compaction kernels run 256 threads");
+static_assert(COMPACT_NT == NT, "the compaction kernels run 256 threads");
 
 struct Cam {
     double fx, fy, cx, cy;
@@ -157,55 +156,28 @@ __global__ __launch_bounds__(NT) void depth_votes_kernel(const float* __restrict
     fused[i] = (float)(sum / (double)(1 + n));
 }
 
-// ---- compaction.  Element j of pair b's sequence (cap = K h w of them) is pixel j % hw of view j / hw.
-__device__ __forceinline__ int seq_source(int j, int b, int B, int hw) {
-    const int k = j / hw;
-    return (k * B + b) * hw + (j - k * hw);                // < K B h w < 2^31
-}
-
+// ---- compaction (compact.h): what a selected point writes
 __global__ __launch_bounds__(NT) void compact_count_kernel(const uint8_t* __restrict__ keep, int B, int hw, int cap,
                                                            int* __restrict__ counts) {
     const int b = blockIdx.y;
-    int n[1] = {0};
-    for (int s = 0; s < SUB; ++s) {
-        const int j = blockIdx.x * TILE + s * NT + threadIdx.x;
-        n[0] += (j < cap && keep[seq_source(j, b, B, hw)] != 0) ? 1 : 0;
-    }
-    block256_sum(n);
-    if (threadIdx.x == 0) counts[(size_t)b * gridDim.x + blockIdx.x] = n[0];
+    const int n = compact_tile_count(cap, [&](int j) { return keep[seq_source(j, b, B, hw)] != 0; });
+    if (threadIdx.x == 0) counts[(size_t)b * gridDim.x + blockIdx.x] = n;
 }
 
 __global__ __launch_bounds__(NT) void compact_write_kernel(const uint8_t* __restrict__ keep, const float* __restrict__ xyz,
                                                            const float* __restrict__ rgb, int B, int hw, int cap,
                                                            const int* __restrict__ counts, float* __restrict__ out_xyz,
                                                            uint8_t* __restrict__ out_rgb, int* __restrict__ count) {
-    __shared__ int wc[SUB][4];                             // selected elements of wave wv in sub-tile s
-    const int b = blockIdx.y, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int before = sum_counts_256(counts + (size_t)b * gridDim.x, (int)blockIdx.x);
-    int src[SUB], below[SUB];
-    bool sel[SUB];
-    for (int s = 0; s < SUB; ++s) {
-        const int j = blockIdx.x * TILE + s * NT + threadIdx.x;
-        src[s] = j < cap ? seq_source(j, b, B, hw) : 0;
-        sel[s] = j < cap && keep[src[s]] != 0;
-        const unsigned long long m = __ballot(sel[s]);
-        below[s] = __popcll(m & ((1ull << lane) - 1ull));
-        if (lane == 0) wc[s][wave] = __popcll(m);
-    }
-    __syncthreads();
-    int at = before;                                       // output row of the first element of (sub-tile, wave), in order
-    for (int s = 0; s < SUB; ++s) {
-        for (int wv = 0; wv < 4; ++wv) {
-            if (wv == wave && sel[s]) {
-                const size_t o = ((size_t)b * cap + (size_t)(at + below[s])) * 3, in = (size_t)src[s] * 3;
-                for (int c = 0; c < 3; ++c) {
-                    out_xyz[o + c] = xyz[in + c];
-                    out_rgb[o + c] = to_byte((rgb[in + c] + 1.0f) * 127.5f);
-                }
+    const int b = blockIdx.y;
+    const int at = compact_tile_rows(
+        counts + (size_t)b * gridDim.x, cap, [&](int j) { return keep[seq_source(j, b, B, hw)] != 0; },
+        [&](int j, int row) {
+            const size_t o = ((size_t)b * cap + (size_t)row) * 3, in = (size_t)seq_source(j, b, B, hw) * 3;
+            for (int c = 0; c < 3; ++c) {
+                out_xyz[o + c] = xyz[in + c];
+                out_rgb[o + c] = to_byte((rgb[in + c] + 1.0f) * 127.5f);
             }
-            at += wc[s][wv];
-        }
-    }
+        });
     if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) count[b] = at;
 }
 

@@ -1,0 +1,236 @@
+"""Two photos in, their dense correspondences out, and the estimated pose polished against them - on the device until the
+user asks for the matches.
+
+`get_z` returns two flows beside the pose: flow[0] lives on view 0's grid and points into view 1, flow[1] the other way
+round.  The reference uses them for the cycle loss and a warped panel only.  Here
+
+  match_fields  per pixel of both directions: the match, the cycle error cycle_masks thresholds, the in-image test and the
+                signed Sampson residual under rel_pose, in pixels: cpn_match_fields, one launch
+  select        the keep mask with stock ops, cpn_compact_matches -> a Matches
+  Matches       xy (x0, y0, x1, y1) / err (cycle, epi) / count on the device; numpy(b) is the one host read
+  refine_pose   robust Gauss-Newton of the relative pose on the Sampson residuals of the matches: cpn_refine_pose, one launch
+  from_pair     get_z once, then the three above
+  photo_coords  host: matches of a prepare_pair dict in the coordinates of the original photos
+
+The conventions and the arithmetic are in include/coponerf_hip.h (round 16).  The selection defaults (cycle error up to 10
+pixels - the reference's own mask -, one match per native flow cell) and scale_px are this package's choices and have not been
+tried on a trained checkpoint, because none is available offline; whether the refined pose is closer to the truth than the
+network's on real data is unknown.  The epipolar residual cannot see the translation's length: the refined pose keeps the
+network's.
+"""
+from __future__ import annotations
+
+from typing import Dict, Optional, Sequence, Tuple
+
+import numpy as np
+import torch
+
+from . import _hip
+from .shards import crop_window
+
+
+def _device_f32(who: str, named, dev=None) -> None:
+    """The checks every entry shares: contiguous fp32 tensors on one HIP device."""
+    for what, x in named:
+        if not torch.is_tensor(x) or not x.is_cuda:
+            raise RuntimeError(f"{who} runs on the HIP device only (coponerf_amd has no non-HIP compute path): {what}")
+        dev = x.device if dev is None else dev
+        if x.dtype != torch.float32 or not x.is_contiguous() or x.device != dev:
+            raise ValueError(f"{who}: {what} must be a contiguous fp32 tensor on one device")
+
+
+def _cameras(who: str, intrinsics: torch.Tensor, rel_pose: torch.Tensor, B: int) -> None:
+    if tuple(intrinsics.shape) != (B, 2, 4, 4):
+        raise ValueError(f"{who}: intrinsics must be (B, 2, 4, 4) with B = {B} (`context.intrinsics`), got {tuple(intrinsics.shape)}")
+    if tuple(rel_pose.shape) != (B, 4, 4):
+        raise ValueError(f"{who}: rel_pose must be (B, 4, 4) with B = {B}, got {tuple(rel_pose.shape)}")
+
+
+@torch.no_grad()
+def match_fields(flow: Sequence[torch.Tensor], intrinsics: torch.Tensor, rel_pose: torch.Tensor, S: int = 256) -> Dict[str, torch.Tensor]:
+    """cpn_match_fields: flow = (flow[0], flow[1]), each (B, 2, h, h) fp32 as get_z returns them, intrinsics (B, 2, 4, 4) fp32
+    (`context.intrinsics`), rel_pose (B, 4, 4) fp32, S a multiple of h -> a dict, index 0 of every tensor the direction:
+    `q` (2, B, S, S, 2) fp32 the match of every pixel, `cycle` (2, B, S, S) fp32 the forward-backward error in pixels, `epi`
+    (2, B, S, S) fp32 the signed Sampson residual in pixels (NaN where it is not defined), `inside` (2, B, S, S) uint8."""
+    if len(flow) < 2:
+        raise ValueError("match_fields: flow must hold the two directions")
+    f0, f1 = flow[0], flow[1]
+    _device_f32("match_fields", (("flow[0]", f0), ("flow[1]", f1), ("intrinsics", intrinsics), ("rel_pose", rel_pose)))
+    if f0.dim() != 4 or f0.shape[1] != 2 or f0.shape[2] != f0.shape[3] or f1.shape != f0.shape:
+        raise ValueError(f"match_fields: flows must both be (B, 2, h, h), got {tuple(f0.shape)} and {tuple(f1.shape)}")
+    B, h, S = int(f0.shape[0]), int(f0.shape[2]), int(S)
+    _cameras("match_fields", intrinsics, rel_pose, B)
+    if h < 1 or S < h or S % h or not 1 <= B <= 32767 or S > 16384 or 2 * B * S * S >= 2 ** 31:
+        raise ValueError(f"match_fields: need S a multiple of h, 1 <= B <= 32767, S <= 16384 and 2 B S S < 2^31, got B = {B}, S = {S}, "
+                         f"h = {h}")
+    dev = f0.device
+    q = torch.empty(2, B, S, S, 2, dtype=torch.float32, device=dev)
+    cycle = torch.empty(2, B, S, S, dtype=torch.float32, device=dev)
+    epi = torch.empty(2, B, S, S, dtype=torch.float32, device=dev)
+    inside = torch.empty(2, B, S, S, dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        _hip.call("cpn_match_fields", f0.data_ptr(), f1.data_ptr(), intrinsics.data_ptr(), rel_pose.data_ptr(), B, S, h, q.data_ptr(),
+                  cycle.data_ptr(), epi.data_ptr(), inside.data_ptr(), _hip.stream_handle())
+    return {"q": q, "cycle": cycle, "epi": epi, "inside": inside}
+
+
+def pack_matches(count: torch.Tensor, xy: torch.Tensor, err: torch.Tensor) -> torch.Tensor:
+    """One pair's count (1) int32, xy (cap, 4) fp32 and err (cap, 2) fp32 as one uint8 buffer: what Matches.numpy reads."""
+    return torch.cat((count.view(torch.uint8), xy.view(torch.uint8).reshape(-1), err.view(torch.uint8).reshape(-1)))
+
+
+def unpack_matches(packed: np.ndarray, cap: int) -> Tuple[np.ndarray, np.ndarray]:
+    """pack_matches' buffer on the host -> ((n, 4) float32, (n, 2) float32): the rows beyond the count are dropped here."""
+    n = int(packed[:4].view(np.int32)[0])
+    xy = packed[4:4 + 16 * cap].view(np.float32).reshape(cap, 4)[:n].copy()
+    err = packed[4 + 16 * cap:4 + 24 * cap].view(np.float32).reshape(cap, 2)[:n].copy()
+    return xy, err
+
+
+class Matches:
+    """The kept matches of B pairs on the device: xy (B, cap, 4) fp32 = (x0, y0, x1, y1) in the pixels of the S x S grid, view
+    0's point first whatever the direction it was found in; err (B, cap, 2) fp32 = (cycle error, epipolar residual) in pixels;
+    count (B) int32.  Pair b's matches are the rows [0, count[b]) in (direction, row, column) order; the rows beyond are not
+    written."""
+
+    def __init__(self, xy: torch.Tensor, err: torch.Tensor, count: torch.Tensor):
+        self.xy, self.err, self.count = xy, err, count
+
+    @torch.no_grad()
+    def numpy(self, b: int = 0) -> Tuple[np.ndarray, np.ndarray]:
+        """Pair b's matches on the host: ((n, 4) float32, (n, 2) float32).  ONE read: the count, xy and err of the pair travel in
+        one buffer."""
+        return unpack_matches(pack_matches(self.count[b:b + 1], self.xy[b], self.err[b]).cpu().numpy(), int(self.xy.shape[1]))
+
+
+_STRIDE_MASKS: Dict = {}
+
+
+def _stride_mask(S: int, stride: int, dev) -> torch.Tensor:
+    """(S, S) bool: the pixels with x % stride == stride // 2 and y % stride == stride // 2; a constant, built once."""
+    key = (S, stride, str(dev))
+    m = _STRIDE_MASKS.get(key)
+    if m is None:
+        on = torch.arange(S, device=dev) % stride == stride // 2
+        m = _STRIDE_MASKS[key] = on[:, None] & on[None, :]
+    return m
+
+
+@torch.no_grad()
+def compact(keep: torch.Tensor, q: torch.Tensor, cycle: torch.Tensor, epi: torch.Tensor) -> Matches:
+    """cpn_compact_matches: keep (2, B, S, S) uint8 (non-zero = kept) and match_fields' q, cycle and epi -> the Matches of every
+    pair in (direction, row, column) order, cap = 2 S S rows per pair."""
+    if not all(torch.is_tensor(x) and x.is_cuda and x.is_contiguous() and x.device == keep.device for x in (keep, q, cycle, epi)):
+        raise RuntimeError("compact: contiguous tensors on one HIP device (coponerf_amd has no non-HIP compute path)")
+    if keep.dtype != torch.uint8 or keep.dim() != 4 or keep.shape[0] != 2 or keep.shape[2] != keep.shape[3]:
+        raise ValueError(f"compact: keep must be (2, B, S, S) uint8, got {tuple(keep.shape)} {keep.dtype}")
+    B, S = int(keep.shape[1]), int(keep.shape[2])
+    for what, x, shape in (("q", q, (2, B, S, S, 2)), ("cycle", cycle, (2, B, S, S)), ("epi", epi, (2, B, S, S))):
+        if x.dtype != torch.float32 or tuple(x.shape) != shape:
+            raise ValueError(f"compact: {what} must be {shape} fp32, got {tuple(x.shape)} {x.dtype}")
+    n_scratch = _hip.lib().cpn_compact_matches_scratch(B, S)
+    if n_scratch <= 0:
+        raise ValueError(f"compact: need 1 <= B <= 32767, S <= 16384 and 2 B S S < 2^31, got B = {B}, S = {S}")
+    dev, cap = keep.device, 2 * S * S
+    xy = torch.empty(B, cap, 4, dtype=torch.float32, device=dev)
+    err = torch.empty(B, cap, 2, dtype=torch.float32, device=dev)
+    count = torch.empty(B, dtype=torch.int32, device=dev)
+    scratch = torch.empty(n_scratch, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        _hip.call("cpn_compact_matches", keep.data_ptr(), q.data_ptr(), cycle.data_ptr(), epi.data_ptr(), B, S, scratch.data_ptr(),
+                  xy.data_ptr(), err.data_ptr(), count.data_ptr(), _hip.stream_handle())
+    return Matches(xy, err, count)
+
+
+@torch.no_grad()
+def select(fields: Dict[str, torch.Tensor], max_cycle_px: float = 10.0, max_epi_px: Optional[float] = None, stride: int = 4) -> Matches:
+    """The Matches of match_fields' dict: a pixel is kept iff its match lies inside the image, its cycle error is at most
+    max_cycle_px (10: the reference's own mask), with max_epi_px its |epi| is at most that (a NaN epi is dropped), and
+    x % stride == y % stride == stride // 2.  stride=4 keeps one match per native flow cell of a 64 x 64 flow at 256 x 256,
+    where neighbouring pixels are 16-fold redundant; stride=1 keeps every pixel.  Stock ops form the mask, the kernel
+    compacts it; nothing is read on the host."""
+    stride = int(stride)
+    if stride < 1:
+        raise ValueError(f"select: stride must be >= 1, got {stride}")
+    cycle, epi, inside = fields["cycle"], fields["epi"], fields["inside"]
+    keep = (inside != 0) & (cycle <= float(max_cycle_px))
+    if max_epi_px is not None:
+        keep &= epi.abs() <= float(max_epi_px)
+    if stride > 1:
+        keep &= _stride_mask(int(cycle.shape[-1]), stride, cycle.device)
+    return compact(keep.to(torch.uint8), fields["q"], cycle, epi)
+
+
+@torch.no_grad()
+def refine_pose(matches: Matches, intrinsics: torch.Tensor, rel_pose: torch.Tensor, iters: int = 10,
+                scale_px: float = 2.0) -> Dict[str, torch.Tensor]:
+    """cpn_refine_pose: `iters` damped Gauss-Newton steps of the relative pose on the Sampson residuals of the matches, each
+    weighted 1 / (1 + (r / scale_px)^2)^2, float64 inside, one launch for all pairs -> `pose` (B, 4, 4) fp32 = [R | |t0| t]
+    (the translation keeps rel_pose's length, which the residual cannot see) and `stats` (B, 8) float64: the cost at the
+    start, the cost / sum of weights / number of usable matches at the end, the angles in degrees the rotation and the
+    translation direction moved by, the updates made, and the status (0 ok, 1 a failed solve: the state before it is
+    returned, 2 nothing to do: no matches, a zero or non-finite pose, or iters == 0 - pose is rel_pose, the rest 0)."""
+    xy, count = matches.xy, matches.count
+    _device_f32("refine_pose", (("matches.xy", xy), ("intrinsics", intrinsics), ("rel_pose", rel_pose)))
+    if xy.dim() != 3 or xy.shape[2] != 4 or xy.shape[1] < 1:
+        raise ValueError(f"refine_pose: matches.xy must be (B, N, 4) with N >= 1, got {tuple(xy.shape)}")
+    B, N = int(xy.shape[0]), int(xy.shape[1])
+    if not torch.is_tensor(count) or count.device != xy.device or count.dtype != torch.int32 or tuple(count.shape) != (B,) or \
+            not count.is_contiguous():
+        raise ValueError(f"refine_pose: matches.count must be a contiguous ({B},) int32 tensor on xy's device")
+    _cameras("refine_pose", intrinsics, rel_pose, B)
+    if int(iters) < 0 or not 0.0 < float(scale_px) < float("inf"):
+        raise ValueError(f"refine_pose: need iters >= 0 and a finite scale_px > 0, got {iters} and {scale_px}")
+    pose = torch.empty(B, 4, 4, dtype=torch.float32, device=xy.device)
+    stats = torch.empty(B, 8, dtype=torch.float64, device=xy.device)
+    with torch.cuda.device(xy.device):
+        _hip.call("cpn_refine_pose", xy.data_ptr(), count.data_ptr(), intrinsics.data_ptr(), rel_pose.data_ptr(), B, N, int(iters),
+                  float(scale_px), pose.data_ptr(), stats.data_ptr(), _hip.stream_handle())
+    return {"pose": pose, "stats": stats}
+
+
+@torch.no_grad()
+def from_flows(flow: Sequence[torch.Tensor], intrinsics: torch.Tensor, rel_pose: torch.Tensor, S: int = 256, refine: bool = True,
+               max_cycle_px: float = 10.0, max_epi_px: Optional[float] = None, stride: int = 4, iters: int = 10,
+               scale_px: float = 2.0) -> Dict:
+    """from_pair's second half, for flows and a pose that get_z has already returned: four launches and the mask between them,
+    no host read."""
+    fields = match_fields(flow, intrinsics, rel_pose, S)
+    matches = select(fields, max_cycle_px=max_cycle_px, max_epi_px=max_epi_px, stride=stride)
+    result = {"matches": matches, "rel_pose": rel_pose, "pose": None, "stats": None, "fields": fields}
+    if refine:
+        result.update(refine_pose(matches, intrinsics, rel_pose, iters=iters, scale_px=scale_px))
+    return result
+
+
+@torch.no_grad()
+def from_pair(model, model_input: Dict, S: int = 256, refine: bool = True, **select_and_refine_keywords) -> Dict:
+    """The matches of the pair(s) in model_input (prepare_pair's dict, or any dict get_z takes).  get_z runs once; its flows
+    and its rel_pose - the ones novel_views.render_path hands on - go through match_fields, select and, with refine=True,
+    refine_pose.  Keywords: select's max_cycle_px, max_epi_px, stride and refine_pose's iters, scale_px.  Returns `matches` (a
+    Matches), `rel_pose` (B, 4, 4) as estimated, `pose` and `stats` as refine_pose returns them (None with refine=False) and
+    `fields`, match_fields' dict.  Nothing is read on the host; Matches.numpy is the read."""
+    _, rel_pose, flow = model.get_z(model_input)
+    flows = (flow[0].float().contiguous(), flow[1].float().contiguous())
+    intrinsics = model_input["context"]["intrinsics"].float().contiguous()
+    return from_flows(flows, intrinsics, rel_pose.float().contiguous(), S=S, refine=refine, **select_and_refine_keywords)
+
+
+def photo_coords(xy, Hi, Wi, size: int) -> np.ndarray:
+    """Matches (n, 4) = (x0, y0, x1, y1) in the pixels of the size x size model images -> the same in the pixels of the original
+    photos of Hi x Wi pixels (two ints, or a pair of ints each where the photos differ): the inverse of the centre square crop
+    and the scale of novel_views.fit_intrinsics, x_photo = x / s + (Wi - side) / 2 with s = size / side.  float64, host."""
+    xy = np.asarray(xy, dtype=np.float64)
+    if xy.ndim != 2 or xy.shape[1] != 4:
+        raise ValueError(f"photo_coords: xy must be (n, 4), got {xy.shape}")
+    Hs = (int(Hi), int(Hi)) if np.ndim(Hi) == 0 else tuple(int(v) for v in Hi)
+    Ws = (int(Wi), int(Wi)) if np.ndim(Wi) == 0 else tuple(int(v) for v in Wi)
+    if len(Hs) != 2 or len(Ws) != 2:
+        raise ValueError("photo_coords: Hi and Wi are ints or pairs of ints (view 0, view 1)")
+    out = np.empty_like(xy)
+    for v in range(2):
+        _, _, side = crop_window(Hs[v], Ws[v])
+        s = size / side
+        out[:, 2 * v + 0] = xy[:, 2 * v + 0] / s + (Ws[v] - side) / 2.0
+        out[:, 2 * v + 1] = xy[:, 2 * v + 1] / s + (Hs[v] - side) / 2.0
+    return out

@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define CPN_ABI_VERSION 12   /* cpn_attend_units (round 7), cpn_ssim_warp* (round 8), cpn_image_metrics* (round 9), summaries.hip (round 10), lpips.hip (round 11), novel_views.hip (round 12), epipolar.hip (round 13), cpn_lpips_*_bwd (round 14) and point_cloud.hip (round 15) are additive - symbols added, none altered: the version stays */
+#define CPN_ABI_VERSION 12   /* cpn_attend_units (round 7), cpn_ssim_warp* (round 8), cpn_image_metrics* (round 9), summaries.hip (round 10), lpips.hip (round 11), novel_views.hip (round 12), epipolar.hip (round 13), cpn_lpips_*_bwd (round 14), point_cloud.hip (round 15) and matches.hip (round 16) are additive - symbols added, none altered: the version stays */
 
 #define CPN_E_ARG   (-1)   /* bad argument (null pointer, size, alignment) */
 #define CPN_E_SHAPE (-2)   /* shape not supported by the compiled tiles    */
@@ -860,6 +860,62 @@ int cpn_depth_votes(const float* depth, const float* poses, const float* intrins
 int cpn_compact_points_scratch(int K, int B, int h, int w);
 int cpn_compact_points(const uint8_t* keep, const float* xyz, const float* rgb, int K, int B, int h, int w, int* scratch,
                        float* out_xyz, uint8_t* out_rgb, int* count, void* stream);
+
+/* ==== dense correspondences from the two flows, and the pose refined against them (round 16) ============================
+ * What a caller does by hand with the flows of get_z to get the matches between two photos, and to ask whether the estimated
+ * pose agrees with them.  The symbols are additive: the ABI version stays.  The selection and the refinement are THIS LIBRARY'S
+ * definitions, not the reference's.  Conventions:
+ *   flow direction: flow0 (B, 2, h, h) fp32 lives on view 0's grid and points into view 1: p + flow0(p) is the match of p;
+ *     flow1 lives on view 1's grid and points into view 0 (what cpn_soft_argmax_pair produces and cycle_masks and
+ *     cpn_flow_panels consume).  Direction d = 0 is the pixels of view 0 matched into view 1 by flow0, d = 1 the other way.
+ *   pose: rel_pose (B, 4, 4) fp32 = [R | t] with X0 = R X1 + t, E = [t]x R and a^T E b = 0 for the normalised points a of
+ *     view 0 and b of view 1: the convention of cpn_epipolar_lines' F and of cpn_camera_path at t = 1.
+ *   intrinsics (B, 2, 4, 4) fp32, a pinhole without skew per view: fx, fy, cx, cy = entries 0, 5, 2, 6; the normalised point
+ *     of pixel (x, y) is ((x - cx) / fx, (y - cy) / fy, 1), no half-pixel offset (as cpn_depth_points).
+ *   the Sampson residual of the pixel pair (a of view 0, b of view 1) under E, in pixels, in float64 from the fp32 inputs,
+ *     one rounding per operation, sums left to right:  (E b)_i = (E_i0 b_0 + E_i1 b_1) + E_i2, (E^T a)_j likewise down the
+ *     columns, E_0j = t_1 R_2j - t_2 R_1j, E_1j = t_2 R_0j - t_0 R_2j, E_2j = t_0 R_1j - t_1 R_0j;
+ *     n = (a_0 (E b)_0 + a_1 (E b)_1) + (E b)_2;  g = ((E b)_0 / fx0, (E b)_1 / fy0, (E^T a)_0 / fx1, (E^T a)_1 / fy1);
+ *     D = ((g_0^2 + g_1^2) + g_2^2) + g_3^2;  r = n / sqrt(D).  r does not count (NaN) where D <= 0 or n, D or r is not finite.
+ * cpn_match_fields: ONE launch for both directions and all pairs, one thread per pixel p = (x, y) of the S x S grid, S a
+ *   multiple of h.  u = (S / h) . F.interpolate(flow_d, S, mode="bilinear")(p) and q = p + u in fp32; inside = 0 <= q_x <= S - 1
+ *   and 0 <= q_y <= S - 1 (aux_outputs._inside); w = the other direction's upsampled flow read at q as utils.warp and
+ *   grid_sample (bilinear, zeros padding, align_corners=False) read it, a tap outside contributing 0;
+ *   cycle = sqrt((u_x + w_x)^2 + (u_y + w_y)^2) in fp32: the value cycle_masks and cpn_flow_panels threshold at 10, in their
+ *   expression sequence.  epi = the residual above rounded once to fp32, of (a, b) = (p, q) for d = 0 and (q, p) for d = 1.
+ *   q (2, B, S, S, 2), cycle (2, B, S, S), epi (2, B, S, S) fp32, inside (2, B, S, S) bytes: every element is written.  A
+ *   non-finite flow gives inside = 0 and a non-finite cycle and reads no tap.  1 <= B <= 32767, S <= 16384, 2 B S S < 2^31
+ *   (CPN_E_SHAPE otherwise).
+ * cpn_compact_matches: cpn_compact_points' deterministic TWO launches (CPN_COMPACT_TILE, CPN_COMPACT_FINISH) on matches.  keep
+ *   (2, B, S, S) bytes (non-zero = kept), q, cycle, epi as above -> per pair, with cap = 2 S S: xy (B, cap, 4) fp32 =
+ *   (x0, y0, x1, y1), view 0's point first whatever the direction, err (B, cap, 2) fp32 = (cycle, epi), count (B) int32; the
+ *   kept matches in ascending (direction, row, column) order, rows count[b] and beyond left untouched.  scratch:
+ *   cpn_compact_matches_scratch(B, S) ints (0 for a shape the kernels do not take).  No atomics: two runs, the same bytes.
+ * cpn_refine_pose: robust Gauss-Newton on the residuals of the matches, ONE launch, one workgroup per pair.  xy (B, N, 4) fp32
+ *   with count (B) int32 on the device (rows beyond min(max(count, 0), N) are never read), iters >= 0, scale_px > 0.  State per
+ *   pair, float64: R and a unit t from rel_pose, t = t0 / |t0|.  Pass k = 0, 1, ..: every match i whose residual r_i counts
+ *   adds, with J_ik = dn / sqrt(D) - (n dD) / ((2 D) sqrt(D)) for the six parameters (w: R <- exp([w]x) R; then dt),
+ *   dE_k = [t]x [e_k]x R (k < 3) and [e_(k-3)]x R, dn = a^T dE_k b, dD = 2 (((g_0 (dE_k b)_0 / fx0 + g_1 (dE_k b)_1 / fy0) +
+ *   g_2 (dE_k^T a)_0 / fx1) + g_3 (dE_k^T a)_1 / fy1), and the weight w_i = 1 / u^2, u = 1 + (r_i / scale_px)^2:
+ *   H_jk += (w_i J_ij) J_ik (j <= k), g_j += (w_i J_ij) r_i, cost += ((r_i r_i) / 2) / u, sum w, the number of matches that
+ *   count.  Thread t adds the matches t, t + 256, .. in ascending order; the 64 lanes of a wave by the xor butterfly 32 .. 1; the
+ *   four waves as (0 + 1) + (2 + 3).  While k < iters: A = H, A_jj = H_jj + 1e-3 H_jj, the translation block
+ *   += (tr H / 6) t t^T (the gauge: the residual cannot see the length of t); delta = -A^-1 g by Cholesky; a pivot <= 0 or a
+ *   value that is not finite leaves the state as it is, sets status 1 and ends the pair's passes.  Otherwise
+ *   R <- exp([delta_w]x) R by Rodrigues (the identity below an angle of 1e-12), t <- (t + delta_t) / |t + delta_t|.
+ *   pose (B, 4, 4) fp32 = [R | |t0| t], last row 0 0 0 1: the translation keeps the length it came with.  stats (B, 8) f64:
+ *   the cost of pass 0; the cost, the sum of weights and the number of matches that count of the last pass (the state that is
+ *   returned); the angles in degrees between R and rel_pose's rotation (2 asin(|R - R0|_F / (2 sqrt 2))) and between t and
+ *   t0 / |t0| (2 asin(|t - t0 / |t0|| / 2)); the updates made; status: 0 ok, 1 a failed solve, 2 nothing to do (count <= 0,
+ *   |t0| == 0, a non-finite pose or iters == 0): then pose is rel_pose's 16 values and the other seven stats are 0.
+ *   No atomics: bit-reproducible, and a pair's result does not depend on the batch around it.                               */
+int cpn_match_fields(const float* flow0, const float* flow1, const float* intrinsics, const float* rel_pose, int B, int S, int h,
+                     float* q, float* cycle, float* epi, uint8_t* inside, void* stream);
+int cpn_compact_matches_scratch(int B, int S);
+int cpn_compact_matches(const uint8_t* keep, const float* q, const float* cycle, const float* epi, int B, int S, int* scratch,
+                        float* xy, float* err, int* count, void* stream);
+int cpn_refine_pose(const float* xy, const int* count, const float* intrinsics, const float* rel_pose, int B, int N, int iters,
+                    double scale_px, float* pose, double* stats, void* stream);
 
 #ifdef __cplusplus
 }
