@@ -8,7 +8,8 @@ IEEE operation sequence bit for bit (sample coordinates / tap indices); ssim_war
 sampling coordinates of the flow warp (its window sums name their FMAs), and summaries.hip, which shares them;
 novel_views.hip for the one-rounding-per-operation sums of its resample and its byte pack; epipolar.hip for the float64
 operation sequence of its fundamental matrices and line end points; point_cloud.hip for that of its points and votes; matches.hip
-for the flow warp's fp32 sequence and the float64 sequence of its residuals, Jacobians and sums.
+for the flow warp's fp32 sequence and the float64 sequence of its residuals, Jacobians and sums; splat.hip for the float64
+sequence of its projection.
 """
 import os
 import subprocess
@@ -56,6 +57,7 @@ UNITS = [
     ("epipolar.hip", ["-ffp-contract=off"]),               # one rounding per float64 operation of the line geometry
     ("point_cloud.hip", ["-ffp-contract=off"]),            # one rounding per float64 operation of the points and the votes
     ("matches.hip", ["-ffp-contract=off"]),                # flow_warp.h's fp32 sequence; float64 residuals, Jacobians and sums
+    ("splat.hip", ["-ffp-contract=off"]),                  # one rounding per float64 operation of the projection
 ]
 
 

@@ -138,6 +138,11 @@ class PointCloud:
         with open(path, "wb") as f:
             f.write(self.ply_bytes(b))
 
+    def frames(self, poses: torch.Tensor, intrinsics: torch.Tensor, H: int, W: int, **kwargs) -> Dict[str, torch.Tensor]:
+        """The cloud as the cameras `poses` (K, B, 4, 4) see it, on the device: coponerf_amd.splat.draw(self, ...)."""
+        from .splat import draw
+        return draw(self, poses, intrinsics, H, W, **kwargs)
+
 
 def ply_bytes(xyz: np.ndarray, rgb: np.ndarray) -> bytes:
     """A binary little-endian PLY of n vertices: xyz (n, 3) float32, rgb (n, 3) uint8; the header is built here, on the host."""

@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define CPN_ABI_VERSION 12   /* cpn_attend_units (round 7), cpn_ssim_warp* (round 8), cpn_image_metrics* (round 9), summaries.hip (round 10), lpips.hip (round 11), novel_views.hip (round 12), epipolar.hip (round 13), cpn_lpips_*_bwd (round 14), point_cloud.hip (round 15) and matches.hip (round 16) are additive - symbols added, none altered: the version stays */
+#define CPN_ABI_VERSION 12   /* cpn_attend_units (round 7), cpn_ssim_warp* (round 8), cpn_image_metrics* (round 9), summaries.hip (round 10), lpips.hip (round 11), novel_views.hip (round 12), epipolar.hip (round 13), cpn_lpips_*_bwd (round 14), point_cloud.hip (round 15), matches.hip (round 16) and splat.hip (round 17) are additive - symbols added, none altered: the version stays */
 
 #define CPN_E_ARG   (-1)   /* bad argument (null pointer, size, alignment) */
 #define CPN_E_SHAPE (-2)   /* shape not supported by the compiled tiles    */
@@ -916,6 +916,48 @@ int cpn_compact_matches(const uint8_t* keep, const float* q, const float* cycle,
                         float* xy, float* err, int* count, void* stream);
 int cpn_refine_pose(const float* xy, const int* count, const float* intrinsics, const float* rel_pose, int B, int N, int iters,
                     double scale_px, float* pose, double* stats, void* stream);
+
+/* ==== z-buffered views of a point cloud, and their score against a photo (round 17) ======================================
+ * What a caller does with a viewer on another machine to look at cpn_compact_points' cloud, and a check of depth and pose
+ * against a photo that needs no ground truth.  The symbols are additive: the ABI version stays.  The footprint, the fill and
+ * the tie rule below are THIS LIBRARY'S definitions: there is no perspective-sized point, no blending and no antialiasing.
+ * Conventions (cpn_depth_points'): xyz (B, cap, 3) fp32 in the reference frame, rgb (B, cap, 3) bytes, count (B) int32 on the
+ *   device - rows beyond min(max(count[b], 0), cap) are never read; poses (K, B, 4, 4) fp32, camera to reference, rigid: the
+ *   inverse is [R^T | -R^T t]; intrinsics (B, 4, 4) fp32 of the OUTPUT image (fx, fy, cx, cy = entries 0, 5, 2, 6), no
+ *   half-pixel offset: pixel (r, c) is (u, v) = (c, r).  The output image is H x W, whatever grid the cloud came from.
+ *   float64 from the fp32 inputs, one rounding per operation, sums left to right.  1 <= K <= 255, K B H W < 2^31, 1 <= cap and
+ *   K B ceil(cap / 256) < 2^31 (CPN_E_SHAPE otherwise).
+ * cpn_splat_points: zbuf (K, B, H, W) uint64.  Every key is first set to all-ones (hipMemsetAsync), then ONE launch over
+ *   (camera k, pair b, point i).  With X the point and [R | t] the pose (k, b):
+ *   Y_j = (R_0j (X_0 - t_0) + R_1j (X_1 - t_1)) + R_2j (X_2 - t_2).  The point COUNTS iff X, the twelve entries of [R | t] and
+ *   fx, fy, cx, cy are finite, Y_z >= near (near > 0), u = (fx Y_x) / Y_z + cx and v = (fy Y_y) / Y_z + cy are finite and
+ *   below 2^30 in magnitude, and z32 = (float)Y_z is finite.  Its pixel is (c, r) = (floor(u + 0.5), floor(v + 0.5)), its
+ *   footprint the (2 radius + 1)^2 square of pixels around it, clipped to the image (0 <= radius <= 8), its key
+ *   (bits of z32) << 32 | i: the bit patterns of non-negative floats are ordered as their values, and of two points of equal
+ *   z32 the one of the lower index has the smaller key.  Every pixel of the footprint takes the minimum of its key and the
+ *   point's by a 64-bit unsigned integer atomic minimum.  This is the library's one atomic on a result path, and it keeps the
+ *   rule that two runs give the same bytes: the minimum of a set of integers does not depend on the order in which they arrive.
+ *   (A key that is read as already smaller than the point's skips the atomic: keys only decrease.)
+ * cpn_splat_resolve: ONE launch, one thread per output pixel.  The pixel's key is its own; if that is all-ones and fill > 0 it
+ *   is the smallest key of the (2 fill + 1)^2 neighbourhood of zbuf as cpn_splat_points left it, clipped to the image: holes
+ *   are filled from splatted pixels only, never from filled ones (0 <= fill <= 4).  A pixel is EMPTY if that key is all-ones
+ *   (or its low word is not below cap: no point wrote it).  index (K, B, H, W) int32 = the low word, -1 if empty; depth
+ *   (K, B, H, W) fp32 = the float of the high word, NaN if empty; frames (K, B, H, W, 3) bytes = rgb[b, index], or the bytes
+ *   (background, background >> 8, background >> 16) & 255 if empty (0 <= background < 2^24).  Every element of the three is
+ *   written; depth and index may be null.
+ * cpn_splat_score: frames and target (K, B, H, W, 3) bytes, index (K, B, H, W) int32 -> stats (K, B, 2) int64: n, the number of
+ *   pixels with index >= 0, and the sum over those pixels and their three channels of (frame - target)^2.  Integers, so exact
+ *   in any order, without atomics: a workgroup of the first launch adds CPN_SPLAT_SCORE_TILE pixels of one image into scratch
+ *   (cpn_splat_score_scratch(K, B, H, W) int64 values, 0 for a shape the kernels do not take), the second adds an image's
+ *   workgroups.  Two launches.                                                                                             */
+#define CPN_SPLAT_SCORE_TILE 4096
+int cpn_splat_points(const float* xyz, const int* count, const float* poses, const float* intrinsics, int K, int B, int cap, int H,
+                     int W, int radius, double near, unsigned long long* zbuf, void* stream);
+int cpn_splat_resolve(const unsigned long long* zbuf, const uint8_t* rgb, int K, int B, int cap, int H, int W, int fill,
+                      int background, uint8_t* frames, float* depth, int* index, void* stream);
+int cpn_splat_score_scratch(int K, int B, int H, int W);
+int cpn_splat_score(const uint8_t* frames, const int* index, const uint8_t* target, int K, int B, int H, int W, long long* scratch,
+                    long long* stats, void* stream);
 
 #ifdef __cplusplus
 }
