@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define CPN_ABI_VERSION 12   /* cpn_attend_units (round 7), cpn_ssim_warp* (round 8), cpn_image_metrics* (round 9), summaries.hip (round 10), lpips.hip (round 11), novel_views.hip (round 12), epipolar.hip (round 13), cpn_lpips_*_bwd (round 14), point_cloud.hip (round 15), matches.hip (round 16) and splat.hip (round 17) are additive - symbols added, none altered: the version stays */
+#define CPN_ABI_VERSION 12   /* cpn_attend_units (round 7), cpn_ssim_warp* (round 8), cpn_image_metrics* (round 9), summaries.hip (round 10), lpips.hip (round 11), novel_views.hip (round 12), epipolar.hip (round 13), cpn_lpips_*_bwd (round 14), point_cloud.hip (round 15), matches.hip (round 16), splat.hip (round 17) and mesh.hip (round 18) are additive - symbols added, none altered: the version stays */
 
 #define CPN_E_ARG   (-1)   /* bad argument (null pointer, size, alignment) */
 #define CPN_E_SHAPE (-2)   /* shape not supported by the compiled tiles    */
@@ -958,6 +958,67 @@ int cpn_splat_resolve(const unsigned long long* zbuf, const uint8_t* rgb, int K,
 int cpn_splat_score_scratch(int K, int B, int H, int W);
 int cpn_splat_score(const uint8_t* frames, const int* index, const uint8_t* target, int K, int B, int H, int W, long long* scratch,
                     long long* stats, void* stream);
+
+/* ==== TSDF fusion of the rendered depth maps and a surface-nets mesh (round 18) ===========================================
+ * What a caller does with a fusion library on another machine to get a SURFACE out of render_path's K depth maps: a depth map
+ * is a staircase (depth_ray is the depth of one of 2 x 64 samples), and a truncated signed distance averaged per voxel over
+ * the views places the surface between the steps.  The symbols are additive: the ABI version stays.  The integration rule, the
+ * vertex rule and the observed-cell rule below are THIS LIBRARY'S definitions.
+ * Conventions are cpn_depth_points' and cpn_splat_points': intrinsics (B, 4, 4) fp32 (fx, fy, cx, cy = entries 0, 5, 2, 6), no
+ *   half-pixel offset; poses (K, B, 4, 4) fp32, camera to reference, rigid, the inverse [R^T | -R^T t] in cpn_splat_points'
+ *   expression Y_j = (R_0j (X_0 - t_0) + R_1j (X_1 - t_1)) + R_2j (X_2 - t_2); the pixel grid is the window (y0, x0, h, w) of an
+ *   S x S image; depth (K, B, h w) fp32, VALID iff finite and 0 < d < 10; valid (K, B, h w) bytes (forward's valid_mask as
+ *   render_path returns it), rgb (K, B, h w, 3) fp32 in [-1, 1].  float64 from the fp32 inputs, one rounding per operation, sums
+ *   left to right from 0, ONE rounding to fp32 at a store; bytes by cpn_pack_frames' rule in fp32 as cpn_compact_points applies
+ *   it: rint(min(max((x + 1) * 127.5, 0), 255)), NaN -> 0, x the float64 value rounded once to fp32.  1 <= K <= 255.  No atomics
+ *   anywhere: two runs give the same bytes, and a pair's result does not depend on the batch around it.
+ * The volume of pair b: a lattice of Nx x Ny x Nz voxels (each >= 2, host integers shared by the batch), voxel (ix, iy, iz) at
+ *   X = origin[b] + (ix sx, iy sy, iz sz) in the reference frame (view 0's), X_x = o_x + ix * s_x and likewise; origin (B, 3),
+ *   spacing (B, 3) and trunc (B) fp32 ON THE DEVICE.  Arrays are (B, Nz, Ny, Nx), x fastest.
+ * cpn_tsdf_integrate: ONE launch, one thread per voxel, the views in ascending order inside it.  For view k: Y = pose^-1 X; the
+ *   view is skipped unless Y_z > 0 and Y is finite; u = (fx Y_x) / Y_z + cx, v = (fy Y_y) / Y_z + cy,
+ *   (c, r) = (floor(u + 0.5) - x0, floor(v + 0.5) - y0); skipped unless 0 <= c < w and 0 <= r < h (a NaN fails), the depth d at
+ *   (r, c) is valid and the valid byte there is not 0; s = d - Y_z, the signed distance along the optical axis (depth_ray is a
+ *   z-depth); skipped if s < -trunc; otherwise the view UPDATES the voxel with f = min(1, s / trunc) and the pixel's rgb.
+ *   tsdf (B, Nz, Ny, Nx) fp32 = (the sum of f over the updating views) / their number n, 1 if n = 0; weight, bytes, = n; colour
+ *   (B, Nz, Ny, Nx, 3) fp32 = (the sum of the updating views' rgb) / n, 0 if n = 0.  Every element of the three is written.  A
+ *   pair whose trunc or any spacing entry is not finite or not > 0 gets the empty volume (weight 0, tsdf 1, colour 0).
+ *   K B h w < 2^31, B Nx Ny Nz < 2^31, the window inside the grid (CPN_E_SHAPE otherwise).
+ * Extraction: naive surface nets, two stages, each cpn_compact_points' deterministic TWO launches (CPN_COMPACT_TILE,
+ *   CPN_COMPACT_FINISH).  INSIDE means tsdf < 0 (an exact 0, and a NaN, is outside).  Cell (cx, cy, cz), 0 <= c < N - 1, has corner
+ *   i = dx + 2 dy + 4 dz at voxel (cx + dx, cy + dy, cz + dz).  It is OBSERVED iff all eight corners have weight >= min_weight
+ *   (1 <= min_weight <= 255) and ACTIVE iff it is observed and its corners are neither all inside nor all outside.  Its twelve
+ *   edges, as (lower corner, upper corner), in this order: the x-edges (0,1) (2,3) (4,5) (6,7), the y-edges (0,2) (1,3) (4,6)
+ *   (5,7), the z-edges (0,4) (1,5) (2,6) (3,7) - each group in (0,0), (1,0), (0,1), (1,1) order of the other two offsets.
+ *   1 <= B <= 65535, B cells < 2^31 and 3 B voxels < 2^31 (CPN_E_SHAPE otherwise; the _scratch functions return 0).
+ * cpn_surface_vertices: the cells of a pair form one sequence in (cz, cy, cx) order, cells = (Nx-1)(Ny-1)(Nz-1) of them; every
+ *   active cell gets one vertex, in that order.  Every edge (a, b) whose ends differ in INSIDE contributes its zero crossing
+ *   t = f_a / (f_a - f_b) from the lower corner: the point (dx, dy, dz) of corner a with t added along the edge's axis, and the
+ *   colour (1 - t) colour_a + t colour_b per channel.  p = (the sum of the points) / m and the colour (the sum of the colours) / m
+ *   over the m contributing edges, in the edge order; the vertex is origin + ((cx, cy, cz) + p) * spacing per axis, rounded once
+ *   to fp32, its colour the byte rule above.  vert_xyz (B, capv, 3) fp32, vert_rgb (B, capv, 3) bytes, nvert (B) int32 = the TRUE
+ *   number of active cells, even above capv; rows at and beyond min(nvert, capv) are left untouched.  cell_vertex (B, cells)
+ *   int32 = the vertex row of every active cell (even a row >= capv), -1 elsewhere: every element is written.  scratch:
+ *   cpn_surface_vertices_scratch(B, Nx, Ny, Nz) ints.  capv >= 1.
+ * cpn_surface_faces: the lattice edges of a pair form one sequence e = 3 voxel + axis, voxels in (iz, iy, ix) order.  Edge (p, a)
+ *   runs from voxel p to p + e_a and EXISTS iff p_a + 1 < N_a.  With (a, b, c) the cyclic order of the axes its four cells are
+ *   (p_b - 1, p_c - 1), (p_b, p_c - 1), (p_b, p_c), (p_b - 1, p_c) at p_a, their vertices v00, v10, v11, v01.  The edge is SELECTED
+ *   iff it exists, its ends differ in INSIDE, the four cells lie in the lattice and all four are active (cell_vertex >= 0:
+ *   cpn_surface_vertices' output, made with the same tsdf).  A selected edge writes two consecutive triangles:
+ *   (v00, v10, v11), (v00, v11, v01) if the lower end p is inside, (v00, v11, v10), (v00, v01, v11) otherwise - the normals point
+ *   from inside to outside, towards the cameras' free space.  faces (B, capf, 3) int32, nface (B) int32 = the TRUE number of
+ *   triangles (2^31 - 1 if it is larger); rows at and beyond capf are left untouched.  scratch:
+ *   cpn_surface_faces_scratch(B, Nx, Ny, Nz) ints.  capf >= 1.                                                             */
+int cpn_tsdf_integrate(const float* depth, const uint8_t* valid, const float* rgb, const float* poses, const float* intrinsics,
+                       const float* origin, const float* spacing, const float* trunc, int K, int B, int S, int y0, int x0, int h,
+                       int w, int Nx, int Ny, int Nz, float* tsdf, uint8_t* weight, float* colour, void* stream);
+int cpn_surface_vertices_scratch(int B, int Nx, int Ny, int Nz);
+int cpn_surface_vertices(const float* tsdf, const uint8_t* weight, const float* colour, const float* origin, const float* spacing,
+                         int B, int Nx, int Ny, int Nz, int min_weight, int capv, int* scratch, float* vert_xyz, uint8_t* vert_rgb,
+                         int* nvert, int* cell_vertex, void* stream);
+int cpn_surface_faces_scratch(int B, int Nx, int Ny, int Nz);
+int cpn_surface_faces(const float* tsdf, const int* cell_vertex, int B, int Nx, int Ny, int Nz, int capf, int* scratch, int* faces,
+                      int* nface, void* stream);
 
 #ifdef __cplusplus
 }
