@@ -3,4 +3,4 @@
 `from coponerf_amd import CoPoNeRF; CoPoNeRF.CoPoNeRF(n_view=2)` mirrors the reference's
 `from models import CoPoNeRF; CoPoNeRF.CoPoNeRF(n_view=2)`.
 """
-__all__ = ["CoPoNeRF", "render", "synthetic", "splat", "mesh", "_hip"]
+__all__ = ["CoPoNeRF", "render", "synthetic", "splat", "mesh", "raster", "_hip"]

@@ -8,7 +8,7 @@ signed distance averaged per voxel over the K views of render_path places the su
   integrate     the K views of render_path -> a Volume: cpn_tsdf_integrate
   Volume        tsdf / weight / colour on the device; extract() -> a Mesh: cpn_surface_vertices, cpn_surface_faces
   Mesh          xyz / rgb / nvert / faces / nface on the device; numpy(b) is the one host read, ply_bytes / save write a binary
-                PLY, cloud() hands the vertices to splat.draw as a PointCloud
+                PLY, cloud() hands the vertices to splat.draw as a PointCloud, frames() the triangles to raster.draw
   reconstruct   novel_views.render_path, integrate, extract
 
 **The TSDF rule (the projective distance along z, the nearest pixel, uniform weights, the colour averaged over every updating
@@ -16,7 +16,8 @@ view), the surface-nets vertex rule, the observed-cell rule and the defaults of 
 package's definitions (include/coponerf_hip.h), not the reference's, which has no mesh.  None of it has been tried on a trained
 checkpoint, because none is available offline.**  Surface nets can produce non-manifold edges in ambiguous cells.  The box of
 `bounds` is the raw extent of the valid points, so outliers stretch it: pass your own.  Left out: marching cubes, normals,
-decimation and smoothing, texture maps, weighting by view angle, a triangle rasteriser.  Writing the PLY is the only file I/O.
+decimation and smoothing, texture maps, weighting by view angle (coponerf_amd.raster draws the triangles: Mesh.frames).  Writing
+the PLY is the only file I/O.
 """
 from __future__ import annotations
 
@@ -195,8 +196,13 @@ class Mesh:
 
     def cloud(self) -> PointCloud:
         """The vertices as a PointCloud (the count clamped to the capacity, on the device): splat.draw(mesh.cloud(), ...)
-        previews the mesh's vertices without a rasteriser of its own."""
+        previews the mesh's vertices alone; frames() draws its triangles."""
         return PointCloud(self.xyz, self.rgb, torch.clamp(self.nvert, max=int(self.xyz.shape[1])))
+
+    def frames(self, poses: torch.Tensor, intrinsics: torch.Tensor, H: int, W: int, **kwargs) -> Dict[str, torch.Tensor]:
+        """The mesh's triangles as the cameras `poses` (K, B, 4, 4) see them, on the device: coponerf_amd.raster.draw(self, ...)."""
+        from .raster import draw
+        return draw(self, poses, intrinsics, H, W, **kwargs)
 
 
 def ply_bytes(xyz: np.ndarray, rgb: np.ndarray, faces: np.ndarray) -> bytes:

@@ -12,7 +12,8 @@ The footprint rule (a square of 2 radius + 1 pixels, whatever the depth), the fi
 point of the splatted neighbourhood, once), the tie rule (equal depths fall to the lower index) and cross_view_check are this
 package's definitions (include/coponerf_hip.h), not the reference's, which has no point renderer.  None of it has been tried
 on a trained checkpoint, because none is available offline.  Left out: perspective-sized points, blending and antialiasing,
-triangles (coponerf_amd.mesh makes a mesh; Mesh.cloud() hands its vertices to draw), video encoding.
+triangles (coponerf_amd.mesh makes a mesh and coponerf_amd.raster draws it; Mesh.cloud() hands its vertices to draw), video
+encoding.
 """
 from __future__ import annotations
 

@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define CPN_ABI_VERSION 12   /* cpn_attend_units (round 7), cpn_ssim_warp* (round 8), cpn_image_metrics* (round 9), summaries.hip (round 10), lpips.hip (round 11), novel_views.hip (round 12), epipolar.hip (round 13), cpn_lpips_*_bwd (round 14), point_cloud.hip (round 15), matches.hip (round 16), splat.hip (round 17) and mesh.hip (round 18) are additive - symbols added, none altered: the version stays */
+#define CPN_ABI_VERSION 12   /* cpn_attend_units (round 7), cpn_ssim_warp* (round 8), cpn_image_metrics* (round 9), summaries.hip (round 10), lpips.hip (round 11), novel_views.hip (round 12), epipolar.hip (round 13), cpn_lpips_*_bwd (round 14), point_cloud.hip (round 15), matches.hip (round 16), splat.hip (round 17), mesh.hip (round 18) and raster.hip (round 19) are additive - symbols added, none altered: the version stays */
 
 #define CPN_E_ARG   (-1)   /* bad argument (null pointer, size, alignment) */
 #define CPN_E_SHAPE (-2)   /* shape not supported by the compiled tiles    */
@@ -1019,6 +1019,64 @@ int cpn_surface_vertices(const float* tsdf, const uint8_t* weight, const float* 
 int cpn_surface_faces_scratch(int B, int Nx, int Ny, int Nz);
 int cpn_surface_faces(const float* tsdf, const int* cell_vertex, int B, int Nx, int Ny, int Nz, int capf, int* scratch, int* faces,
                       int* nface, void* stream);
+
+/* ==== z-buffered views of a triangle mesh (round 19) =======================================================================
+ * What a caller does with a viewer on another machine to look at cpn_surface_faces' mesh: its TRIANGLES drawn into any camera, so
+ * that the surface is closed where it is closed and hides what lies behind it.  The symbols are additive: the ABI version stays.
+ * NO CLIPPING, the 1/256-pixel snap, the fill rule, the tie rule and the headlight below are THIS LIBRARY'S definitions; there is
+ * no antialiasing, no blending, no texture and no smooth normal.
+ * Conventions are cpn_splat_points', word for word: xyz (B, capv, 3) fp32 in the reference frame, rgb (B, capv, 3) bytes, nvert (B)
+ *   int32 and faces (B, capf, 3) int32, nface (B) int32 on the device as cpn_surface_vertices and cpn_surface_faces leave them;
+ *   poses (K, B, 4, 4) fp32, camera to reference, rigid: the inverse is [R^T | -R^T t]; intrinsics (B, 4, 4) fp32 of the OUTPUT image
+ *   (fx, fy, cx, cy = entries 0, 5, 2, 6), no half-pixel offset: pixel (c, r) has its centre at (u, v) = (c, r).  float64 from the
+ *   fp32 inputs, one rounding per operation, sums left to right.  1 <= K <= 255, K B H W < 2^31, 1 <= H, W <= 16384, capv, capf >= 1
+ *   and K B ceil(capf / 256) < 2^31 (CPN_E_SHAPE otherwise).
+ * A face f of pair b (a row of faces, 0 <= f < capf) in camera (k, b) is DRAWABLE iff all of this holds, tested in this order:
+ *   the twelve entries of [R | t] and fx, fy, cx, cy are finite; each of its three indices lies in [0, min(max(nvert[b], 0), capv))
+ *   (nothing is read through one that does not); each vertex X is finite; with
+ *   Y_j = (R_0j (X_0 - t_0) + R_1j (X_1 - t_1)) + R_2j (X_2 - t_2), Y_z >= near, Y_z > 0 and (float)Y_z is finite AT ALL THREE
+ *   VERTICES - there is no clipping: a face with one vertex nearer than near is not drawn at all; the snapped coordinates
+ *   SX = floor(256 u + 0.5), SY = floor(256 v + 0.5) of u = (fx Y_x) / Y_z + cx, v = (fy Y_y) / Y_z + cy are below 2^29 in
+ *   magnitude (2^21 pixels; a NaN fails), from here on int64; and the doubled area
+ *   D(a, b, c) = (SX_b - SX_a)(SY_c - SY_a) - (SY_b - SY_a)(SX_c - SX_a) of its vertices in the order stored is not 0.
+ *   The face is FRONT iff that D < 0: with x right, y down, z forward and fx fy > 0, D has the sign of Y_0 . ((Y_1 - Y_0) x (Y_2 - Y_0)),
+ *   which is negative when the normal cpn_surface_faces winds (towards the cameras' free space) points at the camera.
+ *   CANONICAL ORDER: the three vertices sorted by ascending index, then the second and third exchanged if D of that order is
+ *   negative; A = |D| > 0.  Everything below uses the vertices 0, 1, 2 of this order, so no result depends on the order in which
+ *   a face stores its indices (weight j of `bary` is stored at the position the vertex has in the face's row).
+ *   Edge functions at the pixel centre (256 c, 256 r): w_0 = E(1, 2), w_1 = E(2, 0), w_2 = E(0, 1) with
+ *   E(a, b) = (SX_b - SX_a)(256 r - SY_a) - (SY_b - SY_a)(256 c - SX_a); w_0 + w_1 + w_2 = A.  Edge a -> b OWNS the centres on it iff
+ *   SY_b - SY_a < 0, or SY_b = SY_a and SX_b - SX_a > 0 (a left edge, or a top edge: the TOP-LEFT RULE).  The face COVERS the
+ *   pixel iff for each edge w > 0, or w = 0 and the edge owns: a centre on an edge that two faces of a sheet share runs the two
+ *   ways in them and belongs to exactly one, and so does a centre on a vertex of the sheet.
+ *   q_i = (double)w_i / Y_z,i; s = (q_0 + q_1) + q_2; the depth z = (double)A / s (the perspective-correct camera z), rounded ONCE
+ *   to fp32.
+ * cpn_raster_faces: zbuf (K, B, H, W) uint64.  Every key is first set to all-ones (hipMemsetAsync), then ONE launch over
+ *   (camera k, pair b, face f), f in [0, min(max(nface[b], 0), capf)): rows beyond are never read.  cull = 0 draws every drawable
+ *   face, cull = 1 only the front ones; near > 0.  Every pixel that the face covers, of its bounding box clipped to the image,
+ *   takes the minimum of its key and (bits of the fp32 depth) << 32 | f by cpn_splat_points' 64-bit unsigned atomic minimum
+ *   (behind the same relaxed load): the nearest face wins, of equal fp32 depths the lower f, and two runs give the same bytes.
+ *   A thread sets a face up and walks the box itself if it holds at most CPN_RASTER_SMALL pixels; the faces with larger boxes
+ *   are then taken by their whole wave, one at a time, its 64 lanes striding over the box.
+ *   The launch has min(ceil(capf / 256), CPN_RASTER_TILES) workgroups per (camera, pair), which stride over the pair's faces up to
+ *   nface: its size depends on nothing in device memory, and its cost hardly on the room a mesh has to spare.
+ * cpn_raster_resolve: ONE launch, one thread per output pixel; there is no fill pass, a triangle surface has no holes between
+ *   samples.  A pixel is EMPTY if its key is all-ones or the key's low word f is not below capf or face f is not drawable with
+ *   near = 0 (nothing is read for it).  Otherwise index (K, B, H, W) int32 = f; depth (K, B, H, W) fp32 = the float of the high
+ *   word; bary (K, B, H, W, 3) fp32 = (float)(q_j / s); frames (K, B, H, W, 3) bytes, with byte(x) = floor(x + 0.5) clamped to
+ *   [0, 255] (a NaN gives 0): shade = 0: byte(((q_0 c_0 + q_1 c_1) + q_2 c_2) / s) per channel of the vertices' bytes c;
+ *   shade = 1, a HEADLIGHT: the grey byte(255 sh), sh = |n . d| / sqrt((n . n)(d . d)), 0 if sh is not finite, with
+ *   n = (Y_1 - Y_0) x (Y_2 - Y_0), d = ((c - cx) / fx, (r - cy) / fy, 1) and every dot product (a_0 b_0 + a_1 b_1) + a_2 b_2.
+ *   Empty pixels: index -1, depth and bary NaN, frames (background, background >> 8, background >> 16) & 255
+ *   (0 <= background < 2^24).  Every element is written; depth, index and bary may be null.                                  */
+#define CPN_RASTER_SMALL 64
+#define CPN_RASTER_TILES 256
+int cpn_raster_faces(const float* xyz, const int* nvert, const int* faces, const int* nface, const float* poses,
+                     const float* intrinsics, int K, int B, int capv, int capf, int H, int W, int cull, double near,
+                     unsigned long long* zbuf, void* stream);
+int cpn_raster_resolve(const unsigned long long* zbuf, const float* xyz, const uint8_t* rgb, const int* nvert, const int* faces,
+                       const float* poses, const float* intrinsics, int K, int B, int capv, int capf, int H, int W, int shade,
+                       int background, uint8_t* frames, float* depth, int* index, float* bary, void* stream);
 
 #ifdef __cplusplus
 }
