@@ -10,7 +10,8 @@ novel_views.hip for the one-rounding-per-operation sums of its resample and its 
 operation sequence of its fundamental matrices and line end points; point_cloud.hip for that of its points and votes; matches.hip
 for the flow warp's fp32 sequence and the float64 sequence of its residuals, Jacobians and sums; splat.hip for the float64
 sequence of its projection; mesh.hip for that of its signed distances and vertices; raster.hip for that of its projection,
-depths and colours.
+depths and colours.  The last five share pinhole.h (the float64 camera; its bodies also switch contraction off by pragma) and
+splat and raster zbuffer.h (the key, its atomic minimum, the resolve stores, the clear and the image checks).
 """
 import os
 import subprocess

@@ -14,10 +14,11 @@
 //                             pass, no partials in HBM, no inter-workgroup synchronisation.  Pass `iters` only measures.
 //
 // The residual is float64 from the fp32 inputs, one rounding per operation (-ffp-contract=off), sums left to right:
-// tests/matches_ref.py restates all three in numpy.
+// tests/matches_ref.py restates all three in numpy.  Cam and Pose are pinhole.h's.
 #include "common.h"
 #include "compact.h"
 #include "flow_warp.h"
+#include "pinhole.h"
 
 #include <math.h>
 
@@ -27,14 +28,7 @@ constexpr int NT = 256;
 constexpr int PTW = 32, PTH = NT / PTW;                    // match fields: the tile of one workgroup
 constexpr int NSUM = 30;                                   // refinement: H (21), g (6), cost, sum of weights, finite matches
 
-struct Cam {
-    double fx, fy, cx, cy;
-};
-__device__ __forceinline__ Cam load_cam(const float* __restrict__ Kb) {
-    return Cam{(double)Kb[0], (double)Kb[5], (double)Kb[2], (double)Kb[6]};
-}
-
-// E = [t]x R, row-major
+// E = [t]x R, row-major (a Pose's R[3][3] is such a matrix)
 __device__ __forceinline__ void essential(const double* R, const double* t, double* E) {
     for (int j = 0; j < 3; ++j) {
         E[0 + j] = t[1] * R[6 + j] - t[2] * R[3 + j];
@@ -113,12 +107,9 @@ __global__ __launch_bounds__(NT) void match_fields_kernel(const float* __restric
     // the pair as (view 0's point, view 1's point)
     const double px = (double)gx, py = (double)gy, qx = (double)mx, qy = (double)my;
     const Cam k0 = load_cam(intrinsics + ((size_t)b * 2 + 0) * 16), k1 = load_cam(intrinsics + ((size_t)b * 2 + 1) * 16);
-    double R[9], tr[3], E[9];
-    for (int r = 0; r < 3; ++r) {
-        for (int c = 0; c < 3; ++c) R[3 * r + c] = (double)rel_pose[(size_t)b * 16 + 4 * r + c];
-        tr[r] = (double)rel_pose[(size_t)b * 16 + 4 * r + 3];
-    }
-    essential(R, tr, E);
+    const Pose rel = load_pose(rel_pose + (size_t)b * 16);
+    double E[9];
+    essential(&rel.R[0][0], rel.t, E);
     const Sampson s = d ? sampson(E, k0, k1, qx, qy, px, py) : sampson(E, k0, k1, px, py, qx, qy);
     const double res = s.n / sqrt(s.D);
     const float e32 = residual_ok(s, res) ? (float)res : __builtin_nanf("");
@@ -253,20 +244,19 @@ __global__ __launch_bounds__(NT) void refine_pose_kernel(const float* __restrict
     n = n < 0 ? 0 : (n > N ? N : n);
     double len0 = 0.0, cost0 = 0.0;
     if (tid == 0) {
-        bool fin = true;
-        double t0[3];
+        const Pose rel = load_pose(P);
+        bool fin = true;                                   // finite64, this unit's test: not pinhole.h's pose_finite
         for (int r = 0; r < 3; ++r) {
             for (int c = 0; c < 3; ++c) {
-                st.R[3 * r + c] = (double)P[4 * r + c];
-                fin = fin && finite64(st.R[3 * r + c]);
+                st.R[3 * r + c] = rel.R[r][c];
+                fin = fin && finite64(rel.R[r][c]);
             }
-            t0[r] = (double)P[4 * r + 3];
-            fin = fin && finite64(t0[r]);
+            fin = fin && finite64(rel.t[r]);
         }
-        len0 = sqrt((t0[0] * t0[0] + t0[1] * t0[1]) + t0[2] * t0[2]);
+        len0 = sqrt((rel.t[0] * rel.t[0] + rel.t[1] * rel.t[1]) + rel.t[2] * rel.t[2]);
         st.go = (fin && len0 > 0.0 && finite64(len0) && n > 0 && iters > 0) ? 1 : 0;
         if (st.go) {
-            for (int r = 0; r < 3; ++r) st.t[r] = t0[r] / len0;
+            for (int r = 0; r < 3; ++r) st.t[r] = rel.t[r] / len0;
             set_matrices(st);
         }
     }

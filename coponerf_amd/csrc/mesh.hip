@@ -9,10 +9,11 @@
 //   face_write_kernel         selected edge writes the two triangles of the quad of its four cells.
 //
 // No atomics.  float64 from the fp32 inputs, one rounding per operation (-ffp-contract=off), sums left to right, one rounding
-// to fp32 at a store: tests/mesh_ref.py restates it in numpy.
+// to fp32 at a store: tests/mesh_ref.py restates it in numpy.  The camera and the rule of a valid depth are pinhole.h's.
 #include "common.h"
 #include "byte_pack.h"
 #include "compact.h"
+#include "pinhole.h"
 
 #include <math.h>
 
@@ -26,7 +27,6 @@ struct Dims {
     int nx, ny, nz;
 };
 
-__device__ __forceinline__ bool depth_valid(float d) { return d > 0.0f && d < 10.0f; }      // cpn_depth_points' rule
 __device__ __forceinline__ bool positive(float v) { return v > 0.0f && v < __builtin_inff(); }     // finite and > 0
 
 __global__ __launch_bounds__(NT) void tsdf_integrate_kernel(const float* __restrict__ depth, const uint8_t* __restrict__ valid,
@@ -49,17 +49,13 @@ __global__ __launch_bounds__(NT) void tsdf_integrate_kernel(const float* __restr
         const double tr = (double)tr32;
         const double X[3] = {(double)og[0] + (double)ix * (double)sp[0], (double)og[1] + (double)iy * (double)sp[1],
                              (double)og[2] + (double)iz * (double)sp[2]};
-        const float* const Kb = intrinsics + (size_t)b * 16;
-        const double fx = (double)Kb[0], fy = (double)Kb[5], cx = (double)Kb[2], cy = (double)Kb[6];
+        const Cam cam = load_cam(intrinsics + (size_t)b * 16);
         const int hw = h * w;
         for (int k = 0; k < K; ++k) {
-            const float* const P = poses + ((size_t)k * B + b) * 16;
-            double d[3], Y[3];
-            for (int r = 0; r < 3; ++r) d[r] = X[r] - (double)P[4 * r + 3];
-            // [R^T | -R^T t] X = R^T (X - t): cpn_splat_points' expression
-            for (int j = 0; j < 3; ++j) Y[j] = ((double)P[j] * d[0] + (double)P[4 + j] * d[1]) + (double)P[8 + j] * d[2];
-            if (!(Y[2] > 0.0 && isfinite(Y[0]) && isfinite(Y[1]) && isfinite(Y[2]))) continue;
-            const double u = (fx * Y[0]) / Y[2] + cx, v = (fy * Y[1]) / Y[2] + cy;
+            double Y[3], u, v;
+            to_camera_centred(load_pose(poses + ((size_t)k * B + b) * 16), X, Y);
+            if (!(Y[2] > 0.0 && finite3(Y[0], Y[1], Y[2]))) continue;
+            project(cam, Y, u, v);
             const double c = floor(u + 0.5) - (double)x0, r = floor(v + 0.5) - (double)y0;
             if (!(c >= 0.0 && c < (double)w && r >= 0.0 && r < (double)h)) continue;          // outside the window, or NaN
             const size_t at = ((size_t)k * B + b) * hw + (size_t)((int)r * w + (int)c);

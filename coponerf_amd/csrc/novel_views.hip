@@ -15,6 +15,7 @@
 #include "common.h"
 #include "byte_pack.h"
 #include "jet.h"
+#include "pinhole.h"
 
 #include <math.h>
 
@@ -94,12 +95,8 @@ __global__ __launch_bounds__(NT) void camera_path_kernel(const float* __restrict
     const int i = blockIdx.x * NT + threadIdx.x;
     if (i >= K * B) return;
     const int k = i / B, b = i - k * B;
-    const float* const P = rel_pose + (size_t)b * 16;
-    double R[3][3], tr[3];
-    for (int r = 0; r < 3; ++r) {
-        for (int c = 0; c < 3; ++c) R[r][c] = (double)P[4 * r + c];
-        tr[r] = (double)P[4 * r + 3];
-    }
+    const Pose rel = load_pose(rel_pose + (size_t)b * 16);
+    const double(&R)[3][3] = rel.R, (&tr)[3] = rel.t;
     const double t = ts[k];
     double Q[3][3] = {{1.0, 0.0, 0.0}, {0.0, 1.0, 0.0}, {0.0, 0.0, 1.0}};
     if (t == 1.0) {                                        // the end of the path is view 1's camera itself, not its projection

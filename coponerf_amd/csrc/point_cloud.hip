@@ -9,11 +9,12 @@
 //                             of the workgroups before its own, ranks its own elements by wave ballots and writes: compact.h,
 //                             shared with matches.hip.  No atomics: an element's output row depends on the mask alone.
 //
-// The geometry is float64 from the fp32 inputs, one rounding per operation (-ffp-contract=off), sums left to right, and one
-// rounding to fp32 at the store: tests/point_cloud_ref.py restates it in numpy.
+// The geometry (pinhole.h's camera) is float64 from the fp32 inputs, one rounding per operation (-ffp-contract=off), sums left
+// to right, and one rounding to fp32 at the store: tests/point_cloud_ref.py restates it in numpy.
 #include "common.h"
 #include "byte_pack.h"
 #include "compact.h"
+#include "pinhole.h"
 
 #include <math.h>
 
@@ -22,48 +23,6 @@ namespace {
 constexpr int NT = 256;
 constexpr int TILE = CPN_COMPACT_TILE;
 static_assert(COMPACT_NT == NT, "the compaction kernels run 256 threads");
-
-struct Cam {
-    double fx, fy, cx, cy;
-};
-struct Pose {                                              // camera to reference: X = R p + t
-    double R[3][3], t[3];
-};
-
-__device__ __forceinline__ Cam load_cam(const float* __restrict__ Kb) {
-    return Cam{(double)Kb[0], (double)Kb[5], (double)Kb[2], (double)Kb[6]};
-}
-__device__ __forceinline__ Pose load_pose(const float* __restrict__ P) {
-    Pose o;
-    for (int r = 0; r < 3; ++r) {
-        for (int c = 0; c < 3; ++c) o.R[r][c] = (double)P[4 * r + c];
-        o.t[r] = (double)P[4 * r + 3];
-    }
-    return o;
-}
-// a depth counts iff it is finite and strictly inside the clamp range of depth_ray: both clamp ends are saturated values
-__device__ __forceinline__ bool depth_valid(float d) { return d > 0.0f && d < 10.0f; }
-
-// the point of depth d on the ray of pixel (u, v), in the camera's frame
-__device__ __forceinline__ void on_ray(const Cam& k, double u, double v, double d, double (&p)[3]) {
-    p[0] = d * ((u - k.cx) / k.fx);
-    p[1] = d * ((v - k.cy) / k.fy);
-    p[2] = d;
-}
-__device__ __forceinline__ void to_reference(const Pose& P, const double (&p)[3], double (&X)[3]) {
-    for (int r = 0; r < 3; ++r) X[r] = ((P.R[r][0] * p[0] + P.R[r][1] * p[1]) + P.R[r][2] * p[2]) + P.t[r];
-}
-// the inverse of a rigid pose is [R^T | -R^T t]
-__device__ __forceinline__ void to_camera(const Pose& P, const double (&X)[3], double (&Y)[3]) {
-    for (int r = 0; r < 3; ++r) {
-        const double ti = -((P.R[0][r] * P.t[0] + P.R[1][r] * P.t[1]) + P.R[2][r] * P.t[2]);
-        Y[r] = ((P.R[0][r] * X[0] + P.R[1][r] * X[1]) + P.R[2][r] * X[2]) + ti;
-    }
-}
-__device__ __forceinline__ void project(const Cam& k, const double (&Y)[3], double& x, double& y) {
-    x = (k.fx * Y[0]) / Y[2] + k.cx;
-    y = (k.fy * Y[1]) / Y[2] + k.cy;
-}
 
 // element i = (view k, pair b, pixel p) of the (K, B, h w) arrays
 struct Elem {

@@ -13,8 +13,11 @@
 // Coverage is integer arithmetic on vertices snapped to 1/256 pixel, so it is exact, does not depend on the order of a face's
 // indices, and gives a pixel centre on an edge two faces share to exactly one of them (the top-left rule of
 // include/coponerf_hip.h).  The depth is float64, one rounding per operation (-ffp-contract=off), on the vertices in a
-// canonical order; the key and its atomic minimum are cpn_splat_points'.  tests/raster_ref.py restates all of it in numpy.
+// canonical order (the camera: pinhole.h); the key, its atomic minimum and a resolved pixel's stores are zbuffer.h's, shared
+// with splat.hip.  tests/raster_ref.py restates all of it in numpy.
 #include "common.h"
+#include "pinhole.h"
+#include "zbuffer.h"
 
 #include <math.h>
 
@@ -24,7 +27,6 @@ constexpr int NT = 256;
 constexpr int SMALL = CPN_RASTER_SMALL;
 constexpr int TILES = CPN_RASTER_TILES;                    // workgroups per (camera, pair) at the most
 constexpr int MAX_SIDE = 16384;
-constexpr unsigned long long EMPTY = ~0ULL;
 static_assert(SMALL >= 1, "a face of one pixel takes the one-lane path");
 
 struct Vertex {
@@ -63,34 +65,25 @@ __device__ __forceinline__ long long doubled_area(const Vertex& a, const Vertex&
 // face's three indices, `xyz` at the pair's first vertex; nv = min(max(nvert[b], 0), capv).
 __device__ __forceinline__ bool face_setup(const int* __restrict__ tri, const float* __restrict__ xyz, int nv,
                                            const float* __restrict__ P, const float* __restrict__ Kb, double near, Face& F) {
-    double R[3][3], t[3];
-    bool ok = true;
-    for (int r = 0; r < 3; ++r) {
-        for (int c = 0; c < 3; ++c) {
-            R[r][c] = (double)P[4 * r + c];
-            ok = ok && isfinite(R[r][c]);
-        }
-        t[r] = (double)P[4 * r + 3];
-        ok = ok && isfinite(t[r]);
-    }
-    const double fx = (double)Kb[0], fy = (double)Kb[5], cx = (double)Kb[2], cy = (double)Kb[6];
-    if (!(ok && isfinite(fx) && isfinite(fy) && isfinite(cx) && isfinite(cy))) return false;
+    const Pose pose = load_pose(P);
+    const Cam cam = load_cam(Kb);
+    if (!(pose_finite(pose) && cam_finite(cam))) return false;
     constexpr double LIM = 536870912.0;                    // 2^29: differences stay below 2^30 and their products below 2^60
     for (int j = 0; j < 3; ++j) {
         const int row = tri[j];
         if (row < 0 || row >= nv) return false;            // nothing is read through an index outside the pair's vertices
         const float* const x = xyz + (size_t)row * 3;
-        double d[3];
+        double pt[3];
         for (int a = 0; a < 3; ++a) {
-            const double xa = (double)x[a];
-            if (!isfinite(xa)) return false;
-            d[a] = xa - t[a];
+            pt[a] = (double)x[a];
+            if (!isfinite(pt[a])) return false;
         }
         Vertex& v = F.v[j];
-        for (int m = 0; m < 3; ++m) v.cam[m] = (R[0][m] * d[0] + R[1][m] * d[1]) + R[2][m] * d[2];
+        to_camera_centred(pose, pt, v.cam);
         const double z = v.cam[2];
         if (!(z >= near && z > 0.0 && isfinite((float)z))) return false;        // no clipping: the face is dropped whole
-        const double u = (fx * v.cam[0]) / z + cx, w = (fy * v.cam[1]) / z + cy;
+        double u, w;
+        project(cam, v.cam, u, w);
         const double X = floor(256.0 * u + 0.5), Y = floor(256.0 * w + 0.5);
         if (!(fabs(X) < LIM && fabs(Y) < LIM)) return false;                    // a NaN fails
         v.X = (long long)X;
@@ -138,11 +131,7 @@ __device__ __forceinline__ void cover(const Edge (&e)[3], const double (&z)[3], 
     double q[3];
     const double s = weights(w, z, q);
     const float z32 = (float)((double)area / s);
-    // z32 >= 0: the bit patterns of such floats are ordered as their values; equal depths fall to the lower face
-    const unsigned long long key = ((unsigned long long)__float_as_uint(z32) << 32) | face;
-    unsigned long long* const p = Z + (size_t)r * W + c;
-    // keys only decrease: a stored key that is already smaller when it is read stays smaller, and needs no atomic
-    if (__hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) > key) atomicMin(p, key);
+    zbuf_min(Z + (size_t)r * W + c, zbuf_key(z32, face));
 }
 
 __device__ __forceinline__ int clamped_count(const int* __restrict__ n, int b, int cap) { return min(max(n[b], 0), cap); }
@@ -238,14 +227,14 @@ __global__ __launch_bounds__(NT) void raster_resolve_kernel(const unsigned long 
     if (i >= total) return;
     const int hw = H * W, kb = i / hw, p = i - kb * hw, r = p / W, c = p - r * W, b = kb % B;
     const unsigned long long key = zbuf[i];
-    const unsigned low = (unsigned)key;
     const float* const Kb = intrinsics + (size_t)b * 16;
     Face F;
-    bool hit = key != EMPTY && low < (unsigned)capf;       // a low word beyond the rows of faces reads nothing
+    bool hit = zbuf_hit(key, capf);
     if (hit)
-        hit = face_setup(faces + ((size_t)b * capf + low) * 3, xyz + (size_t)b * capv * 3, clamped_count(nvert, b, capv),
+        hit = face_setup(faces + ((size_t)b * capf + zbuf_row(key)) * 3, xyz + (size_t)b * capv * 3, clamped_count(nvert, b, capv),
                          poses + (size_t)kb * 16, Kb, 0.0, F);
-    uint8_t out[3] = {(uint8_t)(background & 255), (uint8_t)((background >> 8) & 255), (uint8_t)((background >> 16) & 255)};
+    uint8_t out[3];
+    zbuf_background(background, out);
     float wgt[3] = {__builtin_nanf(""), __builtin_nanf(""), __builtin_nanf("")};
     if (hit) {
         const long long w[3] = {edge_at(edge_of(F.v[1], F.v[2]), c, r), edge_at(edge_of(F.v[2], F.v[0]), c, r),
@@ -273,19 +262,15 @@ __global__ __launch_bounds__(NT) void raster_resolve_kernel(const unsigned long 
                 e2[a] = F.v[2].cam[a] - F.v[0].cam[a];
             }
             const double n[3] = {e1[1] * e2[2] - e1[2] * e2[1], e1[2] * e2[0] - e1[0] * e2[2], e1[0] * e2[1] - e1[1] * e2[0]};
-            const double d[3] = {((double)c - (double)Kb[2]) / (double)Kb[0], ((double)r - (double)Kb[6]) / (double)Kb[5], 1.0};
+            double d[3];                                   // the pixel's ray: the point of depth 1 on it
+            on_ray(load_cam(Kb), (double)c, (double)r, 1.0, d);
             const double nd = (n[0] * d[0] + n[1] * d[1]) + n[2] * d[2];
             const double nn = (n[0] * n[0] + n[1] * n[1]) + n[2] * n[2], dd = (d[0] * d[0] + d[1] * d[1]) + d[2] * d[2];
             const double sh = fabs(nd) / sqrt(nn * dd);
             out[0] = out[1] = out[2] = isfinite(sh) ? to_byte(255.0 * sh) : (uint8_t)0;
         }
     }
-    uint8_t* const fr = frames + (size_t)i * 3;
-    fr[0] = out[0];
-    fr[1] = out[1];
-    fr[2] = out[2];
-    if (depth) depth[i] = hit ? __uint_as_float((unsigned)(key >> 32)) : __builtin_nanf("");
-    if (index) index[i] = hit ? (int)low : -1;
+    zbuf_store(i, hit, key, out, frames, depth, index);
     if (bary) {
         float* const w3 = bary + (size_t)i * 3;
         w3[0] = wgt[0];
@@ -294,29 +279,20 @@ __global__ __launch_bounds__(NT) void raster_resolve_kernel(const unsigned long 
     }
 }
 
-int check_image(const char* who, int K, int B, int H, int W) {
-    CPN_REQUIRE(K >= 1 && K <= 255 && B >= 1 && H >= 1 && W >= 1 && H <= MAX_SIDE && W <= MAX_SIDE &&
-                    (long long)K * B * H * W < (1LL << 31),
-                CPN_E_SHAPE, "%s: need 1 <= K <= 255 cameras, B >= 1, 1 <= H, W <= 16384 and K B H W < 2^31 (got K %d, B %d, H %d, W %d)",
-                who, K, B, H, W);
-    return 0;
-}
-
 }  // namespace
 
 extern "C" int cpn_raster_faces(const float* xyz, const int* nvert, const int* faces, const int* nface, const float* poses,
                                 const float* intrinsics, int K, int B, int capv, int capf, int H, int W, int cull, double near,
                                 unsigned long long* zbuf, void* stream) {
     CPN_REQUIRE(xyz && nvert && faces && nface && poses && intrinsics && zbuf, CPN_E_ARG, "cpn_raster_faces: null pointer");
-    if (const int bad = check_image("cpn_raster_faces", K, B, H, W)) return bad;
+    if (const int bad = check_image("cpn_raster_faces", K, B, H, W, MAX_SIDE)) return bad;
     const long long all_tiles = cpn_cdiv(capf, NT), tiles = all_tiles < TILES ? all_tiles : TILES;
     CPN_REQUIRE(capv >= 1 && capf >= 1 && (long long)K * B * all_tiles < (1LL << 31), CPN_E_SHAPE,
                 "cpn_raster_faces: need capv, capf >= 1 and K B ceil(capf / 256) < 2^31 (got K %d, B %d, capv %d, capf %d)", K, B, capv,
                 capf);
     CPN_REQUIRE((cull == 0 || cull == 1) && near > 0.0, CPN_E_ARG, "cpn_raster_faces: need cull 0 or 1 and near > 0 (got %d, %g)",
                 cull, near);
-    const hipError_t e = hipMemsetAsync(zbuf, 0xFF, (size_t)K * B * H * W * sizeof(unsigned long long), (hipStream_t)stream);
-    CPN_REQUIRE(e == hipSuccess, (int)e, "cpn_raster_faces: clearing the z-buffer failed: %s", hipGetErrorString(e));
+    if (const int bad = zbuf_clear(zbuf, K, B, H, W, (hipStream_t)stream, "cpn_raster_faces")) return bad;
     hipLaunchKernelGGL(raster_faces_kernel, dim3((unsigned)(K * B * tiles)), dim3(NT), 0, (hipStream_t)stream, xyz, nvert, faces, nface,
                        poses, intrinsics, B, capv, capf, (int)tiles, H, W, cull, near, zbuf);
     CPN_LAUNCH_CHECK("cpn_raster_faces");
@@ -328,7 +304,7 @@ extern "C" int cpn_raster_resolve(const unsigned long long* zbuf, const float* x
                                   int H, int W, int shade, int background, uint8_t* frames, float* depth, int* index, float* bary,
                                   void* stream) {
     CPN_REQUIRE(zbuf && xyz && rgb && nvert && faces && poses && intrinsics && frames, CPN_E_ARG, "cpn_raster_resolve: null pointer");
-    if (const int bad = check_image("cpn_raster_resolve", K, B, H, W)) return bad;
+    if (const int bad = check_image("cpn_raster_resolve", K, B, H, W, MAX_SIDE)) return bad;
     CPN_REQUIRE(capv >= 1 && capf >= 1, CPN_E_SHAPE, "cpn_raster_resolve: need capv, capf >= 1 (got %d, %d)", capv, capf);
     CPN_REQUIRE((shade == 0 || shade == 1) && background >= 0 && background <= 0xFFFFFF, CPN_E_ARG,
                 "cpn_raster_resolve: need shade 0 or 1 and background = r | g << 8 | b << 16 (got %d, %d)", shade, background);

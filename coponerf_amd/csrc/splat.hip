@@ -10,9 +10,11 @@
 //
 // The atomic minimum is the library's first atomic on a result path.  It keeps the rule that two runs give the same bytes: the
 // minimum of a set of integers does not depend on the order in which they arrive (include/coponerf_hip.h).
-// The geometry is float64 from the fp32 inputs, one rounding per operation (-ffp-contract=off), sums left to right:
-// tests/splat_ref.py restates it in numpy.
+// The key, its minimum and a resolved pixel's stores are zbuffer.h's, shared with raster.hip.  The camera is pinhole.h's: float64
+// from the fp32 inputs, one rounding per operation (-ffp-contract=off), sums left to right: tests/splat_ref.py restates it.
 #include "common.h"
+#include "pinhole.h"
+#include "zbuffer.h"
 
 #include <math.h>
 
@@ -20,10 +22,7 @@ namespace {
 
 constexpr int NT = 256;
 constexpr int SCORE_TILE = CPN_SPLAT_SCORE_TILE;           // pixels of one image per workgroup of the score
-constexpr unsigned long long EMPTY = ~0ULL;
 static_assert(SCORE_TILE % NT == 0, "a thread of the score walks SCORE_TILE / 256 pixels");
-
-__device__ __forceinline__ bool finite3(double a, double b, double c) { return isfinite(a) && isfinite(b) && isfinite(c); }
 
 __global__ __launch_bounds__(NT) void splat_points_kernel(const float* __restrict__ xyz, const int* __restrict__ count,
                                                           const float* __restrict__ poses, const float* __restrict__ intrinsics,
@@ -33,37 +32,24 @@ __global__ __launch_bounds__(NT) void splat_points_kernel(const float* __restric
     const int i = (blockIdx.x - kb * tiles) * NT + threadIdx.x;
     const int b = kb % B;
     if (i >= min(max(count[b], 0), cap)) return;           // rows beyond the count are never read
-    const float* const P = poses + (size_t)kb * 16;
-    const float* const Kb = intrinsics + (size_t)b * 16;
+    const Pose P = load_pose(poses + (size_t)kb * 16);
+    const Cam cam = load_cam(intrinsics + (size_t)b * 16);
     const float* const x = xyz + ((size_t)b * cap + (size_t)i) * 3;
-    double R[3][3], t[3], d[3];
-    bool ok = true;
-    for (int r = 0; r < 3; ++r) {
-        for (int c = 0; c < 3; ++c) R[r][c] = (double)P[4 * r + c];
-        t[r] = (double)P[4 * r + 3];
-        d[r] = (double)x[r] - t[r];
-        ok = ok && finite3(R[r][0], R[r][1], R[r][2]) && isfinite(t[r]) && isfinite((double)x[r]);
-    }
-    const double fx = (double)Kb[0], fy = (double)Kb[5], cx = (double)Kb[2], cy = (double)Kb[6];
-    if (!(ok && finite3(fx, fy, cx) && isfinite(cy))) return;
-    double Y[3];                                           // [R^T | -R^T t] X = R^T (X - t)
-    for (int j = 0; j < 3; ++j) Y[j] = (R[0][j] * d[0] + R[1][j] * d[1]) + R[2][j] * d[2];
+    const double X[3] = {(double)x[0], (double)x[1], (double)x[2]};
+    if (!(pose_finite(P) && finite3(X[0], X[1], X[2]) && cam_finite(cam))) return;
+    double Y[3], u, v;
+    to_camera_centred(P, X, Y);
     if (!(Y[2] >= near)) return;                           // behind the camera, nearer than near, or NaN
-    const double u = (fx * Y[0]) / Y[2] + cx, v = (fy * Y[1]) / Y[2] + cy;
+    project(cam, Y, u, v);
     const float z32 = (float)Y[2];
     constexpr double LIM = 1073741824.0;                   // 2^30: the pixel and its footprint fit an int
     if (!(fabs(u) < LIM && fabs(v) < LIM && isfinite(z32))) return;
     const int c = (int)floor(u + 0.5), r = (int)floor(v + 0.5);
     const int c0 = max(c - radius, 0), c1 = min(c + radius, W - 1), r0 = max(r - radius, 0), r1 = min(r + radius, H - 1);
-    // z32 >= 0: the bit patterns of such floats are ordered as their values; equal depths fall to the lower index
-    const unsigned long long key = ((unsigned long long)__float_as_uint(z32) << 32) | (unsigned)i;
+    const unsigned long long key = zbuf_key(z32, (unsigned)i);
     unsigned long long* const Z = zbuf + (size_t)kb * H * W;
     for (int rr = r0; rr <= r1; ++rr) {                    // an empty range where the footprint misses the image
-        for (int cc = c0; cc <= c1; ++cc) {
-            unsigned long long* const p = Z + (size_t)rr * W + cc;
-            // keys only decrease: a stored key that is already smaller when it is read stays smaller, and needs no atomic
-            if (__hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) > key) atomicMin(p, key);
-        }
+        for (int cc = c0; cc <= c1; ++cc) zbuf_min(Z + (size_t)rr * W + cc, key);
     }
 }
 
@@ -75,26 +61,19 @@ __global__ __launch_bounds__(NT) void splat_resolve_kernel(const unsigned long l
     if (i >= total) return;
     const int hw = H * W, kb = i / hw, p = i - kb * hw, r = p / W, c = p - r * W;
     unsigned long long key = zbuf[i];
-    if (key == EMPTY && fill > 0) {                        // the smallest key around it, of the buffer as it was splatted
+    if (key == ZBUF_EMPTY && fill > 0) {                   // the smallest key around it, of the buffer as it was splatted
         const unsigned long long* const Z = zbuf + (size_t)kb * hw;
         for (int rr = max(r - fill, 0); rr <= min(r + fill, H - 1); ++rr)
             for (int cc = max(c - fill, 0); cc <= min(c + fill, W - 1); ++cc) key = min(key, Z[(size_t)rr * W + cc]);
     }
-    const unsigned low = (unsigned)key;
-    const bool hit = key != EMPTY && low < (unsigned)cap;  // a low word cpn_splat_points never writes reads no colour
-    uint8_t* const f = frames + (size_t)i * 3;
+    const bool hit = zbuf_hit(key, cap);
+    uint8_t out[3];
+    zbuf_background(background, out);
     if (hit) {
-        const uint8_t* const col = rgb + ((size_t)(kb % B) * cap + low) * 3;
-        f[0] = col[0];
-        f[1] = col[1];
-        f[2] = col[2];
-    } else {
-        f[0] = (uint8_t)(background & 255);
-        f[1] = (uint8_t)((background >> 8) & 255);
-        f[2] = (uint8_t)((background >> 16) & 255);
+        const uint8_t* const col = rgb + ((size_t)(kb % B) * cap + zbuf_row(key)) * 3;
+        for (int ch = 0; ch < 3; ++ch) out[ch] = col[ch];
     }
-    if (depth) depth[i] = hit ? __uint_as_float((unsigned)(key >> 32)) : __builtin_nanf("");
-    if (index) index[i] = hit ? (int)low : -1;
+    zbuf_store(i, hit, key, out, frames, depth, index);
 }
 
 // partial (K B, tiles, 2): the covered pixels of the workgroup's SCORE_TILE pixels and their squared differences
@@ -135,16 +114,6 @@ __global__ __launch_bounds__(NT) void splat_score_finish_kernel(const long long*
     }
 }
 
-bool image_ok(int K, int B, int H, int W) {
-    return K >= 1 && K <= 255 && B >= 1 && H >= 1 && W >= 1 && (long long)K * B * H * W < (1LL << 31);
-}
-
-int check_image(const char* who, int K, int B, int H, int W) {
-    CPN_REQUIRE(image_ok(K, B, H, W), CPN_E_SHAPE,
-                "%s: need 1 <= K <= 255 cameras, B, H, W >= 1 and K B H W < 2^31 (got K %d, B %d, H %d, W %d)", who, K, B, H, W);
-    return 0;
-}
-
 long long score_tiles(int H, int W) { return cpn_cdiv((long long)H * W, SCORE_TILE); }
 
 }  // namespace
@@ -158,8 +127,7 @@ extern "C" int cpn_splat_points(const float* xyz, const int* count, const float*
                 "cpn_splat_points: need 1 <= cap < 2^31 and K B ceil(cap / 256) < 2^31 (got K %d, B %d, cap %d)", K, B, cap);
     CPN_REQUIRE(radius >= 0 && radius <= 8 && near > 0.0, CPN_E_ARG,
                 "cpn_splat_points: need 0 <= radius <= 8 and near > 0 (got %d, %g)", radius, near);
-    const hipError_t e = hipMemsetAsync(zbuf, 0xFF, (size_t)K * B * H * W * sizeof(unsigned long long), (hipStream_t)stream);
-    CPN_REQUIRE(e == hipSuccess, (int)e, "cpn_splat_points: clearing the z-buffer failed: %s", hipGetErrorString(e));
+    if (const int bad = zbuf_clear(zbuf, K, B, H, W, (hipStream_t)stream, "cpn_splat_points")) return bad;
     hipLaunchKernelGGL(splat_points_kernel, dim3((unsigned)(K * B * tiles)), dim3(NT), 0, (hipStream_t)stream, xyz, count, poses,
                        intrinsics, B, cap, (int)tiles, H, W, radius, near, zbuf);
     CPN_LAUNCH_CHECK("cpn_splat_points");

@@ -26,17 +26,8 @@ import numpy as np
 import torch
 
 from . import _hip
+from ._args import device_tensors, one_device
 from .shards import crop_window
-
-
-def _device_f32(who: str, named, dev=None) -> None:
-    """The checks every entry shares: contiguous fp32 tensors on one HIP device."""
-    for what, x in named:
-        if not torch.is_tensor(x) or not x.is_cuda:
-            raise RuntimeError(f"{who} runs on the HIP device only (coponerf_amd has no non-HIP compute path): {what}")
-        dev = x.device if dev is None else dev
-        if x.dtype != torch.float32 or not x.is_contiguous() or x.device != dev:
-            raise ValueError(f"{who}: {what} must be a contiguous fp32 tensor on one device")
 
 
 def _cameras(who: str, intrinsics: torch.Tensor, rel_pose: torch.Tensor, B: int) -> None:
@@ -55,7 +46,8 @@ def match_fields(flow: Sequence[torch.Tensor], intrinsics: torch.Tensor, rel_pos
     if len(flow) < 2:
         raise ValueError("match_fields: flow must hold the two directions")
     f0, f1 = flow[0], flow[1]
-    _device_f32("match_fields", (("flow[0]", f0), ("flow[1]", f1), ("intrinsics", intrinsics), ("rel_pose", rel_pose)))
+    device_tensors("match_fields", (("flow[0]", f0, torch.float32, None), ("flow[1]", f1, torch.float32, None),
+                                    ("intrinsics", intrinsics, torch.float32, None), ("rel_pose", rel_pose, torch.float32, None)))
     if f0.dim() != 4 or f0.shape[1] != 2 or f0.shape[2] != f0.shape[3] or f1.shape != f0.shape:
         raise ValueError(f"match_fields: flows must both be (B, 2, h, h), got {tuple(f0.shape)} and {tuple(f1.shape)}")
     B, h, S = int(f0.shape[0]), int(f0.shape[2]), int(S)
@@ -120,8 +112,7 @@ def _stride_mask(S: int, stride: int, dev) -> torch.Tensor:
 def compact(keep: torch.Tensor, q: torch.Tensor, cycle: torch.Tensor, epi: torch.Tensor) -> Matches:
     """cpn_compact_matches: keep (2, B, S, S) uint8 (non-zero = kept) and match_fields' q, cycle and epi -> the Matches of every
     pair in (direction, row, column) order, cap = 2 S S rows per pair."""
-    if not all(torch.is_tensor(x) and x.is_cuda and x.is_contiguous() and x.device == keep.device for x in (keep, q, cycle, epi)):
-        raise RuntimeError("compact: contiguous tensors on one HIP device (coponerf_amd has no non-HIP compute path)")
+    one_device("compact", keep, q, cycle, epi)
     if keep.dtype != torch.uint8 or keep.dim() != 4 or keep.shape[0] != 2 or keep.shape[2] != keep.shape[3]:
         raise ValueError(f"compact: keep must be (2, B, S, S) uint8, got {tuple(keep.shape)} {keep.dtype}")
     B, S = int(keep.shape[1]), int(keep.shape[2])
@@ -171,7 +162,8 @@ def refine_pose(matches: Matches, intrinsics: torch.Tensor, rel_pose: torch.Tens
     translation direction moved by, the updates made, and the status (0 ok, 1 a failed solve: the state before it is
     returned, 2 nothing to do: no matches, a zero or non-finite pose, or iters == 0 - pose is rel_pose, the rest 0)."""
     xy, count = matches.xy, matches.count
-    _device_f32("refine_pose", (("matches.xy", xy), ("intrinsics", intrinsics), ("rel_pose", rel_pose)))
+    device_tensors("refine_pose", (("matches.xy", xy, torch.float32, None), ("intrinsics", intrinsics, torch.float32, None),
+                                   ("rel_pose", rel_pose, torch.float32, None)))
     if xy.dim() != 3 or xy.shape[2] != 4 or xy.shape[1] < 1:
         raise ValueError(f"refine_pose: matches.xy must be (B, N, 4) with N >= 1, got {tuple(xy.shape)}")
     B, N = int(xy.shape[0]), int(xy.shape[1])

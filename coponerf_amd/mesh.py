@@ -27,8 +27,9 @@ import numpy as np
 import torch
 
 from . import _hip
+from ._args import device_tensors
 from .novel_views import render_path
-from .point_cloud import PointCloud, _views, unproject
+from .point_cloud import PointCloud, _views, ply_vertices, unproject
 
 MAX_VERTICES = 2 ** 22                                        # the default capacity of extract never exceeds it
 
@@ -73,12 +74,8 @@ def integrate(views: Dict[str, torch.Tensor], intrinsics: torch.Tensor, S: int, 
     volume.  One launch; nothing is read on the host."""
     depth, valid, rgb, poses = views["depth"], views["valid"], views["rgb"], views["poses"]
     K, B, y0, x0, h, w, Kb = _views("integrate", depth, poses, intrinsics, S, window)
-    for what, x, dtype, shape in (("valid", valid, torch.uint8, (K, B, h * w)), ("rgb", rgb, torch.float32, (K, B, h * w, 3))):
-        if not torch.is_tensor(x) or not x.is_cuda:
-            raise RuntimeError(f"integrate runs on the HIP device only (coponerf_amd has no non-HIP compute path): {what}")
-        if x.dtype != dtype or tuple(x.shape) != shape or not x.is_contiguous() or x.device != depth.device:
-            raise ValueError(f"integrate: {what} must be a contiguous {shape} {dtype} tensor on depth's device, got "
-                             f"{tuple(x.shape)} {x.dtype}")
+    device_tensors("integrate", (("valid", valid, torch.uint8, (K, B, h * w)), ("rgb", rgb, torch.float32, (K, B, h * w, 3))),
+                   depth.device, "depth's device")
     Nx, Ny, Nz = _dims("integrate", dims, B)
     if not float(trunc_voxels) > 0.0:
         raise ValueError(f"integrate: trunc_voxels must be > 0, got {trunc_voxels}")
@@ -127,11 +124,7 @@ class Volume:
         want = (("tsdf", self.tsdf, torch.float32, (B, Nz, Ny, Nx)), ("weight", self.weight, torch.uint8, (B, Nz, Ny, Nx)),
                 ("colour", self.colour, torch.float32, (B, Nz, Ny, Nx, 3)), ("origin", self.origin, torch.float32, (B, 3)),
                 ("spacing", self.spacing, torch.float32, (B, 3)))
-        for what, x, dtype, shape in want:
-            if not torch.is_tensor(x) or not x.is_cuda:
-                raise RuntimeError(f"extract runs on the HIP device only (coponerf_amd has no non-HIP compute path): {what}")
-            if x.dtype != dtype or tuple(x.shape) != shape or not x.is_contiguous() or x.device != dev:
-                raise ValueError(f"extract: {what} must be a contiguous {shape} {dtype} tensor on the volume's device")
+        device_tensors("extract", want, dev, "the volume's device")
         lib = _hip.lib()
         n_vert, n_face = lib.cpn_surface_vertices_scratch(B, Nx, Ny, Nz), lib.cpn_surface_faces_scratch(B, Nx, Ny, Nz)
         if n_vert <= 0 or n_face <= 0:
@@ -208,21 +201,14 @@ class Mesh:
 def ply_bytes(xyz: np.ndarray, rgb: np.ndarray, faces: np.ndarray) -> bytes:
     """A binary little-endian PLY of n vertices (xyz (n, 3) float32, rgb (n, 3) uint8: point_cloud.ply_bytes' vertex element) and m
     triangles (faces (m, 3) int32); the header is built here, on the host."""
-    xyz, rgb, faces = np.asarray(xyz), np.asarray(rgb), np.asarray(faces)
-    n, m = int(xyz.shape[0]), int(faces.shape[0])
-    if xyz.shape != (n, 3) or rgb.shape != (n, 3) or xyz.dtype != np.float32 or rgb.dtype != np.uint8 or faces.shape != (m, 3) or \
-            faces.dtype != np.int32:
-        raise ValueError(f"ply_bytes: xyz (n, 3) float32, rgb (n, 3) uint8 and faces (m, 3) int32, got {xyz.shape} {xyz.dtype}, "
-                         f"{rgb.shape} {rgb.dtype} and {faces.shape} {faces.dtype}")
-    header = ("ply\nformat binary_little_endian 1.0\n" f"element vertex {n}\n"
-              "property float x\nproperty float y\nproperty float z\n"
-              "property uchar red\nproperty uchar green\nproperty uchar blue\n"
-              f"element face {m}\nproperty list uchar int vertex_indices\nend_header\n")
-    rows = np.empty(n, dtype=np.dtype([("xyz", "<f4", 3), ("rgb", "u1", 3)]))
-    rows["xyz"], rows["rgb"] = xyz, rgb
+    faces = np.asarray(faces)
+    m = int(faces.shape[0])
+    if faces.shape != (m, 3) or faces.dtype != np.int32:
+        raise ValueError(f"ply_bytes: faces (m, 3) int32, got {faces.shape} {faces.dtype}")
+    header, rows = ply_vertices(xyz, rgb)
     tris = np.empty(m, dtype=np.dtype([("n", "u1"), ("v", "<i4", 3)]))
     tris["n"], tris["v"] = 3, faces
-    return header.encode("ascii") + rows.tobytes() + tris.tobytes()
+    return (header + f"element face {m}\nproperty list uchar int vertex_indices\nend_header\n").encode("ascii") + rows + tris.tobytes()
 
 
 @torch.no_grad()

@@ -23,24 +23,19 @@ import numpy as np
 import torch
 
 from . import _hip
+from ._args import device_tensors, one_device, pair_intrinsics
 from .novel_views import render_path
 
 
 def _views(who: str, depth: torch.Tensor, poses: torch.Tensor, intrinsics: torch.Tensor, S: int,
            window: Optional[Sequence[int]]) -> Tuple[int, int, int, int, int, int, torch.Tensor]:
     """The checks unproject and vote share -> (K, B, y0, x0, h, w, the (B, 4, 4) intrinsics)."""
-    for what, x in (("depth", depth), ("poses", poses), ("intrinsics", intrinsics)):
-        if not torch.is_tensor(x) or not x.is_cuda:
-            raise RuntimeError(f"{who} runs on the HIP device only (coponerf_amd has no non-HIP compute path): {what}")
-        if x.dtype != torch.float32 or not x.is_contiguous() or x.device != depth.device:
-            raise ValueError(f"{who}: {what} must be a contiguous fp32 tensor on depth's device")
+    device_tensors(who, (("depth", depth, torch.float32, None), ("poses", poses, torch.float32, None),
+                         ("intrinsics", intrinsics, torch.float32, None)), owner="depth's device")
     if depth.dim() != 3 or poses.dim() != 4 or poses.shape[:2] != depth.shape[:2] or poses.shape[2:] != (4, 4):
         raise ValueError(f"{who}: depth (K, B, h * w) and poses (K, B, 4, 4), got {tuple(depth.shape)} and {tuple(poses.shape)}")
     K, B = int(depth.shape[0]), int(depth.shape[1])
-    if intrinsics.dim() == 4 and intrinsics.shape[1] == 1:                   # query.intrinsics: (B, 1, 4, 4)
-        intrinsics = intrinsics[:, 0]
-    if tuple(intrinsics.shape) != (B, 4, 4):
-        raise ValueError(f"{who}: intrinsics must be (B, 4, 4) or (B, 1, 4, 4) with B = {B}, got {tuple(intrinsics.shape)}")
+    Kb = pair_intrinsics(who, intrinsics, B)
     S = int(S)
     y0, x0, h, w = (0, 0, S, S) if window is None else (int(v) for v in window)
     if not (0 <= y0 and 0 <= x0 and h >= 1 and w >= 1 and y0 + h <= S and x0 + w <= S):
@@ -49,7 +44,7 @@ def _views(who: str, depth: torch.Tensor, poses: torch.Tensor, intrinsics: torch
         raise ValueError(f"{who}: depth of shape {tuple(depth.shape)} does not fill a window of {h} x {w}")
     if not 1 <= K <= 255 or B < 1 or K * B * h * w >= 2 ** 31:
         raise ValueError(f"{who}: need 1 <= K <= 255 views, B >= 1 and K B h w < 2^31, got K = {K}, B = {B}, h w = {h * w}")
-    return K, B, y0, x0, h, w, intrinsics.contiguous()
+    return K, B, y0, x0, h, w, Kb
 
 
 @torch.no_grad()
@@ -89,8 +84,7 @@ def vote(depth: torch.Tensor, poses: torch.Tensor, intrinsics: torch.Tensor, S: 
 def compact(keep: torch.Tensor, xyz: torch.Tensor, rgb: torch.Tensor, h: int, w: int) -> "PointCloud":
     """cpn_compact_points: keep (K, B, h * w) uint8 (non-zero = selected), xyz and rgb (K, B, h * w, 3) fp32 -> the PointCloud of
     the selected points of every pair in (view, row, column) order; its rows beyond the count are not written."""
-    if not all(torch.is_tensor(x) and x.is_cuda and x.is_contiguous() and x.device == keep.device for x in (keep, xyz, rgb)):
-        raise RuntimeError("compact: contiguous tensors on one HIP device (coponerf_amd has no non-HIP compute path)")
+    one_device("compact", keep, xyz, rgb)
     if keep.dtype != torch.uint8 or keep.dim() != 3 or int(keep.shape[2]) != h * w:
         raise ValueError(f"compact: keep must be (K, B, {h} * {w}) uint8, got {tuple(keep.shape)} {keep.dtype}")
     K, B = int(keep.shape[0]), int(keep.shape[1])
@@ -146,16 +140,22 @@ class PointCloud:
 
 def ply_bytes(xyz: np.ndarray, rgb: np.ndarray) -> bytes:
     """A binary little-endian PLY of n vertices: xyz (n, 3) float32, rgb (n, 3) uint8; the header is built here, on the host."""
+    header, rows = ply_vertices(xyz, rgb)
+    return (header + "end_header\n").encode("ascii") + rows
+
+
+def ply_vertices(xyz: np.ndarray, rgb: np.ndarray) -> Tuple[str, bytes]:
+    """The vertex element of this module's PLY and mesh's: the header up to its last property, and the n rows."""
     xyz, rgb = np.asarray(xyz), np.asarray(rgb)
     n = int(xyz.shape[0])
     if xyz.shape != (n, 3) or rgb.shape != (n, 3) or xyz.dtype != np.float32 or rgb.dtype != np.uint8:
         raise ValueError(f"ply_bytes: xyz (n, 3) float32 and rgb (n, 3) uint8, got {xyz.shape} {xyz.dtype} and {rgb.shape} {rgb.dtype}")
     header = ("ply\nformat binary_little_endian 1.0\n" f"element vertex {n}\n"
               "property float x\nproperty float y\nproperty float z\n"
-              "property uchar red\nproperty uchar green\nproperty uchar blue\nend_header\n")
+              "property uchar red\nproperty uchar green\nproperty uchar blue\n")
     rows = np.empty(n, dtype=np.dtype([("xyz", "<f4", 3), ("rgb", "u1", 3)]))
     rows["xyz"], rows["rgb"] = xyz, rgb
-    return header.encode("ascii") + rows.tobytes()
+    return header, rows.tobytes()
 
 
 @torch.no_grad()

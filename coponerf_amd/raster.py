@@ -22,8 +22,9 @@ from typing import Dict, Sequence, Tuple
 import torch
 
 from . import _hip
-from .novel_views import pack_frames, render_path
-from .splat import _cameras, score
+from ._args import background_word, device_tensors, frame_outputs, view_cameras, zbuffer_dims
+from .novel_views import render_path
+from .splat import score_photo
 
 SHADES = {"colour": 0, "headlight": 1}
 MAX_SIDE = 16384
@@ -31,13 +32,9 @@ MAX_SIDE = 16384
 
 def _mesh(who: str, mesh) -> Tuple[int, int, int]:
     xyz = mesh.xyz
-    want = (("xyz", mesh.xyz, torch.float32), ("rgb", mesh.rgb, torch.uint8), ("nvert", mesh.nvert, torch.int32),
-            ("faces", mesh.faces, torch.int32), ("nface", mesh.nface, torch.int32))
-    for what, x, dtype in want:
-        if not torch.is_tensor(x) or not x.is_cuda:
-            raise RuntimeError(f"{who} runs on the HIP device only (coponerf_amd has no non-HIP compute path): mesh.{what}")
-        if x.dtype != dtype or not x.is_contiguous() or x.device != xyz.device:
-            raise ValueError(f"{who}: mesh.{what} must be a contiguous {dtype} tensor on the mesh's device")
+    device_tensors(who, (("mesh.xyz", mesh.xyz, torch.float32, None), ("mesh.rgb", mesh.rgb, torch.uint8, None),
+                         ("mesh.nvert", mesh.nvert, torch.int32, None), ("mesh.faces", mesh.faces, torch.int32, None),
+                         ("mesh.nface", mesh.nface, torch.int32, None)), owner="the mesh's device")
     B = int(xyz.shape[0]) if xyz.dim() == 3 else -1
     if xyz.dim() != 3 or xyz.shape[2] != 3 or mesh.rgb.shape != xyz.shape or mesh.faces.dim() != 3 or \
             tuple(mesh.faces.shape[::2]) != (B, 3) or tuple(mesh.nvert.shape) != (B,) or tuple(mesh.nface.shape) != (B,):
@@ -50,13 +47,6 @@ def _mesh(who: str, mesh) -> Tuple[int, int, int]:
     return B, capv, capf
 
 
-def _views(who: str, poses: torch.Tensor, intrinsics: torch.Tensor, B: int, capf: int, H: int, W: int,
-           dev: torch.device) -> Tuple[int, torch.Tensor]:
-    if H > MAX_SIDE or W > MAX_SIDE:
-        raise ValueError(f"{who}: need H, W <= {MAX_SIDE}, got H = {H}, W = {W}")
-    return _cameras(who, poses, intrinsics, B, capf, H, W, dev)
-
-
 @torch.no_grad()
 def raster_faces(mesh, poses: torch.Tensor, intrinsics: torch.Tensor, H: int, W: int, cull: bool = False,
                  near: float = 1e-3) -> torch.Tensor:
@@ -67,7 +57,7 @@ def raster_faces(mesh, poses: torch.Tensor, intrinsics: torch.Tensor, H: int, W:
     clipping: a face with a vertex nearer than `near` is not drawn at all."""
     H, W = int(H), int(W)
     B, capv, capf = _mesh("raster_faces", mesh)
-    K, Kb = _views("raster_faces", poses, intrinsics, B, capf, H, W, mesh.xyz.device)
+    K, Kb = view_cameras("raster_faces", poses, intrinsics, B, capf, H, W, mesh.xyz.device, "the mesh's device", MAX_SIDE)
     if not float(near) > 0.0:
         raise ValueError(f"raster_faces: need near > 0, got {near}")
     zbuf = torch.empty(K, B, H, W, dtype=torch.int64, device=mesh.xyz.device)
@@ -90,33 +80,19 @@ def resolve(zbuf: torch.Tensor, mesh, poses: torch.Tensor, intrinsics: torch.Ten
     colours say nothing.  background: the empty pixels' bytes.  There is no fill pass: a triangle surface has no holes
     between samples."""
     B, capv, capf = _mesh("resolve", mesh)
-    if not torch.is_tensor(zbuf) or not zbuf.is_cuda:
-        raise RuntimeError("resolve runs on the HIP device only (coponerf_amd has no non-HIP compute path): zbuf")
-    if zbuf.dtype != torch.int64 or zbuf.dim() != 4 or not zbuf.is_contiguous() or zbuf.device != mesh.xyz.device or \
-            int(zbuf.shape[1]) != B:
-        raise ValueError(f"resolve: zbuf must be a contiguous (K, B, H, W) int64 tensor on the mesh's device with B = {B}, got "
-                         f"{tuple(zbuf.shape)} {zbuf.dtype}")
-    H, W = int(zbuf.shape[2]), int(zbuf.shape[3])
-    K, Kb = _views("resolve", poses, intrinsics, B, capf, H, W, mesh.xyz.device)
-    if K != int(zbuf.shape[0]):
-        raise ValueError(f"resolve: zbuf holds {int(zbuf.shape[0])} cameras, poses {K}")
-    bg = [int(v) for v in background]
-    if shade not in SHADES or len(bg) != 3 or not all(0 <= v <= 255 for v in bg):
-        raise ValueError(f"resolve: need shade in {tuple(SHADES)} and three background bytes, got {shade!r} and {tuple(background)}")
-    dev = zbuf.device
-    out = {"frames": torch.empty(K, B, H, W, 3, dtype=torch.uint8, device=dev)}
-    if return_depth:
-        out["depth"] = torch.empty(K, B, H, W, dtype=torch.float32, device=dev)
-    if return_index:
-        out["index"] = torch.empty(K, B, H, W, dtype=torch.int32, device=dev)
-    if return_bary:
-        out["bary"] = torch.empty(K, B, H, W, 3, dtype=torch.float32, device=dev)
+    dev = device_tensors("resolve", (("zbuf", zbuf, torch.int64, None),), mesh.xyz.device, "the mesh's device")
+    nk, _, H, W = zbuffer_dims("resolve", zbuf, B)
+    K, Kb = view_cameras("resolve", poses, intrinsics, B, capf, H, W, dev, "the mesh's device", MAX_SIDE)
+    if K != nk:
+        raise ValueError(f"resolve: zbuf holds {nk} cameras, poses {K}")
+    if shade not in SHADES:
+        raise ValueError(f"resolve: need shade in {tuple(SHADES)}, got {shade!r}")
+    word = background_word("resolve", background)
+    out, (frames, depth, index, bary) = frame_outputs(K, B, H, W, dev, return_depth, return_index, return_bary)
     with torch.cuda.device(dev):
         _hip.call("cpn_raster_resolve", zbuf.data_ptr(), mesh.xyz.data_ptr(), mesh.rgb.data_ptr(), mesh.nvert.data_ptr(),
-                  mesh.faces.data_ptr(), poses.data_ptr(), Kb.data_ptr(), K, B, capv, capf, H, W, SHADES[shade],
-                  bg[0] | bg[1] << 8 | bg[2] << 16, out["frames"].data_ptr(), out["depth"].data_ptr() if return_depth else None,
-                  out["index"].data_ptr() if return_index else None, out["bary"].data_ptr() if return_bary else None,
-                  _hip.stream_handle())
+                  mesh.faces.data_ptr(), poses.data_ptr(), Kb.data_ptr(), K, B, capv, capf, H, W, SHADES[shade], word, frames, depth,
+                  index, bary, _hip.stream_handle())
     return out
 
 
@@ -156,15 +132,12 @@ def photo_check(model, model_input: Dict, t=(0.0, 0.25, 0.5, 0.75, 1.0), cull: b
     if reconstruct_kwargs:
         raise TypeError(f"photo_check: unknown arguments {sorted(reconstruct_kwargs)}")
     ctx = model_input["context"]
-    B, S = int(ctx["rgb"].shape[0]), int(ctx["rgb"].shape[2])
+    S = int(ctx["rgb"].shape[2])
     res = render_path(model, model_input, t, window=fuse.get("window"), return_rgb=True, return_depth=True)
     surface = integrate(res, model_input["query"]["intrinsics"], S, **fuse).extract(**take)
-    coverage, psnr = [], []
+    scores = []
     for view, k in ((0, 0), (1, len(t) - 1)):
         out = draw(surface, res["poses"][k:k + 1].contiguous(), ctx["intrinsics"][:, view].contiguous(), S, S, cull=cull,
                    return_index=True)
-        photo = pack_frames(ctx["rgb"][:, view].contiguous(), torch.empty(B, S, S, 3, dtype=torch.uint8, device=ctx["rgb"].device))
-        c, p = score(out["frames"], out["index"], photo.unsqueeze(0))
-        coverage.append(c[0])
-        psnr.append(p[0])
-    return torch.stack(coverage), torch.stack(psnr)
+        scores.append(score_photo(out, ctx["rgb"][:, view]))
+    return torch.stack([c for c, _ in scores]), torch.stack([p for _, p in scores])

@@ -23,41 +23,18 @@ import numpy as np
 import torch
 
 from . import _hip
+from ._args import background_word, device_tensors, frame_outputs, one_device, view_cameras, zbuffer_dims
 from .novel_views import pack_frames, render_path
 
 
 def _cloud(who: str, cloud) -> Tuple[int, int]:
     xyz, rgb, count = cloud.xyz, cloud.rgb, cloud.count
-    for what, x, dtype in (("xyz", xyz, torch.float32), ("rgb", rgb, torch.uint8), ("count", count, torch.int32)):
-        if not torch.is_tensor(x) or not x.is_cuda:
-            raise RuntimeError(f"{who} runs on the HIP device only (coponerf_amd has no non-HIP compute path): cloud.{what}")
-        if x.dtype != dtype or not x.is_contiguous() or x.device != xyz.device:
-            raise ValueError(f"{who}: cloud.{what} must be a contiguous {dtype} tensor on the cloud's device")
+    device_tensors(who, (("cloud.xyz", xyz, torch.float32, None), ("cloud.rgb", rgb, torch.uint8, None),
+                         ("cloud.count", count, torch.int32, None)), owner="the cloud's device")
     if xyz.dim() != 3 or xyz.shape[2] != 3 or rgb.shape != xyz.shape or tuple(count.shape) != (int(xyz.shape[0]),):
         raise ValueError(f"{who}: a PointCloud of xyz (B, cap, 3), rgb (B, cap, 3) and count (B), got {tuple(xyz.shape)}, "
                          f"{tuple(rgb.shape)} and {tuple(count.shape)}")
     return int(xyz.shape[0]), int(xyz.shape[1])
-
-
-def _cameras(who: str, poses: torch.Tensor, intrinsics: torch.Tensor, B: int, cap: int, H: int, W: int,
-             dev: torch.device) -> Tuple[int, torch.Tensor]:
-    """The checks of the cameras, as point_cloud._views makes them -> (K, the (B, 4, 4) intrinsics)."""
-    for what, x in (("poses", poses), ("intrinsics", intrinsics)):
-        if not torch.is_tensor(x) or not x.is_cuda:
-            raise RuntimeError(f"{who} runs on the HIP device only (coponerf_amd has no non-HIP compute path): {what}")
-        if x.dtype != torch.float32 or not x.is_contiguous() or x.device != dev:
-            raise ValueError(f"{who}: {what} must be a contiguous fp32 tensor on the cloud's device")
-    if poses.dim() != 4 or int(poses.shape[1]) != B or poses.shape[2:] != (4, 4):
-        raise ValueError(f"{who}: poses must be (K, B, 4, 4) with B = {B}, got {tuple(poses.shape)}")
-    if intrinsics.dim() == 4 and intrinsics.shape[1] == 1:                   # query.intrinsics: (B, 1, 4, 4)
-        intrinsics = intrinsics[:, 0]
-    if tuple(intrinsics.shape) != (B, 4, 4):
-        raise ValueError(f"{who}: intrinsics must be (B, 4, 4) or (B, 1, 4, 4) with B = {B}, got {tuple(intrinsics.shape)}")
-    K = int(poses.shape[0])
-    if not 1 <= K <= 255 or H < 1 or W < 1 or K * B * H * W >= 2 ** 31 or cap < 1 or K * B * -(-cap // 256) >= 2 ** 31:
-        raise ValueError(f"{who}: need 1 <= K <= 255 cameras, H, W, cap >= 1, K B H W < 2^31 and K B ceil(cap / 256) < 2^31, got "
-                         f"K = {K}, B = {B}, H = {H}, W = {W}, cap = {cap}")
-    return K, intrinsics.contiguous()
 
 
 @torch.no_grad()
@@ -68,7 +45,7 @@ def splat_points(cloud, poses: torch.Tensor, intrinsics: torch.Tensor, H: int, W
     holding uint64 keys: (bits of the fp32 depth) << 32 | point index, -1 (all ones) where no point fell."""
     H, W, radius = int(H), int(W), int(radius)
     B, cap = _cloud("splat_points", cloud)
-    K, Kb = _cameras("splat_points", poses, intrinsics, B, cap, H, W, cloud.xyz.device)
+    K, Kb = view_cameras("splat_points", poses, intrinsics, B, cap, H, W, cloud.xyz.device, "the cloud's device")
     if not 0 <= radius <= 8 or not float(near) > 0.0:
         raise ValueError(f"splat_points: need 0 <= radius <= 8 and near > 0, got {radius} and {near}")
     zbuf = torch.empty(K, B, H, W, dtype=torch.int64, device=cloud.xyz.device)
@@ -84,29 +61,19 @@ def resolve(zbuf: torch.Tensor, rgb: torch.Tensor, fill: int = 0, background: Se
     """cpn_splat_resolve: splat_points' z-buffer (K, B, H, W) and the cloud's rgb (B, cap, 3) uint8 -> `frames` (K, B, H, W, 3)
     uint8, on request `depth` (K, B, H, W) fp32 (NaN where empty) and `index` (K, B, H, W) int32 (-1 where empty).  fill > 0:
     an empty pixel takes the nearest point of the (2 fill + 1)^2 splatted pixels around it; background: the empty pixels' bytes."""
-    if not all(torch.is_tensor(x) and x.is_cuda and x.is_contiguous() and x.device == zbuf.device for x in (zbuf, rgb)):
-        raise RuntimeError("resolve: contiguous tensors on one HIP device (coponerf_amd has no non-HIP compute path)")
-    if zbuf.dtype != torch.int64 or zbuf.dim() != 4 or rgb.dtype != torch.uint8 or rgb.dim() != 3 or rgb.shape[2] != 3 or \
-            rgb.shape[0] != zbuf.shape[1]:
-        raise ValueError(f"resolve: zbuf (K, B, H, W) int64 and rgb (B, cap, 3) uint8, got {tuple(zbuf.shape)} {zbuf.dtype} and "
-                         f"{tuple(rgb.shape)} {rgb.dtype}")
-    K, B, H, W = (int(v) for v in zbuf.shape)
-    cap, fill = int(rgb.shape[1]), int(fill)
-    bg = [int(v) for v in background]
-    if not 0 <= fill <= 4 or len(bg) != 3 or not all(0 <= v <= 255 for v in bg):
-        raise ValueError(f"resolve: need 0 <= fill <= 4 and three background bytes, got {fill} and {tuple(background)}")
+    one_device("resolve", zbuf, rgb)
+    if rgb.dtype != torch.uint8 or rgb.dim() != 3 or rgb.shape[2] != 3:
+        raise ValueError(f"resolve: rgb must be (B, cap, 3) uint8, got {tuple(rgb.shape)} {rgb.dtype}")
+    K, B, H, W = zbuffer_dims("resolve", zbuf, int(rgb.shape[0]))
+    cap, fill, word = int(rgb.shape[1]), int(fill), background_word("resolve", background)
+    if not 0 <= fill <= 4:
+        raise ValueError(f"resolve: need 0 <= fill <= 4, got {fill}")
     if not 1 <= K <= 255 or min(B, H, W, cap) < 1 or K * B * H * W >= 2 ** 31:
         raise ValueError(f"resolve: need 1 <= K <= 255, B, H, W, cap >= 1 and K B H W < 2^31, got {tuple(zbuf.shape)}, cap = {cap}")
-    dev = zbuf.device
-    out = {"frames": torch.empty(K, B, H, W, 3, dtype=torch.uint8, device=dev)}
-    if return_depth:
-        out["depth"] = torch.empty(K, B, H, W, dtype=torch.float32, device=dev)
-    if return_index:
-        out["index"] = torch.empty(K, B, H, W, dtype=torch.int32, device=dev)
-    with torch.cuda.device(dev):
-        _hip.call("cpn_splat_resolve", zbuf.data_ptr(), rgb.data_ptr(), K, B, cap, H, W, fill, bg[0] | bg[1] << 8 | bg[2] << 16,
-                  out["frames"].data_ptr(), out["depth"].data_ptr() if return_depth else None,
-                  out["index"].data_ptr() if return_index else None, _hip.stream_handle())
+    out, (frames, depth, index, _) = frame_outputs(K, B, H, W, zbuf.device, return_depth, return_index)
+    with torch.cuda.device(zbuf.device):
+        _hip.call("cpn_splat_resolve", zbuf.data_ptr(), rgb.data_ptr(), K, B, cap, H, W, fill, word, frames, depth, index,
+                  _hip.stream_handle())
     return out
 
 
@@ -127,8 +94,7 @@ def draw(cloud, poses: torch.Tensor, intrinsics: torch.Tensor, H: int, W: int, r
 def score_counts(frames: torch.Tensor, index: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
     """cpn_splat_score: stats (K, B, 2) int64 = (the number n of pixels with index >= 0, the sum over them and their three
     channels of (frames - target)^2) of frames and target (K, B, H, W, 3) uint8 and index (K, B, H, W) int32."""
-    if not all(torch.is_tensor(x) and x.is_cuda and x.is_contiguous() and x.device == frames.device for x in (frames, index, target)):
-        raise RuntimeError("score: contiguous tensors on one HIP device (coponerf_amd has no non-HIP compute path)")
+    one_device("score", frames, index, target)
     if frames.dtype != torch.uint8 or frames.dim() != 5 or frames.shape[4] != 3 or target.dtype != torch.uint8 or \
             target.shape != frames.shape or index.dtype != torch.int32 or index.shape != frames.shape[:4]:
         raise ValueError(f"score: frames and target (K, B, H, W, 3) uint8 and index (K, B, H, W) int32, got {tuple(frames.shape)} "
@@ -211,17 +177,23 @@ def cross_view_check(model, model_input: Dict, radius: int = 1, fill: int = 1) -
     is mostly invalid.  This package's definition; not tried on a trained checkpoint."""
     from .point_cloud import from_views
     ctx = model_input["context"]
-    B, S = int(ctx["rgb"].shape[0]), int(ctx["rgb"].shape[2])
+    S = int(ctx["rgb"].shape[2])
     res = render_path(model, model_input, (0.0, 1.0), return_rgb=True, return_depth=True)
-    coverage, psnr = [], []
+    scores = []
     for src in (0, 1):
         dst = 1 - src
         views = {k: res[k][src:src + 1].contiguous() for k in ("depth", "valid", "rgb", "poses")}
         cloud = from_views(views, model_input["query"]["intrinsics"], S, min_votes=0)
         out = draw(cloud, res["poses"][dst:dst + 1].contiguous(), ctx["intrinsics"][:, dst].contiguous(), S, S, radius=radius,
                    fill=fill, return_index=True)
-        photo = pack_frames(ctx["rgb"][:, dst].contiguous(), torch.empty(B, S, S, 3, dtype=torch.uint8, device=ctx["rgb"].device))
-        c, p = score(out["frames"], out["index"], photo.unsqueeze(0))
-        coverage.append(c[0])
-        psnr.append(p[0])
-    return torch.stack(coverage), torch.stack(psnr)
+        scores.append(score_photo(out, ctx["rgb"][:, dst]))
+    return torch.stack([c for c, _ in scores]), torch.stack([p for _, p in scores])
+
+
+def score_photo(out: Dict[str, torch.Tensor], photo: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(coverage (B), psnr (B)) of a draw into ONE camera (`frames` and `index` with K = 1: splat.draw's, raster.draw's) against
+    the photo (B, H, W, 3) fp32 in [-1, 1] taken there, as bytes (pack_frames): what cross_view_check and raster.photo_check end in."""
+    _, B, H, W = out["index"].shape
+    target = pack_frames(photo.contiguous(), torch.empty(B, H, W, 3, dtype=torch.uint8, device=photo.device))
+    coverage, psnr = score(out["frames"], out["index"], target.unsqueeze(0))
+    return coverage[0], psnr[0]

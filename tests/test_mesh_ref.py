@@ -208,3 +208,17 @@ def test_ply_bytes_parse_back(n, m):
         ply_bytes(xyz.astype(np.float64), rgb, faces)
     with pytest.raises(ValueError):
         ply_bytes(xyz, rgb, faces.astype(np.int64))
+
+
+def test_entry_checks_refuse_host_tensors():
+    """Tiny CPU tensors of otherwise valid shape: K = 2 views of a 4 x 4 grid and a 2 x 2 x 2 volume.  No library load."""
+    import torch
+    from coponerf_amd import mesh
+    views = {"depth": torch.ones(2, 1, 16), "valid": torch.ones(2, 1, 16, dtype=torch.uint8), "rgb": torch.zeros(2, 1, 16, 3),
+             "poses": torch.eye(4).expand(2, 1, 4, 4).contiguous()}
+    with pytest.raises(RuntimeError, match="HIP device only"):
+        mesh.integrate(views, torch.eye(4).expand(1, 4, 4).contiguous(), 4, dims=(2, 2, 2), bounds=(torch.zeros(1, 3), torch.ones(1, 3)))
+    volume = mesh.Volume(torch.ones(1, 2, 2, 2), torch.zeros(1, 2, 2, 2, dtype=torch.uint8), torch.zeros(1, 2, 2, 2, 3),
+                         torch.zeros(1, 3), torch.ones(1, 3), torch.ones(1), (2, 2, 2))
+    with pytest.raises(RuntimeError, match="HIP device only"):
+        volume.extract()

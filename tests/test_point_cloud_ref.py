@@ -221,3 +221,15 @@ def test_new_symbols_are_declared():
     for name in ("cpn_depth_points", "cpn_depth_votes", "cpn_compact_points", "cpn_compact_points_scratch"):
         assert name in _hip.PROTOTYPES
     assert _hip.ABI_VERSION == 12 and _hip.CONSTANTS["COMPACT_TILE"] % _hip.CONSTANTS["COMPACT_FINISH"] == 0
+
+
+def test_entry_checks_refuse_host_tensors():
+    """Tiny CPU tensors of otherwise valid shape: K = 2 views of a 4 x 4 grid.  No library load."""
+    import torch
+    depth, poses, intr = torch.ones(2, 1, 16), torch.eye(4).expand(2, 1, 4, 4).contiguous(), torch.eye(4).expand(1, 4, 4).contiguous()
+    with pytest.raises(RuntimeError, match="HIP device only"):
+        pc.unproject(depth, poses, intr, 4)
+    with pytest.raises(RuntimeError, match="HIP device only"):
+        pc.vote(depth, poses, intr, 4, 1.0, 0.01)
+    with pytest.raises(RuntimeError, match="one HIP device"):
+        pc.compact(torch.ones(2, 1, 16, dtype=torch.uint8), torch.zeros(2, 1, 16, 3), torch.zeros(2, 1, 16, 3), 4, 4)

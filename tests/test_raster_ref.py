@@ -269,3 +269,17 @@ def test_headlight_is_brightest_where_the_surface_faces_the_camera():
     centre = (r - r.mean()) ** 2 + (c - c.mean()) ** 2 < 9
     rim = (r - r.mean()) ** 2 + (c - c.mean()) ** 2 > 49
     assert grey[r[centre], c[centre], 0].min() > 200 and grey[r[rim], c[rim], 0].mean() < grey[r[centre], c[centre], 0].mean() - 40
+
+
+def test_entry_checks_refuse_host_tensors():
+    """Tiny CPU tensors of otherwise valid shape: one triangle, one camera, H = W = 4.  No library load."""
+    import torch
+    from coponerf_amd import raster
+    from coponerf_amd.mesh import Mesh
+    one = torch.ones(1, dtype=torch.int32)
+    mesh = Mesh(torch.zeros(1, 3, 3), torch.zeros(1, 3, 3, dtype=torch.uint8), 3 * one, torch.tensor([[[0, 1, 2]]], dtype=torch.int32), one)
+    poses, intr = torch.eye(4).expand(1, 1, 4, 4).contiguous(), torch.eye(4).expand(1, 4, 4).contiguous()
+    with pytest.raises(RuntimeError, match="HIP device only"):
+        raster.raster_faces(mesh, poses, intr, 4, 4)
+    with pytest.raises(RuntimeError, match="HIP device only"):
+        raster.resolve(torch.full((1, 1, 4, 4), -1, dtype=torch.int64), mesh, poses, intr)

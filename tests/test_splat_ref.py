@@ -178,3 +178,16 @@ def test_symbols_are_declared_with_their_types():
     assert pr["cpn_splat_score_scratch"] == (I, [I] * 4)
     assert pr["cpn_splat_score"] == (I, [P] * 3 + [I] * 4 + [P] * 3)
     assert _hip.CONSTANTS["SPLAT_SCORE_TILE"] == 4096 and _hip.ABI_VERSION == 12
+
+
+def test_entry_checks_refuse_host_tensors():
+    """Tiny CPU tensors of otherwise valid shape: a 2-point cloud, one camera, H = W = 4.  No library load."""
+    from coponerf_amd.point_cloud import PointCloud
+    cloud = PointCloud(torch.zeros(1, 2, 3), torch.zeros(1, 2, 3, dtype=torch.uint8), torch.full((1,), 2, dtype=torch.int32))
+    with pytest.raises(RuntimeError, match="HIP device only"):
+        splat.splat_points(cloud, torch.eye(4).expand(1, 1, 4, 4).contiguous(), torch.eye(4).expand(1, 4, 4).contiguous(), 4, 4)
+    with pytest.raises(RuntimeError, match="one HIP device"):
+        splat.resolve(torch.full((1, 1, 4, 4), -1, dtype=torch.int64), cloud.rgb)
+    frames = torch.zeros(1, 1, 4, 4, 3, dtype=torch.uint8)
+    with pytest.raises(RuntimeError, match="one HIP device"):
+        splat.score_counts(frames, torch.zeros(1, 1, 4, 4, dtype=torch.int32), frames)
