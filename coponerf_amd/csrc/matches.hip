@@ -14,11 +14,13 @@
 //                             pass, no partials in HBM, no inter-workgroup synchronisation.  Pass `iters` only measures.
 //
 // The residual is float64 from the fp32 inputs, one rounding per operation (-ffp-contract=off), sums left to right:
-// tests/matches_ref.py restates all three in numpy.  Cam and Pose are pinhole.h's.
+// tests/matches_ref.py restates all three in numpy.  Cam and Pose are pinhole.h's; essential, sampson and residual_ok are sampson.h's,
+// which ransac.hip shares.
 #include "common.h"
 #include "compact.h"
 #include "flow_warp.h"
 #include "pinhole.h"
+#include "sampson.h"
 
 #include <math.h>
 
@@ -27,47 +29,6 @@ namespace {
 constexpr int NT = 256;
 constexpr int PTW = 32, PTH = NT / PTW;                    // match fields: the tile of one workgroup
 constexpr int NSUM = 30;                                   // refinement: H (21), g (6), cost, sum of weights, finite matches
-
-// E = [t]x R, row-major (a Pose's R[3][3] is such a matrix)
-__device__ __forceinline__ void essential(const double* R, const double* t, double* E) {
-    for (int j = 0; j < 3; ++j) {
-        E[0 + j] = t[1] * R[6 + j] - t[2] * R[3 + j];
-        E[3 + j] = t[2] * R[0 + j] - t[0] * R[6 + j];
-        E[6 + j] = t[0] * R[3 + j] - t[1] * R[0 + j];
-    }
-}
-
-// The pieces of the Sampson residual of the pixel pair (x0, y0) of view 0 and (x1, y1) of view 1
-struct Sampson {
-    double a0, a1, b0, b1;          // the normalised points (third component 1)
-    double g[4];                    // (E b)_0 / fx0, (E b)_1 / fy0, (E^T a)_0 / fx1, (E^T a)_1 / fy1
-    double n, D;
-};
-template <class Mat>
-__device__ __forceinline__ Sampson sampson(const Mat& E, const Cam& k0, const Cam& k1, double x0, double y0, double x1, double y1) {
-    Sampson s;
-    s.a0 = (x0 - k0.cx) / k0.fx;
-    s.a1 = (y0 - k0.cy) / k0.fy;
-    s.b0 = (x1 - k1.cx) / k1.fx;
-    s.b1 = (y1 - k1.cy) / k1.fy;
-    const double eb0 = (E[0] * s.b0 + E[1] * s.b1) + E[2];
-    const double eb1 = (E[3] * s.b0 + E[4] * s.b1) + E[5];
-    const double eb2 = (E[6] * s.b0 + E[7] * s.b1) + E[8];
-    const double ea0 = (E[0] * s.a0 + E[3] * s.a1) + E[6];
-    const double ea1 = (E[1] * s.a0 + E[4] * s.a1) + E[7];
-    s.n = (s.a0 * eb0 + s.a1 * eb1) + eb2;
-    s.g[0] = eb0 / k0.fx;
-    s.g[1] = eb1 / k0.fy;
-    s.g[2] = ea0 / k1.fx;
-    s.g[3] = ea1 / k1.fy;
-    s.D = ((s.g[0] * s.g[0] + s.g[1] * s.g[1]) + s.g[2] * s.g[2]) + s.g[3] * s.g[3];
-    return s;
-}
-__device__ __forceinline__ bool finite64(double v) { return fabs(v) <= 1.79769313486231570815e308; }      // false for NaN
-// the residual n / sqrt(D) counts iff D > 0 and n, D and the quotient are finite
-__device__ __forceinline__ bool residual_ok(const Sampson& s, double r) {
-    return s.D > 0.0 && finite64(s.D) && finite64(s.n) && finite64(r);
-}
 
 __global__ __launch_bounds__(NT) void match_fields_kernel(const float* __restrict__ flow0, const float* __restrict__ flow1,
                                                           const float* __restrict__ intrinsics, const float* __restrict__ rel_pose,

@@ -1,0 +1,508 @@
+// The relative pose of two photos from their matches alone (coponerf_amd/matches.py: ransac_pose): 8-point RANSAC.
+//
+//   ransac_hypotheses_kernel  cpn_ransac_hypotheses: one thread per hypothesis index h (workgroups of 64), every pair in the
+//                             launch.  The thread draws 8 distinct rows by a counter hash of (seed, h, draw), forms the 8 x 9
+//                             system of a^T E b = 0 and eliminates it with complete pivoting.  The 72 doubles, the solution and
+//                             the column permutation live in LDS, one column per lane ([entry][lane]: a lane's accesses never
+//                             meet another lane's bank), so that the pivot's runtime indices never touch a private array.
+//   ransac_score_kernel       cpn_ransac_score: grid (tiles of 256 hypotheses, chunks of CPN_RANSAC_CHUNK matches, pairs).  The
+//                             workgroup normalises its chunk into LDS once; each lane then holds one E in registers and walks
+//                             the chunk - every lane reads the same LDS address, a broadcast - and counts in a register.
+//   ransac_finish_kernel      cpn_ransac_finish: one workgroup per pair sums the partial counts, picks the winner, thread 0
+//                             splits its E by a one-sided Jacobi SVD, all threads mark the inliers and vote on the four poses.
+//
+// Every decision is an integer or a comparison of values that tests/ransac_ref.py forms in the same float64 sequence
+// (-ffp-contract=off): no atomics, integer sums only, the same bytes every run.  The residual is sampson.h's.
+#include "common.h"
+#include "pinhole.h"
+#include "sampson.h"
+
+#include "../../include/coponerf_hip.h"
+
+#include <math.h>
+
+namespace {
+
+constexpr int NT = 256;
+constexpr int HT = 64;                                     // hypotheses: threads per workgroup
+constexpr int CH = CPN_RANSAC_CHUNK;
+constexpr int DRAWS = 64;
+constexpr int SWEEPS = 8;
+constexpr double RANK_TOL = 1e-9;
+constexpr unsigned long long GOLDEN = 0x9E3779B97F4A7C15ull;
+
+__device__ __forceinline__ unsigned long long mix64(unsigned long long z) {      // splitmix64's finaliser
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
+__device__ __forceinline__ int clamp_count(int c, int N) { return c < 0 ? 0 : (c > N ? N : c); }
+__device__ __forceinline__ bool finite32(float v) { return fabsf(v) <= 3.402823466e38f; }               // false for NaN
+
+__global__ __launch_bounds__(HT) void ransac_hypotheses_kernel(const float* __restrict__ xy, const int* __restrict__ count,
+                                                               const float* __restrict__ intrinsics, int N, int Hn,
+                                                               unsigned long long seed, double* __restrict__ E,
+                                                               int* __restrict__ sample, uint8_t* __restrict__ valid) {
+    __shared__ double A[72][HT];                           // the system, row-major entry 9 r + c of lane l at A[9 r + c][l]
+    __shared__ double X[9][HT];                            // the solution in the permuted column order
+    __shared__ int perm[9][HT];                            // the column of E at each permuted position
+    const int l = threadIdx.x, h = blockIdx.x * HT + l, b = blockIdx.y;
+    if (h >= Hn) return;                                   // no barrier below: a lane touches its own LDS column only
+    const int n = clamp_count(count[b], N);
+    const size_t at = (size_t)b * Hn + h;
+
+    // ---- the draw
+    int s[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) s[j] = -1;
+    int got = 0;
+    const unsigned long long key = mix64(seed + GOLDEN * (unsigned long long)(h + 1));
+    for (int d = 0; d < DRAWS && got < 8; ++d) {
+        const unsigned long long u = mix64(key + GOLDEN * (unsigned long long)(d + 1));
+        const int idx = (int)(((u >> 32) * (unsigned long long)n) >> 32);
+        bool dup = false;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) dup = dup || s[j] == idx;
+        if (!dup && n > 0) {
+#pragma unroll
+            for (int j = 0; j < 8; ++j)
+                if (j == got) s[j] = idx;
+            ++got;
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < 8; ++j) sample[at * 8 + j] = s[j];
+
+    // ---- the system
+    bool ok = got == 8;
+    if (ok) {
+        const Cam k0 = load_cam(intrinsics + ((size_t)b * 2 + 0) * 16), k1 = load_cam(intrinsics + ((size_t)b * 2 + 1) * 16);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const float* const m = xy + ((size_t)b * N + s[j]) * 4;
+            const float x0 = m[0], y0 = m[1], x1 = m[2], y1 = m[3];
+            ok = ok && finite32(x0) && finite32(y0) && finite32(x1) && finite32(y1);
+            const double a0 = ((double)x0 - k0.cx) / k0.fx, a1 = ((double)y0 - k0.cy) / k0.fy;
+            const double b0 = ((double)x1 - k1.cx) / k1.fx, b1 = ((double)y1 - k1.cy) / k1.fy;
+            A[9 * j + 0][l] = a0 * b0;
+            A[9 * j + 1][l] = a0 * b1;
+            A[9 * j + 2][l] = a0;
+            A[9 * j + 3][l] = a1 * b0;
+            A[9 * j + 4][l] = a1 * b1;
+            A[9 * j + 5][l] = a1;
+            A[9 * j + 6][l] = b0;
+            A[9 * j + 7][l] = b1;
+            A[9 * j + 8][l] = 1.0;
+        }
+    }
+    // ---- elimination with complete pivoting
+    if (ok) {
+        for (int c = 0; c < 9; ++c) perm[c][l] = c;
+        double p0 = 0.0;
+        for (int k = 0; k < 8 && ok; ++k) {
+            double best = -1.0;
+            int pr = k, pc = k;
+            for (int r = k; r < 8; ++r)
+                for (int c = k; c < 9; ++c) {
+                    const double v = fabs(A[9 * r + c][l]);
+                    if (v > best) {                        // the first largest in (row, column) order; never a NaN
+                        best = v;
+                        pr = r;
+                        pc = c;
+                    }
+                }
+            if (pr != k)
+                for (int c = 0; c < 9; ++c) {
+                    const double v = A[9 * k + c][l];
+                    A[9 * k + c][l] = A[9 * pr + c][l];
+                    A[9 * pr + c][l] = v;
+                }
+            if (pc != k) {
+                for (int r = 0; r < 8; ++r) {
+                    const double v = A[9 * r + k][l];
+                    A[9 * r + k][l] = A[9 * r + pc][l];
+                    A[9 * r + pc][l] = v;
+                }
+                const int v = perm[k][l];
+                perm[k][l] = perm[pc][l];
+                perm[pc][l] = v;
+            }
+            const double p = A[9 * k + k][l];
+            if (k == 0) p0 = fabs(p);
+            ok = finite64(p) && fabs(p) > RANK_TOL * p0;   // the rank test
+            if (!ok) break;
+            for (int r = k + 1; r < 8; ++r) {
+                const double m = A[9 * r + k][l] / p;
+                for (int c = k + 1; c < 9; ++c) A[9 * r + c][l] = A[9 * r + c][l] - m * A[9 * k + c][l];
+            }
+        }
+    }
+    // ---- back substitution with the free (last) unknown 1, the norm and the sign
+    double e[9];
+#pragma unroll
+    for (int c = 0; c < 9; ++c) e[c] = 0.0;
+    if (ok) {
+        X[8][l] = 1.0;
+        for (int r = 7; r >= 0; --r) {
+            double sum = A[9 * r + r + 1][l] * X[r + 1][l];
+            for (int c = r + 2; c < 9; ++c) sum = sum + A[9 * r + c][l] * X[c][l];
+            X[r][l] = -sum / A[9 * r + r][l];
+        }
+        for (int c = 0; c < 9; ++c) A[perm[c][l]][l] = X[c][l];           // the system is spent: entries 0 .. 8 take E
+#pragma unroll
+        for (int c = 0; c < 9; ++c) e[c] = A[c][l];
+        double ss = e[0] * e[0];
+#pragma unroll
+        for (int c = 1; c < 9; ++c) ss = ss + e[c] * e[c];
+        const double nrm = sqrt(ss);
+        double big = -1.0, lead = 0.0;
+#pragma unroll
+        for (int c = 0; c < 9; ++c) {
+            e[c] = e[c] / nrm;
+            if (fabs(e[c]) > big) {
+                big = fabs(e[c]);
+                lead = e[c];
+            }
+        }
+#pragma unroll
+        for (int c = 0; c < 9; ++c) {
+            if (lead < 0.0) e[c] = -e[c];
+            ok = ok && finite64(e[c]);
+        }
+    }
+#pragma unroll
+    for (int c = 0; c < 9; ++c) E[at * 9 + c] = ok ? e[c] : 0.0;
+    valid[at] = ok ? 1 : 0;
+}
+
+__global__ __launch_bounds__(NT) void ransac_score_kernel(const double* __restrict__ E, const uint8_t* __restrict__ valid,
+                                                          const float* __restrict__ xy, const int* __restrict__ count,
+                                                          const float* __restrict__ intrinsics, const float* __restrict__ rel_pose,
+                                                          int N, int Hn, double inlier_px, int* __restrict__ partial) {
+    __shared__ double pts[CH][4];
+    const int tid = threadIdx.x, chunk = blockIdx.y, b = blockIdx.z;
+    const int n = clamp_count(count[b], N), start = chunk * CH;
+    const int m = n - start < CH ? n - start : CH;         // the rows of this chunk below the count (<= 0: none)
+    const Cam k0 = load_cam(intrinsics + ((size_t)b * 2 + 0) * 16), k1 = load_cam(intrinsics + ((size_t)b * 2 + 1) * 16);
+    for (int i = tid; i < m; i += NT) {
+        const float* const row = xy + ((size_t)b * N + start + i) * 4;
+        pts[i][0] = ((double)row[0] - k0.cx) / k0.fx;
+        pts[i][1] = ((double)row[1] - k0.cy) / k0.fy;
+        pts[i][2] = ((double)row[2] - k1.cx) / k1.fx;
+        pts[i][3] = ((double)row[3] - k1.cy) / k1.fy;
+    }
+    __syncthreads();
+    const int slot = blockIdx.x * NT + tid;
+    if (slot > Hn) return;
+    double e[9];
+    bool on = m > 0;
+    if (slot < Hn) {
+        const size_t at = (size_t)b * Hn + slot;
+        on = on && valid[at] != 0;
+#pragma unroll
+        for (int c = 0; c < 9; ++c) e[c] = on ? E[at * 9 + c] : 0.0;
+    } else {                                               // the extra slot: rel_pose's own E, where there is one
+        on = on && rel_pose != nullptr;
+        if (on) {
+            const Pose rel = load_pose(rel_pose + (size_t)b * 16);
+            essential(&rel.R[0][0], rel.t, e);
+        }
+    }
+    int cnt = 0;
+    if (on) {
+        for (int i = 0; i < m; ++i) {
+            const Sampson s = sampson_normalised(e, k0, k1, pts[i][0], pts[i][1], pts[i][2], pts[i][3]);
+            const double r = s.n / sqrt(s.D);
+            if (residual_ok(s, r) && fabs(r) <= inlier_px) ++cnt;
+        }
+    }
+    partial[((size_t)b * gridDim.y + chunk) * (Hn + 1) + slot] = cnt;
+}
+
+// ---- finish
+// a value of every thread of the 256 combined by op, returned in every thread; red: 4 values in LDS
+template <class Op>
+__device__ __forceinline__ long long block_all(long long v, Op op, long long* red) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = op(v, __shfl_xor(v, o));
+    __syncthreads();                                       // red is free of its last use
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return op(op(red[0], red[1]), op(red[2], red[3]));
+}
+
+// one rotation of the one-sided Jacobi method: columns p and q of G (and of V) are turned so that G's become orthogonal
+__device__ __forceinline__ void jacobi_pair(double (&G)[9], double (&V)[9], int p, int q) {
+    const double alpha = (G[p] * G[p] + G[3 + p] * G[3 + p]) + G[6 + p] * G[6 + p];
+    const double beta = (G[q] * G[q] + G[3 + q] * G[3 + q]) + G[6 + q] * G[6 + q];
+    const double gamma = (G[p] * G[q] + G[3 + p] * G[3 + q]) + G[6 + p] * G[6 + q];
+    if (gamma == 0.0) return;
+    const double zeta = (beta - alpha) / (2.0 * gamma);
+    const double root = fabs(zeta) + sqrt(1.0 + zeta * zeta);
+    const double tt = (zeta < 0.0 ? -1.0 : 1.0) / root;
+    const double c = 1.0 / sqrt(1.0 + tt * tt), s = c * tt;
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+        const double gp = G[3 * r + p], gq = G[3 * r + q];
+        G[3 * r + p] = c * gp - s * gq;
+        G[3 * r + q] = s * gp + c * gq;
+        const double vp = V[3 * r + p], vq = V[3 * r + q];
+        V[3 * r + p] = c * vp - s * vq;
+        V[3 * r + q] = s * vp + c * vq;
+    }
+}
+__device__ __forceinline__ double norm3(const double* v) { return sqrt((v[0] * v[0] + v[1] * v[1]) + v[2] * v[2]); }
+__device__ __forceinline__ void cross3(const double* a, const double* b, double* o) {
+    o[0] = a[1] * b[2] - a[2] * b[1];
+    o[1] = a[2] * b[0] - a[0] * b[2];
+    o[2] = a[0] * b[1] - a[1] * b[0];
+}
+__device__ __forceinline__ void swap_columns(double (&G)[9], double (&V)[9], double (&sg)[3], int p, int q) {
+    for (int r = 0; r < 3; ++r) {
+        const double g = G[3 * r + p], v = V[3 * r + p];
+        G[3 * r + p] = G[3 * r + q];
+        G[3 * r + q] = g;
+        V[3 * r + p] = V[3 * r + q];
+        V[3 * r + q] = v;
+    }
+    const double x = sg[p];
+    sg[p] = sg[q];
+    sg[q] = x;
+}
+// a right-handed orthonormal frame from columns c0 and c1 of M: f0 = c0 / |c0|, f1 = (c1 - (f0 . c1) f0) / |..|, f2 = f0 x f1
+__device__ __forceinline__ void frame(const double (&M)[9], int c0, int c1, double (&F)[3][3]) {
+    const double a[3] = {M[c0], M[3 + c0], M[6 + c0]}, b[3] = {M[c1], M[3 + c1], M[6 + c1]};
+    const double la = norm3(a);
+    for (int i = 0; i < 3; ++i) F[0][i] = a[i] / la;
+    const double d = (F[0][0] * b[0] + F[0][1] * b[1]) + F[0][2] * b[2];
+    double w[3];
+    for (int i = 0; i < 3; ++i) w[i] = b[i] - d * F[0][i];
+    const double lw = norm3(w);
+    for (int i = 0; i < 3; ++i) F[1][i] = w[i] / lw;
+    cross3(F[0], F[1], F[2]);
+}
+
+struct FinishState {
+    double E[9], R[2][9], t[3];
+    long long red[4];
+    int ok;
+};
+
+__global__ __launch_bounds__(NT) void ransac_finish_kernel(const double* __restrict__ E, const uint8_t* __restrict__ valid,
+                                                           const int* __restrict__ partial, const float* __restrict__ xy,
+                                                           const int* __restrict__ count, const float* __restrict__ intrinsics,
+                                                           const float* __restrict__ rel_pose, int N, int Hn, int chunks,
+                                                           double inlier_px, float* __restrict__ pose,
+                                                           uint8_t* __restrict__ inlier, double* __restrict__ stats) {
+    __shared__ FinishState st;
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const int n = clamp_count(count[b], N);
+    const float* const rows = xy + (size_t)b * N * 4;
+    const float* const P = rel_pose ? rel_pose + (size_t)b * 16 : nullptr;
+    uint8_t* const mask = inlier + (size_t)b * N;
+    float* const o = pose + (size_t)b * 16;
+    double* const so = stats + (size_t)b * 8;
+    const auto add = [](long long x, long long y) { return x + y; };
+    const auto larger = [](long long x, long long y) { return x > y ? x : y; };
+
+    long long mine = 0;
+    for (int i = tid; i < n; i += NT) {
+        const float* const m = rows + (size_t)i * 4;
+        mine += (finite32(m[0]) && finite32(m[1]) && finite32(m[2]) && finite32(m[3])) ? 1 : 0;
+    }
+    const long long usable = block_all(mine, add, st.red);
+
+    // the winner: most inliers, the lower index on ties - the largest of count << 32 | ~index
+    const int used = (n + CH - 1) / CH;                    // the chunks beyond hold zeros
+    const int* const part = partial + (size_t)b * chunks * (Hn + 1);
+    long long best = -1, n_valid = 0, rel_count = 0;
+    for (int h = tid; h < Hn; h += NT) {
+        if (!valid[(size_t)b * Hn + h]) continue;
+        ++n_valid;
+        if (usable < 8) continue;
+        long long sum = 0;
+        for (int c = 0; c < used; ++c) sum += part[(size_t)c * (Hn + 1) + h];
+        best = larger(best, (sum << 32) | (long long)(0x7FFFFFFF - h));
+    }
+    if (P)
+        for (int c = tid; c < used; c += NT) rel_count += part[(size_t)c * (Hn + 1) + Hn];
+    best = block_all(best, larger, st.red);
+    n_valid = block_all(n_valid, add, st.red);
+    rel_count = block_all(rel_count, add, st.red);
+    const int winner = best < 0 ? 0 : 0x7FFFFFFF - (int)(best & 0x7FFFFFFF);
+    const long long winner_count = best < 0 ? 0 : best >> 32;
+
+    if (tid == 0) {
+        st.ok = 0;
+        if (best >= 0) {
+            double G[9], V[9] = {1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0};
+            for (int c = 0; c < 9; ++c) G[c] = st.E[c] = E[((size_t)b * Hn + winner) * 9 + c];
+            for (int sweep = 0; sweep < SWEEPS; ++sweep) {
+                jacobi_pair(G, V, 0, 1);
+                jacobi_pair(G, V, 0, 2);
+                jacobi_pair(G, V, 1, 2);
+            }
+            // the columns by descending norm (three compare-and-swaps, a swap only where strictly smaller comes first)
+            double sg[3];
+            for (int c = 0; c < 3; ++c) sg[c] = sqrt((G[c] * G[c] + G[3 + c] * G[3 + c]) + G[6 + c] * G[6 + c]);
+            if (sg[0] < sg[1]) swap_columns(G, V, sg, 0, 1);
+            if (sg[1] < sg[2]) swap_columns(G, V, sg, 1, 2);
+            if (sg[0] < sg[1]) swap_columns(G, V, sg, 0, 1);
+            double U[3][3], W[3][3];                       // the frames' vectors by rows: U[k] = u_k, W[k] = v_k
+            frame(G, 0, 1, U);
+            frame(V, 0, 1, W);
+            bool fin = true;
+            for (int i = 0; i < 3; ++i)
+                for (int j = 0; j < 3; ++j) {
+                    const double r1 = (U[1][i] * W[0][j] - U[0][i] * W[1][j]) + U[2][i] * W[2][j];
+                    const double r2 = (U[0][i] * W[1][j] - U[1][i] * W[0][j]) + U[2][i] * W[2][j];
+                    st.R[0][3 * i + j] = r1;
+                    st.R[1][3 * i + j] = r2;
+                    fin = fin && finite64(r1) && finite64(r2);
+                }
+            for (int i = 0; i < 3; ++i) st.t[i] = U[2][i];
+            st.ok = fin ? 1 : 0;
+        }
+    }
+    __syncthreads();
+    const bool solved = st.ok != 0;
+
+    // the inliers of the winner and their votes: candidate (R, +t) holds where both depths are positive, (R, -t) where both
+    // are negative
+    long long votes[4] = {0, 0, 0, 0};
+    const Cam k0 = load_cam(intrinsics + ((size_t)b * 2 + 0) * 16), k1 = load_cam(intrinsics + ((size_t)b * 2 + 1) * 16);
+    for (int i = tid; i < N; i += NT) {
+        bool in = false;
+        if (solved && i < n) {
+            const float* const m = rows + (size_t)i * 4;
+            const Sampson s = sampson(st.E, k0, k1, (double)m[0], (double)m[1], (double)m[2], (double)m[3]);
+            const double r = s.n / sqrt(s.D);
+            in = residual_ok(s, r) && fabs(r) <= inlier_px;
+            if (in) {
+                const double a[3] = {s.a0, s.a1, 1.0};
+#pragma unroll
+                for (int k = 0; k < 2; ++k) {
+                    const double* const R = st.R[k];
+                    double c[3], ac[3], tc[3], ta[3];
+                    for (int j = 0; j < 3; ++j) c[j] = (R[3 * j] * s.b0 + R[3 * j + 1] * s.b1) + R[3 * j + 2];
+                    cross3(a, c, ac);
+                    cross3(st.t, c, tc);
+                    cross3(st.t, a, ta);
+                    const double z0 = (tc[0] * ac[0] + tc[1] * ac[1]) + tc[2] * ac[2];
+                    const double z1 = (ta[0] * ac[0] + ta[1] * ac[1]) + ta[2] * ac[2];
+                    votes[2 * k + 0] += (z0 > 0.0 && z1 > 0.0) ? 1 : 0;
+                    votes[2 * k + 1] += (z0 < 0.0 && z1 < 0.0) ? 1 : 0;
+                }
+            }
+        }
+        mask[i] = in ? 1 : 0;
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) votes[k] = block_all(votes[k], add, st.red);
+    if (tid != 0) return;
+
+    // rel_pose: its length where it is finite and not zero, its inliers under the same rule
+    double len0 = 0.0;
+    bool rel_ok = false;
+    Pose rel;
+    if (P) {
+        rel = load_pose(P);
+        rel_ok = true;
+        for (int r = 0; r < 3; ++r) {
+            for (int c = 0; c < 3; ++c) rel_ok = rel_ok && finite64(rel.R[r][c]);
+            rel_ok = rel_ok && finite64(rel.t[r]);
+        }
+        len0 = sqrt((rel.t[0] * rel.t[0] + rel.t[1] * rel.t[1]) + rel.t[2] * rel.t[2]);
+        rel_ok = rel_ok && len0 > 0.0 && finite64(len0);
+    }
+    const bool nothing = usable < 8 || Hn == 0;
+    if (nothing || !solved) {                              // status 2, or 1: no valid hypothesis
+        for (int k = 0; k < 16; ++k) o[k] = P ? P[k] : ((k % 5 == 0) ? 1.0f : 0.0f);
+        for (int k = 0; k < 8; ++k) so[k] = 0.0;
+        so[1] = nothing ? 0.0 : (double)usable;
+        so[4] = (P && !nothing) ? (double)rel_count : -1.0;
+        so[7] = nothing ? 2.0 : 1.0;
+        return;
+    }
+    int pick = 0;
+    for (int k = 1; k < 4; ++k)
+        if (votes[k] > votes[pick]) pick = k;              // most votes, the lowest candidate on ties
+    const double* const R = st.R[pick >> 1];
+    const double sign = (pick & 1) ? -1.0 : 1.0, scale = rel_ok ? len0 : 1.0;
+    double dR = 0.0, dt = 0.0;
+    for (int r = 0; r < 3; ++r) {
+        const double tr = sign * st.t[r];
+        for (int c = 0; c < 3; ++c) {
+            o[4 * r + c] = (float)R[3 * r + c];
+            if (rel_ok) {
+                const double e = R[3 * r + c] - rel.R[r][c];
+                dR += e * e;
+            }
+        }
+        o[4 * r + 3] = (float)(scale * tr);
+        if (rel_ok) {
+            const double e = tr - rel.t[r] / len0;
+            dt += e * e;
+        }
+        o[12 + r] = 0.0f;
+    }
+    o[15] = 1.0f;
+    const double deg = 57.29577951308232;
+    so[0] = (double)winner_count;
+    so[1] = (double)usable;
+    so[2] = (double)winner;
+    so[3] = (double)n_valid;
+    so[4] = P ? (double)rel_count : -1.0;
+    so[5] = 2.0 * asin(fmin(sqrt(dR) / 2.8284271247461903, 1.0)) * deg;
+    so[6] = 2.0 * asin(fmin(sqrt(dt) / 2.0, 1.0)) * deg;
+    so[7] = 0.0;
+}
+
+bool shape_ok(int B, int N, int Hn) {
+    return B >= 1 && B <= 32767 && N >= 1 && N <= (1 << 24) && Hn >= 0 && Hn <= (1 << 20) &&
+           (long long)B * cpn_cdiv(N, CH) * (Hn + 1LL) < (1LL << 31);
+}
+bool px_ok(double px) { return px >= 0.0 && px <= 1.79769313486231570815e308; }
+
+}  // namespace
+
+extern "C" int cpn_ransac_hypotheses(const float* xy, const int* count, const float* intrinsics, int B, int N, int Hn, long long seed,
+                                     double* E, int* sample, uint8_t* valid, void* stream) {
+    CPN_REQUIRE(xy && count && intrinsics && E && sample && valid, CPN_E_ARG, "cpn_ransac_hypotheses: null pointer");
+    CPN_REQUIRE(shape_ok(B, N, Hn) && Hn >= 1, CPN_E_SHAPE,
+                "cpn_ransac_hypotheses: need 1 <= B <= 32767, 1 <= N <= 2^24, 1 <= Hn <= 2^20 and B chunks (Hn + 1) < 2^31 (got B %d, "
+                "N %d, Hn %d)", B, N, Hn);
+    hipLaunchKernelGGL(ransac_hypotheses_kernel, dim3(cpn_cdiv(Hn, HT), B), dim3(HT), 0, (hipStream_t)stream, xy, count, intrinsics, N,
+                       Hn, (unsigned long long)seed, E, sample, valid);
+    CPN_LAUNCH_CHECK("cpn_ransac_hypotheses");
+    return 0;
+}
+
+extern "C" int cpn_ransac_score(const double* E, const uint8_t* valid, const float* xy, const int* count, const float* intrinsics,
+                                const float* rel_pose, int B, int N, int Hn, double inlier_px, int* partial, void* stream) {
+    CPN_REQUIRE(xy && count && intrinsics && partial && (Hn == 0 || (E && valid)), CPN_E_ARG, "cpn_ransac_score: null pointer");
+    CPN_REQUIRE(shape_ok(B, N, Hn), CPN_E_SHAPE,
+                "cpn_ransac_score: need 1 <= B <= 32767, 1 <= N <= 2^24, 0 <= Hn <= 2^20 and B chunks (Hn + 1) < 2^31 (got B %d, N %d, "
+                "Hn %d)", B, N, Hn);
+    CPN_REQUIRE(px_ok(inlier_px), CPN_E_ARG, "cpn_ransac_score: need a finite inlier_px >= 0 (got %g)", inlier_px);
+    const dim3 grid(cpn_cdiv(Hn + 1, NT), cpn_cdiv(N, CH), B);
+    hipLaunchKernelGGL(ransac_score_kernel, grid, dim3(NT), 0, (hipStream_t)stream, E, valid, xy, count, intrinsics, rel_pose, N, Hn,
+                       inlier_px, partial);
+    CPN_LAUNCH_CHECK("cpn_ransac_score");
+    return 0;
+}
+
+extern "C" int cpn_ransac_finish(const double* E, const uint8_t* valid, const int* partial, const float* xy, const int* count,
+                                 const float* intrinsics, const float* rel_pose, int B, int N, int Hn, double inlier_px, float* pose,
+                                 uint8_t* inlier, double* stats, void* stream) {
+    CPN_REQUIRE(partial && xy && count && intrinsics && pose && inlier && stats && (Hn == 0 || (E && valid)), CPN_E_ARG,
+                "cpn_ransac_finish: null pointer");
+    CPN_REQUIRE(shape_ok(B, N, Hn), CPN_E_SHAPE,
+                "cpn_ransac_finish: need 1 <= B <= 32767, 1 <= N <= 2^24, 0 <= Hn <= 2^20 and B chunks (Hn + 1) < 2^31 (got B %d, N %d, "
+                "Hn %d)", B, N, Hn);
+    CPN_REQUIRE(px_ok(inlier_px), CPN_E_ARG, "cpn_ransac_finish: need a finite inlier_px >= 0 (got %g)", inlier_px);
+    hipLaunchKernelGGL(ransac_finish_kernel, dim3(B), dim3(NT), 0, (hipStream_t)stream, E, valid, partial, xy, count, intrinsics,
+                       rel_pose, N, Hn, (int)cpn_cdiv(N, CH), inlier_px, pose, inlier, stats);
+    CPN_LAUNCH_CHECK("cpn_ransac_finish");
+    return 0;
+}

@@ -9,7 +9,9 @@ round.  The reference uses them for the cycle loss and a warped panel only.  Her
   select        the keep mask with stock ops, cpn_compact_matches -> a Matches
   Matches       xy (x0, y0, x1, y1) / err (cycle, epi) / count on the device; numpy(b) is the one host read
   refine_pose   robust Gauss-Newton of the relative pose on the Sampson residuals of the matches: cpn_refine_pose, one launch
-  from_pair     get_z once, then the three above
+  ransac_pose   the relative pose from the matches ALONE: 8-point RANSAC, cpn_ransac_hypotheses / _score / _finish, three
+                launches; with it the inlier count of rel_pose under the same rule and an inlier mask
+  from_pair     get_z once, then the three above (and ransac_pose with ransac={...})
   photo_coords  host: matches of a prepare_pair dict in the coordinates of the original photos
 
 The conventions and the arithmetic are in include/coponerf_hip.h (round 16).  The selection defaults (cycle error up to 10
@@ -17,6 +19,11 @@ pixels - the reference's own mask -, one match per native flow cell) and scale_p
 tried on a trained checkpoint, because none is available offline; whether the refined pose is closer to the truth than the
 network's on real data is unknown.  The epipolar residual cannot see the translation's length: the refined pose keeps the
 network's.
+
+refine_pose is a local method: from a rel_pose 30 degrees off it does not move.  ransac_pose (round 20 of the header) does not
+look at rel_pose to find its pose, so the pose head cannot spoil it; `ransac={..., "start": "ransac" | "best"}` lets from_flows
+and from_pair refine from it.  Its sampler, solver, threshold and hypothesis count are this package's definitions as well and
+are as untried on a trained checkpoint; the linear 8-point solver is degenerate for a planar scene and for a pure rotation.
 """
 from __future__ import annotations
 
@@ -152,6 +159,17 @@ def select(fields: Dict[str, torch.Tensor], max_cycle_px: float = 10.0, max_epi_
     return compact(keep.to(torch.uint8), fields["q"], cycle, epi)
 
 
+def _matches_args(who: str, matches: Matches) -> Tuple[int, int]:
+    xy, count = matches.xy, matches.count
+    if xy.dim() != 3 or xy.shape[2] != 4 or xy.shape[1] < 1:
+        raise ValueError(f"{who}: matches.xy must be (B, N, 4) with N >= 1, got {tuple(xy.shape)}")
+    B, N = int(xy.shape[0]), int(xy.shape[1])
+    if not torch.is_tensor(count) or count.device != xy.device or count.dtype != torch.int32 or tuple(count.shape) != (B,) or \
+            not count.is_contiguous():
+        raise ValueError(f"{who}: matches.count must be a contiguous ({B},) int32 tensor on xy's device")
+    return B, N
+
+
 @torch.no_grad()
 def refine_pose(matches: Matches, intrinsics: torch.Tensor, rel_pose: torch.Tensor, iters: int = 10,
                 scale_px: float = 2.0) -> Dict[str, torch.Tensor]:
@@ -164,12 +182,7 @@ def refine_pose(matches: Matches, intrinsics: torch.Tensor, rel_pose: torch.Tens
     xy, count = matches.xy, matches.count
     device_tensors("refine_pose", (("matches.xy", xy, torch.float32, None), ("intrinsics", intrinsics, torch.float32, None),
                                    ("rel_pose", rel_pose, torch.float32, None)))
-    if xy.dim() != 3 or xy.shape[2] != 4 or xy.shape[1] < 1:
-        raise ValueError(f"refine_pose: matches.xy must be (B, N, 4) with N >= 1, got {tuple(xy.shape)}")
-    B, N = int(xy.shape[0]), int(xy.shape[1])
-    if not torch.is_tensor(count) or count.device != xy.device or count.dtype != torch.int32 or tuple(count.shape) != (B,) or \
-            not count.is_contiguous():
-        raise ValueError(f"refine_pose: matches.count must be a contiguous ({B},) int32 tensor on xy's device")
+    B, N = _matches_args("refine_pose", matches)
     _cameras("refine_pose", intrinsics, rel_pose, B)
     if int(iters) < 0 or not 0.0 < float(scale_px) < float("inf"):
         raise ValueError(f"refine_pose: need iters >= 0 and a finite scale_px > 0, got {iters} and {scale_px}")
@@ -182,16 +195,98 @@ def refine_pose(matches: Matches, intrinsics: torch.Tensor, rel_pose: torch.Tens
 
 
 @torch.no_grad()
+def ransac_pose(matches: Matches, intrinsics: torch.Tensor, rel_pose: Optional[torch.Tensor] = None, hypotheses: int = 1024,
+                inlier_px: float = 1.0, seed: int = 0) -> Dict[str, torch.Tensor]:
+    """cpn_ransac_hypotheses, cpn_ransac_score, cpn_ransac_finish: `hypotheses` linear 8-point solutions from samples drawn by
+    a counter hash of (seed, hypothesis, draw) - the same for every pair -, each scored by its matches within inlier_px of
+    Sampson residual, the best split into the pose that puts its inliers in front of both cameras.  float64 inside, three
+    launches for all pairs, nothing read on the host -> `pose` (B, 4, 4) fp32 = [R | s t] with |t| = 1 and s the length of
+    rel_pose's translation (1 without a usable one: the residual cannot see it), `inlier` (B, N) uint8 and `stats` (B, 8)
+    float64: the winner's inliers, the usable matches, the winner's index, the valid hypotheses, the inliers of rel_pose under
+    the same rule (-1 without one), the angles in degrees between the pose and rel_pose (rotation, translation direction), the
+    status (0 ok, 1 no valid hypothesis, 2 nothing to do: fewer than 8 usable matches or hypotheses == 0 - pose is rel_pose,
+    or the identity without one).  rel_pose is only measured against, never searched from."""
+    xy, count = matches.xy, matches.count
+    named = [("matches.xy", xy, torch.float32, None), ("intrinsics", intrinsics, torch.float32, None)]
+    if rel_pose is not None:
+        named.append(("rel_pose", rel_pose, torch.float32, None))
+    device_tensors("ransac_pose", tuple(named))
+    B, N = _matches_args("ransac_pose", matches)
+    if tuple(intrinsics.shape) != (B, 2, 4, 4):
+        raise ValueError(f"ransac_pose: intrinsics must be (B, 2, 4, 4) with B = {B} (`context.intrinsics`), got {tuple(intrinsics.shape)}")
+    if rel_pose is not None and tuple(rel_pose.shape) != (B, 4, 4):
+        raise ValueError(f"ransac_pose: rel_pose must be (B, 4, 4) with B = {B}, got {tuple(rel_pose.shape)}")
+    Hn, px, seed = int(hypotheses), float(inlier_px), int(seed)
+    chunks = -(-N // _hip.CONSTANTS["RANSAC_CHUNK"])
+    if not 0 <= Hn <= 2 ** 20 or not 1 <= B <= 32767 or N > 2 ** 24 or B * chunks * (Hn + 1) >= 2 ** 31:
+        raise ValueError(f"ransac_pose: need 0 <= hypotheses <= 2^20, 1 <= B <= 32767, N <= 2^24 and B ceil(N / "
+                         f"{_hip.CONSTANTS['RANSAC_CHUNK']}) (hypotheses + 1) < 2^31, got hypotheses = {hypotheses}, B = {B}, N = {N}")
+    if not 0.0 <= px < float("inf"):
+        raise ValueError(f"ransac_pose: need a finite inlier_px >= 0, got {inlier_px}")
+    if not -2 ** 63 <= seed < 2 ** 63:
+        raise ValueError(f"ransac_pose: seed must fit 64 bits, got {seed}")
+    dev = xy.device
+    E = torch.empty(B, max(Hn, 1), 9, dtype=torch.float64, device=dev)
+    sample = torch.empty(B, max(Hn, 1), 8, dtype=torch.int32, device=dev)
+    valid = torch.empty(B, max(Hn, 1), dtype=torch.uint8, device=dev)
+    partial = torch.empty(B, chunks, Hn + 1, dtype=torch.int32, device=dev)
+    pose = torch.empty(B, 4, 4, dtype=torch.float32, device=dev)
+    inlier = torch.empty(B, N, dtype=torch.uint8, device=dev)
+    stats = torch.empty(B, 8, dtype=torch.float64, device=dev)
+    rel = 0 if rel_pose is None else rel_pose.data_ptr()
+    with torch.cuda.device(dev):
+        s = _hip.stream_handle()
+        if Hn:
+            _hip.call("cpn_ransac_hypotheses", xy.data_ptr(), count.data_ptr(), intrinsics.data_ptr(), B, N, Hn, seed, E.data_ptr(),
+                      sample.data_ptr(), valid.data_ptr(), s)
+        _hip.call("cpn_ransac_score", E.data_ptr(), valid.data_ptr(), xy.data_ptr(), count.data_ptr(), intrinsics.data_ptr(), rel, B, N,
+                  Hn, px, partial.data_ptr(), s)
+        _hip.call("cpn_ransac_finish", E.data_ptr(), valid.data_ptr(), partial.data_ptr(), xy.data_ptr(), count.data_ptr(),
+                  intrinsics.data_ptr(), rel, B, N, Hn, px, pose.data_ptr(), inlier.data_ptr(), stats.data_ptr(), s)
+    return {"pose": pose, "inlier": inlier, "stats": stats}
+
+
+_STARTS = ("network", "ransac", "best")
+
+
+def _ransac_keywords(who: str, ransac: Dict) -> Tuple[Dict, str]:
+    if not isinstance(ransac, dict):
+        raise ValueError(f"{who}: ransac must be None or a dict of ransac_pose's keywords and `start`, got {type(ransac).__name__}")
+    kw = dict(ransac)
+    start = kw.pop("start", "network")
+    if start not in _STARTS:
+        raise ValueError(f"{who}: ransac['start'] must be one of {_STARTS}, got {start!r}")
+    unknown = set(kw) - {"hypotheses", "inlier_px", "seed"}
+    if unknown:
+        raise ValueError(f"{who}: ransac holds unknown keywords {sorted(unknown)}")
+    return kw, start
+
+
+@torch.no_grad()
 def from_flows(flow: Sequence[torch.Tensor], intrinsics: torch.Tensor, rel_pose: torch.Tensor, S: int = 256, refine: bool = True,
                max_cycle_px: float = 10.0, max_epi_px: Optional[float] = None, stride: int = 4, iters: int = 10,
-               scale_px: float = 2.0) -> Dict:
+               scale_px: float = 2.0, ransac: Optional[Dict] = None) -> Dict:
     """from_pair's second half, for flows and a pose that get_z has already returned: four launches and the mask between them,
-    no host read."""
+    no host read.  ransac: None, or a dict of ransac_pose's keywords (hypotheses, inlier_px, seed) and `start`: three more
+    launches, and the result gains the key `ransac` (ransac_pose's dict).  start="network" (the default) refines from rel_pose
+    as without it, "ransac" from RANSAC's pose, "best" per pair from the one with more inliers under ransac_pose's rule (a tie
+    and a status other than 0 go to rel_pose; chosen by torch.where on the device)."""
+    if ransac is not None:
+        ransac_kw, start = _ransac_keywords("from_flows", ransac)
     fields = match_fields(flow, intrinsics, rel_pose, S)
     matches = select(fields, max_cycle_px=max_cycle_px, max_epi_px=max_epi_px, stride=stride)
     result = {"matches": matches, "rel_pose": rel_pose, "pose": None, "stats": None, "fields": fields}
+    begin = rel_pose
+    if ransac is not None:
+        found = result["ransac"] = ransac_pose(matches, intrinsics, rel_pose, **ransac_kw)
+        st = found["stats"]
+        if start == "ransac":
+            begin = found["pose"]
+        elif start == "best":
+            better = (st[:, 7] == 0) & (st[:, 0] > st[:, 4])
+            begin = torch.where(better[:, None, None], found["pose"], rel_pose)
     if refine:
-        result.update(refine_pose(matches, intrinsics, rel_pose, iters=iters, scale_px=scale_px))
+        result.update(refine_pose(matches, intrinsics, begin, iters=iters, scale_px=scale_px))
     return result
 
 
@@ -199,7 +294,8 @@ def from_flows(flow: Sequence[torch.Tensor], intrinsics: torch.Tensor, rel_pose:
 def from_pair(model, model_input: Dict, S: int = 256, refine: bool = True, **select_and_refine_keywords) -> Dict:
     """The matches of the pair(s) in model_input (prepare_pair's dict, or any dict get_z takes).  get_z runs once; its flows
     and its rel_pose - the ones novel_views.render_path hands on - go through match_fields, select and, with refine=True,
-    refine_pose.  Keywords: select's max_cycle_px, max_epi_px, stride and refine_pose's iters, scale_px.  Returns `matches` (a
+    refine_pose.  Keywords: select's max_cycle_px, max_epi_px, stride, refine_pose's iters, scale_px and from_flows' ransac
+    (with a dict the result gains the key `ransac`).  Returns `matches` (a
     Matches), `rel_pose` (B, 4, 4) as estimated, `pose` and `stats` as refine_pose returns them (None with refine=False) and
     `fields`, match_fields' dict.  Nothing is read on the host; Matches.numpy is the read."""
     _, rel_pose, flow = model.get_z(model_input)

@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define CPN_ABI_VERSION 12   /* cpn_attend_units (round 7), cpn_ssim_warp* (round 8), cpn_image_metrics* (round 9), summaries.hip (round 10), lpips.hip (round 11), novel_views.hip (round 12), epipolar.hip (round 13), cpn_lpips_*_bwd (round 14), point_cloud.hip (round 15), matches.hip (round 16), splat.hip (round 17), mesh.hip (round 18) and raster.hip (round 19) are additive - symbols added, none altered: the version stays */
+#define CPN_ABI_VERSION 12   /* cpn_attend_units (round 7), cpn_ssim_warp* (round 8), cpn_image_metrics* (round 9), summaries.hip (round 10), lpips.hip (round 11), novel_views.hip (round 12), epipolar.hip (round 13), cpn_lpips_*_bwd (round 14), point_cloud.hip (round 15), matches.hip (round 16), splat.hip (round 17), mesh.hip (round 18), raster.hip (round 19) and ransac.hip (round 20) are additive - symbols added, none altered: the version stays */
 
 #define CPN_E_ARG   (-1)   /* bad argument (null pointer, size, alignment) */
 #define CPN_E_SHAPE (-2)   /* shape not supported by the compiled tiles    */
@@ -1077,6 +1077,71 @@ int cpn_raster_faces(const float* xyz, const int* nvert, const int* faces, const
 int cpn_raster_resolve(const unsigned long long* zbuf, const float* xyz, const uint8_t* rgb, const int* nvert, const int* faces,
                        const float* poses, const float* intrinsics, int K, int B, int capv, int capf, int H, int W, int shade,
                        int background, uint8_t* frames, float* depth, int* index, float* bary, void* stream);
+
+/* ==== the relative pose from the matches alone: 8-point RANSAC (round 20) ================================================
+ * cpn_refine_pose is a local method that starts from rel_pose; these three give a pose that depends on the matches only, the
+ * inlier count of rel_pose under the same rule, and an inlier mask.  The symbols are additive: the ABI version stays.  The
+ * sampler, the solver, the threshold, the scoring and the choice among the four poses are THIS LIBRARY'S definitions.  There is
+ * no local optimisation inside the loop (cpn_refine_pose afterwards is that step), no adaptive stopping, no MSAC / MAGSAC
+ * scoring and no 5-point solver; the linear 8-point solver is degenerate for a planar scene and for a pure rotation.
+ * Conventions: round 16's.  xy (B, N, 4) fp32 = (x0, y0, x1, y1) with count (B) int32 on the device, n = min(max(count, 0), N);
+ *   rows at and beyond n are never read.  a = ((x0 - cx0) / fx0, (y0 - cy0) / fy0, 1), b likewise of view 1, float64 from the
+ *   fp32 inputs.  X0 = R X1 + t, E = [t]x R, a^T E b = 0; E (.., 9) float64 row-major.  One rounding per operation, sums left to
+ *   right, no fused multiply-add.  Hn hypotheses per pair.  1 <= B <= 32767, 1 <= N <= 2^24, Hn <= 2^20 and
+ *   B ceil(N / CPN_RANSAC_CHUNK) (Hn + 1) < 2^31 (CPN_E_SHAPE otherwise); inlier_px finite and >= 0 (CPN_E_ARG otherwise).
+ * cpn_ransac_hypotheses (Hn >= 1): ONE launch, one thread per (pair, hypothesis index h).
+ *   The draw: with mix(z) = splitmix64's finaliser (z ^= z >> 30; z *= 0xBF58476D1CE4E5B9; z ^= z >> 27;
+ *   z *= 0x94D049BB133111EB; z ^= z >> 31, 64-bit unsigned) and G = 0x9E3779B97F4A7C15, draw number d = 0, 1, .. of hypothesis h
+ *   is u = mix(mix(seed + G (h + 1)) + G (d + 1)) and the row index ((u >> 32) n) >> 32.  The pair index is NOT part of the key:
+ *   two equal pairs get equal samples, and a pair's result does not depend on the batch around it.  An index already taken is
+ *   skipped and the next draw number is used; after 64 draws without 8 distinct indices (always so for n < 8) the hypothesis
+ *   is invalid.  sample (B, Hn, 8) int32: the indices in the order drawn, -1 where none was.
+ *   The system: row j of the 8 x 9 matrix is (a0 b0, a0 b1, a0, a1 b0, a1 b1, a1, b0, b1, 1) of sampled match j.
+ *   The null vector: Gaussian elimination with COMPLETE pivoting.  Step k = 0 .. 7: the pivot is the entry of the largest
+ *   magnitude among rows k .. 7 and columns k .. 8, the first one in (row, column) order on ties; its row and column are
+ *   exchanged with row k and column k; RANK TEST: the hypothesis is invalid unless the pivot p_k is finite and
+ *   |p_k| > 1e-9 |p_0|; then row r > k becomes row_r - (A_rk / p_k) row_k on the columns beyond k.  Back substitution with
+ *   the unknown of the last column set to 1: x_r = -((A_r,r+1 x_r+1 + A_r,r+2 x_r+2) + .. + A_r8 x_8) / A_rr for r = 7 .. 0;
+ *   the exchanges of columns are undone; E = x / sqrt((x_0^2 + x_1^2) + .. + x_8^2), negated where its entry of the largest
+ *   magnitude (the lower index on ties) is negative.  A hypothesis is invalid also where one of the four values of a sampled row
+ *   or a value of E is not finite.  E (B, Hn, 9) float64, all 0 where invalid; valid (B, Hn) bytes 0 / 1.  Every element of
+ *   the three outputs is written.
+ * cpn_ransac_score: ONE launch over (tiles of 256 slots, chunks of CPN_RANSAC_CHUNK rows, pairs).  Slot h < Hn is hypothesis
+ *   h; slot Hn is rel_pose's own E = [t]x R in round 16's expression (rel_pose may be null: the slot is then 0 and nothing is
+ *   read).  A match is an INLIER of a slot iff its round-16 residual r under the slot's E counts and |r| <= inlier_px.  partial
+ *   (B, ceil(N / CPN_RANSAC_CHUNK), Hn + 1) int32: the inliers of the slot among the chunk's rows below n; 0 for an invalid
+ *   hypothesis and for a chunk at or beyond n.  Every element is written.  Integers: exact in any order, no atomics.  Hn may be
+ *   0 (E and valid are then not read).
+ * cpn_ransac_finish: ONE launch, one workgroup per pair.  usable = the rows below n with four finite values.  The WINNER is the
+ *   valid hypothesis with the largest sum of its partial counts, the lower index on ties.  Its E is split by a cyclic one-sided
+ *   Jacobi method on the columns of G = E with V = 1: 8 sweeps of the pairs (0, 1), (0, 2), (1, 2); for a pair (p, q) with
+ *   alpha = |G_p|^2, beta = |G_q|^2, gamma = G_p . G_q (each (x + y) + z down the rows), nothing where gamma == 0, otherwise
+ *   zeta = (beta - alpha) / (2 gamma), tt = sign(zeta) / (|zeta| + sqrt(1 + zeta zeta)) (sign(0) = 1), c = 1 / sqrt(1 + tt tt),
+ *   s = c tt, and columns p, q of G and of V become (c x_p - s x_q, s x_p + c x_q).  The columns are then ordered by descending
+ *   norm with the exchanges (0, 1), (1, 2), (0, 1), each made only where the earlier norm is strictly smaller.  From columns 0
+ *   and 1 of G: u_1 = G_0 / |G_0|, u_2 = w / |w| with w = G_1 - (u_1 . G_1) u_1, u_3 = u_1 x u_2; v_1, v_2, v_3 the same of V.
+ *   R1 = (u_2 v_1^T - u_1 v_2^T) + u_3 v_3^T, R2 = (u_1 v_2^T - u_2 v_1^T) + u_3 v_3^T, t = u_3: both rotations are orthonormal
+ *   to 1e-12 with determinant +1 by construction.  THE VOTE: every inlier of the winner, with c = R b (row sums
+ *   (R_j0 b_0 + R_j1 b_1) + R_j2), z_0 = (t x c) . (a x c) and z_1 = (t x a) . (a x c) - the depths of the point in views 0
+ *   and 1 times |a x c|^2 -, votes for (R, +t) where z_0 > 0 and z_1 > 0 and for (R, -t) where z_0 < 0 and z_1 < 0.  The pose is
+ *   the candidate with the most votes, the first of (R1, +t), (R1, -t), (R2, +t), (R2, -t) on ties.
+ *   pose (B, 4, 4) fp32 = [R | s t], last row 0 0 0 1, with s = sqrt((t0_0^2 + t0_1^2) + t0_2^2) of rel_pose's translation t0
+ *   where rel_pose is given, all twelve entries finite and s finite and > 0, otherwise s = 1 (the residual cannot see the
+ *   length).  inlier (B, N) bytes: 1 for the inliers of the winner, 0 elsewhere and at and beyond n; every byte is written.
+ *   stats (B, 8) float64: [0] the winner's inliers; [1] usable; [2] the winner's index; [3] the number of valid hypotheses;
+ *   [4] the inliers of rel_pose (-1 without one); [5], [6] the angles in degrees between R and rel_pose's rotation and between
+ *   the signed t and t0 / |t0|, in cpn_refine_pose's two formulas (0 without a usable rel_pose); [7] the status: 0 ok; 1 no
+ *   valid hypothesis, or a split that is not finite: pose and inlier as for status 2, [1] and [4] as for status 0, the rest
+ *   0; 2 nothing to do (usable < 8 or Hn == 0): pose is rel_pose's 16 values, or the identity without one, inlier is all 0,
+ *   [4] is -1 and the other six are 0.  No atomics: bit-reproducible, and a pair's result does not depend on the batch.    */
+#define CPN_RANSAC_CHUNK 256
+int cpn_ransac_hypotheses(const float* xy, const int* count, const float* intrinsics, int B, int N, int Hn, long long seed,
+                          double* E, int* sample, uint8_t* valid, void* stream);
+int cpn_ransac_score(const double* E, const uint8_t* valid, const float* xy, const int* count, const float* intrinsics,
+                     const float* rel_pose, int B, int N, int Hn, double inlier_px, int* partial, void* stream);
+int cpn_ransac_finish(const double* E, const uint8_t* valid, const int* partial, const float* xy, const int* count,
+                      const float* intrinsics, const float* rel_pose, int B, int N, int Hn, double inlier_px, float* pose,
+                      uint8_t* inlier, double* stats, void* stream);
 
 #ifdef __cplusplus
 }

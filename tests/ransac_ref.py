@@ -1,0 +1,463 @@
+"""Yardstick of coponerf_amd.matches.ransac_pose (csrc/ransac.hip): a numpy restatement, for ONE pair, of the three rules of
+include/coponerf_hip.h (round 20) in the header's operation sequence.  tests/test_ransac_ref.py holds it to independent forms on
+the CPU; tests/test_gpu_ransac.py compares the kernels with it.
+
+numpy float64 arithmetic is IEEE with one rounding per operation, which is what -ffp-contract=off gives the kernels, and every
+expression below is written in the kernels' order: the decisions (the samples, the pivots, the inliers, the winner, the votes)
+are integers or comparisons of values both sides form alike, so they are compared exactly - after the fixtures have been shown to
+keep every |r| at least MARGIN = 1e-9 px from the threshold and every depth expression at least 1e-9 from 0.  The residual, the
+scenes and the refinement are tests/matches_ref.py's.
+
+Bounds (E = 2^-53), from operation counts, none from a run:
+  null vector   per hypothesis |e - e_svd|_inf <= NULL_OPS E / (sigma_8 / sigma_1) with NULL_OPS = 1000: the conditioning of the
+                null vector of an 8 x 9 matrix times a generous count of the elimination's operations (8 steps of at most 8 x 9
+                updates of two operations, the back substitution, the norm), stated by the issue for sigma_8 / sigma_1 >= 1e-5.
+                The same bound holds a kernel's E to the restatement's: two float64 evaluations of one rule.
+  the split     split_bound: SPLIT_OPS E sigma_1 / (sigma_2 - sigma_3) per entry of R and t.  8 sweeps of 3 rotations of about
+                30 operations, the norms, the two Gram-Schmidt frames and the products of R: under 1000 operations, SPLIT_OPS =
+                1000; the rotations and t depend on the plane of the two large singular values only, whose conditioning is the
+                gap between sigma_2 and sigma_3 (0 for an essential matrix) relative to sigma_1.
+"""
+import functools
+
+import numpy as np
+
+from tests import matches_ref as mr
+
+E = mr.E
+CHUNK = 256
+DRAWS = 64
+SWEEPS = 8
+RANK_TOL = 1e-9
+NULL_OPS = 1000
+SPLIT_OPS = 1000
+MARGIN = 1e-9
+GOLDEN = np.uint64(0x9E3779B97F4A7C15)
+M1 = np.uint64(0xBF58476D1CE4E5B9)
+M2 = np.uint64(0x94D049BB133111EB)
+DEG = 57.29577951308232
+
+
+# ------------------------------------------------------------------------------------------------------------- the sampler
+def mix64(z):
+    """splitmix64's finaliser on uint64 arrays (wrapping)."""
+    z = (z ^ (z >> np.uint64(30))) * M1
+    z = (z ^ (z >> np.uint64(27))) * M2
+    return z ^ (z >> np.uint64(31))
+
+
+def draw_index(seed, h, d, n, pair=0, defect=None):
+    """Row index of draw d of hypothesis h (arrays broadcast): ((u >> 32) n) >> 32, u = mix(mix(seed + G (h + 1)) + G (d + 1)).
+    defect="pair in key": the pair index enters the key."""
+    with np.errstate(over="ignore"):
+        seed = np.asarray(int(seed) & (2 ** 64 - 1), dtype=np.uint64)
+        if defect == "pair in key":
+            seed = seed + np.uint64(pair) * M1
+        key = mix64(seed + GOLDEN * (np.asarray(h).astype(np.uint64) + np.uint64(1)))
+        u = mix64(key + GOLDEN * (np.asarray(d).astype(np.uint64) + np.uint64(1)))
+        return (((u >> np.uint64(32)) * np.uint64(n)) >> np.uint64(32)).astype(np.int64)
+
+
+def draw_samples(seed, Hn, n, pair=0, defect=None):
+    """-> (sample (Hn, 8) int32 in the order drawn, -1 where none was; got (Hn) the number drawn).  defect="no redraw": a
+    repeated index is taken."""
+    sample = np.full((Hn, 8), -1, dtype=np.int32)
+    got = np.zeros(Hn, dtype=np.int64)
+    h = np.arange(Hn)
+    if n > 0:
+        for d in range(DRAWS):
+            idx = draw_index(seed, h, d, n, pair, defect)
+            dup = (sample == idx[:, None]).any(axis=1)
+            if defect == "no redraw":
+                dup[:] = False
+            take = ~dup & (got < 8)
+            sample[h[take], got[take]] = idx[take]
+            got[take] += 1
+    return sample, got
+
+
+# ------------------------------------------------------------------------------------------------------------ the 8-point
+def normalised(xy, k0, k1):
+    xy = np.asarray(xy, dtype=np.float32).astype(np.float64)
+    with np.errstate(all="ignore"):
+        return ((xy[..., 0] - k0[2]) / k0[0], (xy[..., 1] - k0[3]) / k0[1], (xy[..., 2] - k1[2]) / k1[0], (xy[..., 3] - k1[3]) / k1[1])
+
+
+def system(a0, a1, b0, b1):
+    """(.., 9): the row (a0 b0, a0 b1, a0, a1 b0, a1 b1, a1, b0, b1, 1) of a^T E b = 0."""
+    with np.errstate(all="ignore"):
+        return np.stack((a0 * b0, a0 * b1, a0, a1 * b0, a1 * b1, a1, b0, b1, np.ones_like(a0)), axis=-1)
+
+
+def null_vector(A, defect=None):
+    """A (H, 8, 9) -> (e (H, 9) of Frobenius norm 1 with its largest entry positive, 0 where invalid; valid (H) bool): the
+    header's elimination with complete pivoting, rank test, back substitution, norm and sign.  defect="no rank test"."""
+    A = np.array(A, dtype=np.float64)
+    H = len(A)
+    ar = np.arange(H)
+    perm = np.tile(np.arange(9), (H, 1))
+    valid = np.ones(H, dtype=bool)
+    p0 = None
+    with np.errstate(all="ignore"):
+        for k in range(8):
+            sub = np.abs(A[:, k:, k:])
+            sub = np.where(np.isnan(sub), -1.0, sub)
+            flat = sub.reshape(H, -1).argmax(axis=1)               # the first largest in (row, column) order
+            pr, pc = k + flat // (9 - k), k + flat % (9 - k)
+            rk, rp = A[ar, k, :].copy(), A[ar, pr, :].copy()
+            A[ar, pr, :], A[ar, k, :] = rk, rp
+            ck, cp = A[ar, :, k].copy(), A[ar, :, pc].copy()
+            A[ar, :, pc], A[ar, :, k] = ck, cp
+            qk, qp = perm[ar, k].copy(), perm[ar, pc].copy()
+            perm[ar, pc], perm[ar, k] = qk, qp
+            p = A[:, k, k].copy()
+            if k == 0:
+                p0 = np.abs(p)
+            if defect != "no rank test":
+                valid &= np.isfinite(p) & (np.abs(p) > RANK_TOL * p0)
+            m = A[:, k + 1:, k] / p[:, None]
+            A[:, k + 1:, k + 1:] = A[:, k + 1:, k + 1:] - m[:, :, None] * A[:, k, None, k + 1:]
+        x = np.zeros((H, 9))
+        x[:, 8] = 1.0
+        for r in range(7, -1, -1):
+            s = A[:, r, r + 1] * x[:, r + 1]
+            for c in range(r + 2, 9):
+                s = s + A[:, r, c] * x[:, c]
+            x[:, r] = -s / A[:, r, r]
+        e = np.zeros((H, 9))
+        e[ar[:, None], perm] = x
+        ss = e[:, 0] * e[:, 0]
+        for c in range(1, 9):
+            ss = ss + e[:, c] * e[:, c]
+        e = e / np.sqrt(ss)[:, None]
+        mag = np.where(np.isnan(e), -1.0, np.abs(e))
+        lead = e[ar, mag.argmax(axis=1)]
+        e = np.where((lead < 0.0)[:, None], -e, e)
+        valid &= np.isfinite(e).all(axis=1)
+    e[~valid] = 0.0
+    return e, valid
+
+
+def hypotheses(xy, count, intrinsics, Hn, seed, pair=0, defect=None):
+    """The rule of cpn_ransac_hypotheses for one pair: xy (N, 4) fp32 -> (E (Hn, 9) float64, sample (Hn, 8) int32, valid (Hn)
+    uint8)."""
+    xy = np.asarray(xy, dtype=np.float32)
+    n = min(max(int(count), 0), len(xy))
+    sample, got = draw_samples(seed, Hn, n, pair, defect)
+    k0, k1 = mr.cam_of(intrinsics[0]), mr.cam_of(intrinsics[1])
+    rows = xy[np.maximum(sample, 0)]                                # (Hn, 8, 4)
+    ok = (got == 8) & np.isfinite(rows).all(axis=(1, 2))
+    A = system(*normalised(rows, k0, k1))
+    A[~ok] = 0.0
+    e, valid = null_vector(A, defect)
+    valid &= ok
+    e[~valid] = 0.0
+    return e, sample, valid.astype(np.uint8)
+
+
+# ------------------------------------------------------------------------------------------------------------- the score
+def residuals(Em, xy, intrinsics):
+    """Em (H, 9), xy (n, 4) fp32 -> (r (H, n), counts (H, n) bool): round 16's residual of every match under every E."""
+    k0, k1 = mr.cam_of(intrinsics[0]), mr.cam_of(intrinsics[1])
+    xy = np.asarray(xy, dtype=np.float32).astype(np.float64)
+    M = np.asarray(Em, dtype=np.float64).reshape(-1, 3, 3).transpose(1, 2, 0)[..., None]          # M[i, j]: (H, 1)
+    with np.errstate(all="ignore"):
+        s = mr.sampson(M, k0, k1, xy[None, :, 0], xy[None, :, 1], xy[None, :, 2], xy[None, :, 3])
+        r, ok = mr.residual(s)
+    return r, ok
+
+
+def inliers(Em, xy, intrinsics, inlier_px, defect=None):
+    """(H, n) bool.  defect="signed": r <= inlier_px without the magnitude."""
+    r, ok = residuals(Em, xy, intrinsics)
+    with np.errstate(invalid="ignore"):
+        return ok & ((r if defect == "signed" else np.abs(r)) <= inlier_px)
+
+
+def rel_essential(rel_pose):
+    P = np.asarray(rel_pose, dtype=np.float32).astype(np.float64)
+    with np.errstate(all="ignore"):
+        return mr.essential(P[:3, :3], P[:3, 3]).reshape(9)
+
+
+def score(Em, valid, xy, count, intrinsics, inlier_px, rel_pose=None, defect=None):
+    """The rule of cpn_ransac_score for one pair -> partial (ceil(N / CHUNK), Hn + 1) int32."""
+    N, Hn = len(xy), len(Em)
+    n = min(max(int(count), 0), N)
+    chunks = -(-N // CHUNK)
+    slots = np.zeros((Hn + 1, 9))
+    slots[:Hn] = Em
+    on = np.zeros(Hn + 1, dtype=bool)
+    on[:Hn] = np.asarray(valid) != 0
+    if rel_pose is not None:
+        slots[Hn], on[Hn] = rel_essential(rel_pose), True
+    inl = inliers(slots, xy[:n], intrinsics, inlier_px, defect) & on[:, None]
+    padded = np.zeros((Hn + 1, chunks * CHUNK), dtype=np.int32)
+    padded[:, :n] = inl
+    return np.ascontiguousarray(padded.reshape(Hn + 1, chunks, CHUNK).sum(axis=2).T.astype(np.int32))
+
+
+# ------------------------------------------------------------------------------------------------------------- the finish
+def _norm3(v):
+    return np.sqrt((v[0] * v[0] + v[1] * v[1]) + v[2] * v[2])
+
+
+def _cross(a, b):
+    return np.array([a[1] * b[2] - a[2] * b[1], a[2] * b[0] - a[0] * b[2], a[0] * b[1] - a[1] * b[0]])
+
+
+def _frame(M):
+    """Rows u_1, u_2, u_3 from columns 0 and 1 of M."""
+    a, b = M[:, 0], M[:, 1]
+    f0 = a / _norm3(a)
+    d = (f0[0] * b[0] + f0[1] * b[1]) + f0[2] * b[2]
+    w = b - d * f0
+    f1 = w / _norm3(w)
+    return np.stack((f0, f1, _cross(f0, f1)))
+
+
+def split(e, defect=None):
+    """The header's split of E (9) -> (R1, R2 (3, 3), t (3), sigma (3) the column norms in descending order).
+    defect="one sweep"."""
+    G, V = np.array(e, dtype=np.float64).reshape(3, 3), np.eye(3)
+    with np.errstate(all="ignore"):
+        for _ in range(1 if defect == "one sweep" else SWEEPS):
+            for p, q in ((0, 1), (0, 2), (1, 2)):
+                alpha = (G[0, p] * G[0, p] + G[1, p] * G[1, p]) + G[2, p] * G[2, p]
+                beta = (G[0, q] * G[0, q] + G[1, q] * G[1, q]) + G[2, q] * G[2, q]
+                gamma = (G[0, p] * G[0, q] + G[1, p] * G[1, q]) + G[2, p] * G[2, q]
+                if gamma == 0.0:
+                    continue
+                zeta = (beta - alpha) / (2.0 * gamma)
+                root = np.abs(zeta) + np.sqrt(1.0 + zeta * zeta)
+                tt = (-1.0 if zeta < 0.0 else 1.0) / root
+                c = 1.0 / np.sqrt(1.0 + tt * tt)
+                s = c * tt
+                for X in (G, V):
+                    xp, xq = X[:, p].copy(), X[:, q].copy()
+                    X[:, p] = c * xp - s * xq
+                    X[:, q] = s * xp + c * xq
+        sg = np.array([_norm3(G[:, c]) for c in range(3)])
+        for p, q in ((0, 1), (1, 2), (0, 1)):
+            if sg[p] < sg[q]:
+                for X in (G, V):
+                    X[:, [p, q]] = X[:, [q, p]]
+                sg[[p, q]] = sg[[q, p]]
+        U, W = _frame(G), _frame(V)
+        R1, R2 = np.empty((3, 3)), np.empty((3, 3))
+        for i in range(3):
+            for j in range(3):
+                R1[i, j] = (U[1, i] * W[0, j] - U[0, i] * W[1, j]) + U[2, i] * W[2, j]
+                R2[i, j] = (U[0, i] * W[1, j] - U[1, i] * W[0, j]) + U[2, i] * W[2, j]
+    return R1, R2, U[2].copy(), sg
+
+
+def split_bound(sigma):
+    return SPLIT_OPS * E * sigma[0] / (sigma[1] - sigma[2])
+
+
+def depths(R, t, a0, a1, b0, b1):
+    """(z0, z1): (t x c) . (a x c) and (t x a) . (a x c) with c = R b, arrays over the matches."""
+    one = np.ones_like(a0)
+    a = (a0, a1, one)
+    c = [(R[j, 0] * b0 + R[j, 1] * b1) + R[j, 2] for j in range(3)]
+    tt = (t[0] * one, t[1] * one, t[2] * one)
+    cr = lambda x, y: (x[1] * y[2] - x[2] * y[1], x[2] * y[0] - x[0] * y[2], x[0] * y[1] - x[1] * y[0])
+    ac, tc, ta = cr(a, c), cr(tt, c), cr(tt, a)
+    return (tc[0] * ac[0] + tc[1] * ac[1]) + tc[2] * ac[2], (ta[0] * ac[0] + ta[1] * ac[1]) + ta[2] * ac[2]
+
+
+def votes(R1, R2, t, pts, defect=None):
+    """The four vote counts of the inliers' normalised points pts = (a0, a1, b0, b1) -> (4) int, and the smallest |z|.
+    defect="one view": only view 0's depth is asked."""
+    out, small = [], np.inf
+    for R in (R1, R2):
+        z0, z1 = depths(R, t, *pts)
+        if len(z0):
+            small = min(small, np.abs(z0).min(), np.abs(z1).min())
+        if defect == "one view":
+            out += [int((z0 > 0).sum()), int((z0 < 0).sum())]
+        else:
+            out += [int(((z0 > 0) & (z1 > 0)).sum()), int(((z0 < 0) & (z1 < 0)).sum())]
+    return np.array(out), small
+
+
+def rel_parts(rel_pose):
+    """(R0, t0 / |t0|, |t0|, usable) of a rel_pose, or of None."""
+    if rel_pose is None:
+        return None, None, 0.0, False
+    P = np.asarray(rel_pose, dtype=np.float32).astype(np.float64)
+    t0 = P[:3, 3]
+    with np.errstate(all="ignore"):
+        len0 = np.sqrt((t0[0] * t0[0] + t0[1] * t0[1]) + t0[2] * t0[2])
+        ok = bool(np.isfinite(P[:3]).all() and len0 > 0.0 and np.isfinite(len0))
+        return P[:3, :3], (t0 / len0 if ok else t0), len0, ok
+
+
+def finish(Em, valid, partial, xy, count, intrinsics, inlier_px, rel_pose=None, defect=None):
+    """The rule of cpn_ransac_finish for one pair -> (pose (4, 4) float64 before the fp32 store, inlier (N) uint8, stats (8),
+    info): info holds the sums per hypothesis, the votes, sigma, the smallest |depth expression| and the candidates.
+    defect="last on ties": the higher index wins a tie; "one view", "one sweep": votes' and split's."""
+    xy = np.asarray(xy, dtype=np.float32)
+    N, Hn = len(xy), len(Em)
+    n = min(max(int(count), 0), N)
+    usable = int(np.isfinite(xy[:n]).all(axis=1).sum())
+    used = -(-n // CHUNK)
+    inlier = np.zeros(N, dtype=np.uint8)
+    nothing = usable < 8 or Hn == 0
+    sums = np.asarray(partial)[:used].sum(axis=0, dtype=np.int64) if Hn + 1 else None
+    ok = np.asarray(valid) != 0
+    info = {"sums": sums}
+    solved = False
+    if not nothing and ok.any():
+        cand = np.where(ok, sums[:Hn], -1)
+        winner = int(len(cand) - 1 - cand[::-1].argmax()) if defect == "last on ties" else int(cand.argmax())
+        R1, R2, t, sigma = split(Em[winner], defect)
+        solved = bool(np.isfinite(R1).all() and np.isfinite(R2).all() and np.isfinite(t).all())
+    if nothing or not solved:
+        pose = np.eye(4) if rel_pose is None else np.asarray(rel_pose, dtype=np.float32).astype(np.float64)
+        stats = np.zeros(8)
+        stats[1] = 0.0 if nothing else usable
+        stats[4] = float(sums[Hn]) if (rel_pose is not None and not nothing) else -1.0
+        stats[7] = 2.0 if nothing else 1.0
+        return pose, inlier, stats, info
+    k0, k1 = mr.cam_of(intrinsics[0]), mr.cam_of(intrinsics[1])
+    inl = inliers(Em[winner][None], xy[:n], intrinsics, inlier_px)[0]
+    inlier[:n] = inl
+    pts = tuple(p[inl] for p in normalised(xy[:n], k0, k1))
+    v, small = votes(R1, R2, t, pts, defect)
+    pick = int(v.argmax())
+    R, sign = (R1, R2)[pick >> 1], (-1.0 if pick & 1 else 1.0)
+    R0, t0, len0, rel_ok = rel_parts(rel_pose)
+    pose = np.eye(4)
+    pose[:3, :3], pose[:3, 3] = R, (len0 if rel_ok else 1.0) * (sign * t)
+    dR = dt = 0.0
+    if rel_ok:
+        for r in range(3):
+            for c in range(3):
+                e = R[r, c] - R0[r, c]
+                dR += e * e
+            e = sign * t[r] - t0[r]
+            dt += e * e
+    stats = np.array([float(sums[winner]), float(usable), float(winner), float(ok.sum()),
+                      float(sums[Hn]) if rel_pose is not None else -1.0,
+                      2.0 * np.arcsin(min(np.sqrt(dR) / 2.8284271247461903, 1.0)) * DEG,
+                      2.0 * np.arcsin(min(np.sqrt(dt) / 2.0, 1.0)) * DEG, 0.0])
+    info.update(votes=v, sigma=sigma, small_depth=small, R1=R1, R2=R2, t=t, pick=pick, winner=winner)
+    return pose, inlier, stats, info
+
+
+def ransac_pose(xy, count, intrinsics, rel_pose=None, hypotheses_n=1024, inlier_px=1.0, seed=0, defect=None):
+    """The three rules in a row for one pair -> (pose, inlier, stats, info); info also holds E, sample, valid and partial."""
+    Em, sample, valid = hypotheses(xy, count, intrinsics, hypotheses_n, seed, defect=defect)
+    partial = score(Em, valid, xy, count, intrinsics, inlier_px, rel_pose, defect=defect)
+    pose, inlier, stats, info = finish(Em, valid, partial, xy, count, intrinsics, inlier_px, rel_pose, defect=defect)
+    info.update(E=Em, sample=sample, valid=valid, partial=partial)
+    return pose, inlier, stats, info
+
+
+def threshold_margin(Em, xy, intrinsics, inlier_px):
+    """The smallest | |r| - inlier_px | over the residuals that count: a decision closer than MARGIN could differ between two
+    float64 evaluations."""
+    r, ok = residuals(Em, xy, intrinsics)
+    d = np.abs(np.abs(r) - inlier_px)
+    return float(d[ok].min()) if ok.any() else np.inf
+
+
+# ------------------------------------------------------------------------------------------------------------- the scenes
+def stalled_start(scene, deg=30.0):
+    """rel_pose `deg` off the scene's truth: rodrigues((1, -0.5, 0.7), deg) @ R_true and t turned deg about t_true x z."""
+    pose = np.eye(4)
+    pose[:3, :3] = mr.rodrigues((1.0, -0.5, 0.7), deg) @ scene["R_true"]
+    pose[:3, 3] = mr.rodrigues(np.cross(scene["t_true"], (0.0, 0.0, 1.0)), deg) @ scene["t_true"]
+    return pose.astype(np.float32)
+
+
+def true_pose(scene):
+    pose = np.eye(4)
+    pose[:3, :3], pose[:3, 3] = scene["R_true"], scene["t_true"]
+    return pose.astype(np.float32)
+
+
+NOISY = dict(n=1000, seed=16, noise_px=0.5, outliers=0.3)          # the scene of the recovery case
+EXACT = dict(n=1000, seed=16, noise_px=0.0, outliers=0.0)          # the tie fixture: every good hypothesis reaches n
+
+
+@functools.lru_cache(maxsize=None)
+def hypotheses_case():
+    """B = 6 pairs of N = 64 rows of the noisy scene: counts 64, 9 (redraws), 5 (below 8), 100 (beyond N), -3, and 64 with a NaN
+    row inside the count.  -> (xy (6, 64, 4) fp32, counts (6) int32, intrinsics (6, 2, 4, 4) fp32).  Shared, never written to."""
+    sc = mr.refine_scene(**NOISY)
+    xy = np.stack([sc["xy"][64 * b:64 * b + 64] for b in (0, 1, 2, 0, 3, 0)]).copy()
+    xy[5, NAN_ROW, 2] = np.nan
+    return xy, np.asarray((64, 9, 5, 100, -3, 64), dtype=np.int32), np.stack([sc["intrinsics"]] * 6)
+
+
+NAN_ROW = 17
+
+
+@functools.lru_cache(maxsize=None)
+def score_case(Hn=65):
+    """B = 3 pairs of N = CHUNK + 1 rows, counts (CHUNK + 1, 0, 7): the second chunk holds one row.  E and valid are the
+    restatement's own hypotheses of pair 0 for every pair, hypothesis 3 switched off; rel_pose is the stalled start.
+    -> (xy, counts, intrinsics, rel_pose (3, 4, 4), E (3, Hn, 9), valid (3, Hn))."""
+    sc = mr.refine_scene(**NOISY)
+    N = CHUNK + 1
+    xy = np.stack([sc["xy"][:N]] * 3).copy()
+    Em, _, valid = hypotheses(xy[0], N, sc["intrinsics"], Hn, 0)
+    valid = valid.copy()
+    valid[3] = 0
+    return (xy, np.asarray((N, 0, 7), dtype=np.int32), np.stack([sc["intrinsics"]] * 3), np.stack([stalled_start(sc)] * 3),
+            np.stack([Em] * 3), np.stack([valid] * 3))
+
+
+@functools.lru_cache(maxsize=None)
+def finish_case(Hn=65):
+    """B = 4 pairs of N = 1000 rows: the noisy scene, the tie fixture, the noisy scene with every hypothesis invalid (status
+    1) and the noisy scene with count 7 (status 2).  -> (xy, counts, intrinsics, rel_pose, E, valid, partial
+    (4, chunks, Hn + 1) int32), E, valid and partial the restatement's."""
+    noisy, exact = mr.refine_scene(**NOISY), mr.refine_scene(**EXACT)
+    xy = np.stack((noisy["xy"], exact["xy"], noisy["xy"], noisy["xy"]))
+    counts = np.asarray((1000, 1000, 1000, 7), dtype=np.int32)
+    K = np.stack([noisy["intrinsics"]] * 4)
+    P = np.stack([stalled_start(noisy)] * 4)
+    Es, vs, ps = [], [], []
+    for b in range(4):
+        Em, _, valid = hypotheses(xy[b], counts[b], K[b], Hn, 0)
+        if b == 2:
+            valid = np.zeros_like(valid)
+        Es.append(Em)
+        vs.append(valid)
+        ps.append(score(Em, valid, xy[b], counts[b], K[b], 1.0, P[b]))
+    return xy, counts, K, P, np.stack(Es), np.stack(vs), np.stack(ps)
+
+
+@functools.lru_cache(maxsize=None)
+def recovery_case(hypotheses_n=1024, seed=0):
+    """The result that justifies the feature: the noisy scene with rel_pose 30 degrees off -> (scene, rel_pose, the
+    restatement's (pose, inlier, stats, info))."""
+    sc = mr.refine_scene(**NOISY)
+    start = stalled_start(sc)
+    return sc, start, ransac_pose(sc["xy"], 1000, sc["intrinsics"], start, hypotheses_n, 1.0, seed)
+
+
+@functools.lru_cache(maxsize=None)
+def flow_scene(S=32):
+    """Two exact flows (1, 2, S, S) fp32 of a pair of cameras looking at two smooth surfaces that are no planes, one per
+    direction (they need not agree: the tests keep every match inside the image, whatever its cycle error) -> (f0, f1,
+    intrinsics (1, 2, 4, 4), the true pose (4, 4) fp32, a pose 30 degrees off (4, 4) fp32)."""
+    f = 0.9 * S
+    R, t = mr.rodrigues((0.3, 1.0, -0.2), 6.0), np.array([0.30, 0.04, 0.10])
+    y, x = np.mgrid[0:S, 0:S].astype(np.float64)
+    ray = np.stack(((x - S / 2.0) / f, (y - S / 2.0) / f, np.ones_like(x)), -1)
+    z0 = 3.0 + np.sin(x / 5.0) + 0.8 * np.cos(y / 4.0) + 0.05 * x
+    z1 = 3.5 + 0.9 * np.cos(x / 6.0 + 1.0) + np.sin(y / 3.0) - 0.04 * y
+    X1 = (ray * z0[..., None] - t) @ R                              # view 0's pixels seen from view 1: R^T (X0 - t)
+    X0 = (ray * z1[..., None]) @ R.T + t                            # view 1's pixels seen from view 0: R X1 + t
+    flows = []
+    for X in (X1, X0):
+        q = f * X[..., :2] / X[..., 2:] + S / 2.0
+        flows.append(np.stack((q[..., 0] - x, q[..., 1] - y))[None].astype(np.float32))
+    K = mr.pinhole(f, S)
+    scene = {"R_true": R, "t_true": t}
+    return flows[0], flows[1], np.stack((K, K))[None], true_pose(scene)[None], stalled_start(scene)[None]
