@@ -10,7 +10,8 @@ novel_views.hip for the one-rounding-per-operation sums of its resample and its 
 operation sequence of its fundamental matrices and line end points; point_cloud.hip for that of its points and votes; matches.hip
 for the flow warp's fp32 sequence and the float64 sequence of its residuals, Jacobians and sums; splat.hip for the float64
 sequence of its projection; ransac.hip for that of its 8-point systems, its residuals (sampson.h, shared with matches.hip) and
-its split of the essential matrix; mesh.hip for that of its signed distances and vertices; raster.hip for that of its projection,
+its split of the essential matrix; ransac5.hip for that of its 5-point solver, which tests/ransac5_ref.py follows bit for bit
+(both take their sampler from ransac_draw.h); mesh.hip for that of its signed distances and vertices; raster.hip for that of its projection,
 depths and colours.  The last five share pinhole.h (the float64 camera; its bodies also switch contraction off by pragma) and
 splat and raster zbuffer.h (the key, its atomic minimum, the resolve stores, the clear and the image checks).
 """
@@ -61,6 +62,7 @@ UNITS = [
     ("point_cloud.hip", ["-ffp-contract=off"]),            # one rounding per float64 operation of the points and the votes
     ("matches.hip", ["-ffp-contract=off"]),                # flow_warp.h's fp32 sequence; float64 residuals, Jacobians and sums
     ("ransac.hip", ["-ffp-contract=off"]),                 # the float64 sequence of its systems, residuals and pose split
+    ("ransac5.hip", ["-ffp-contract=off"]),                # the float64 sequence of the 5-point solver, bit for bit
     ("splat.hip", ["-ffp-contract=off"]),                  # one rounding per float64 operation of the projection
     ("mesh.hip", ["-ffp-contract=off"]),                   # one rounding per float64 operation of the TSDF and the vertices
     ("raster.hip", ["-ffp-contract=off"]),                 # one rounding per float64 operation of the projection and the depth

@@ -6,8 +6,10 @@
 //                             the column permutation live in LDS, one column per lane ([entry][lane]: a lane's accesses never
 //                             meet another lane's bank), so that the pivot's runtime indices never touch a private array.
 //   ransac_score_kernel       cpn_ransac_score: grid (tiles of 256 hypotheses, chunks of CPN_RANSAC_CHUNK matches, pairs).  The
-//                             workgroup normalises its chunk into LDS once; each lane then holds one E in registers and walks
-//                             the chunk - every lane reads the same LDS address, a broadcast - and counts in a register.
+//                             workgroup normalises its chunk into LDS once and packs the tile's valid slots to its first
+//                             lanes (a ballot and four counts: invalid slots, most of the 5-point solver's, write their 0 and
+//                             cost no wave); each lane then holds one E in registers and walks the chunk - every lane reads
+//                             the same LDS address, a broadcast - and counts in a register.
 //   ransac_finish_kernel      cpn_ransac_finish: one workgroup per pair sums the partial counts, picks the winner, thread 0
 //                             splits its E by a one-sided Jacobi SVD, all threads mark the inliers and vote on the four poses.
 //
@@ -15,6 +17,7 @@
 // (-ffp-contract=off): no atomics, integer sums only, the same bytes every run.  The residual is sampson.h's.
 #include "common.h"
 #include "pinhole.h"
+#include "ransac_draw.h"
 #include "sampson.h"
 
 #include "../../include/coponerf_hip.h"
@@ -26,18 +29,10 @@ namespace {
 constexpr int NT = 256;
 constexpr int HT = 64;                                     // hypotheses: threads per workgroup
 constexpr int CH = CPN_RANSAC_CHUNK;
-constexpr int DRAWS = 64;
 constexpr int SWEEPS = 8;
 constexpr double RANK_TOL = 1e-9;
-constexpr unsigned long long GOLDEN = 0x9E3779B97F4A7C15ull;
-
-__device__ __forceinline__ unsigned long long mix64(unsigned long long z) {      // splitmix64's finaliser
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
-__device__ __forceinline__ int clamp_count(int c, int N) { return c < 0 ? 0 : (c > N ? N : c); }
-__device__ __forceinline__ bool finite32(float v) { return fabsf(v) <= 3.402823466e38f; }               // false for NaN
+using ransac_draw::clamp_count;
+using ransac_draw::finite32;
 
 __global__ __launch_bounds__(HT) void ransac_hypotheses_kernel(const float* __restrict__ xy, const int* __restrict__ count,
                                                                const float* __restrict__ intrinsics, int N, int Hn,
@@ -53,23 +48,7 @@ __global__ __launch_bounds__(HT) void ransac_hypotheses_kernel(const float* __re
 
     // ---- the draw
     int s[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) s[j] = -1;
-    int got = 0;
-    const unsigned long long key = mix64(seed + GOLDEN * (unsigned long long)(h + 1));
-    for (int d = 0; d < DRAWS && got < 8; ++d) {
-        const unsigned long long u = mix64(key + GOLDEN * (unsigned long long)(d + 1));
-        const int idx = (int)(((u >> 32) * (unsigned long long)n) >> 32);
-        bool dup = false;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) dup = dup || s[j] == idx;
-        if (!dup && n > 0) {
-#pragma unroll
-            for (int j = 0; j < 8; ++j)
-                if (j == got) s[j] = idx;
-            ++got;
-        }
-    }
+    const int got = ransac_draw::draw_rows<8>(seed, h, n, s);
 #pragma unroll
     for (int j = 0; j < 8; ++j) sample[at * 8 + j] = s[j];
 
@@ -180,9 +159,16 @@ __global__ __launch_bounds__(NT) void ransac_score_kernel(const double* __restri
                                                           const float* __restrict__ intrinsics, const float* __restrict__ rel_pose,
                                                           int N, int Hn, double inlier_px, int* __restrict__ partial) {
     __shared__ double pts[CH][4];
+    __shared__ int packed[NT], packed_n[NT / 64];
     const int tid = threadIdx.x, chunk = blockIdx.y, b = blockIdx.z;
     const int n = clamp_count(count[b], N), start = chunk * CH;
     const int m = n - start < CH ? n - start : CH;         // the rows of this chunk below the count (<= 0: none)
+    const int slot = blockIdx.x * NT + tid;
+    int* const out = partial + ((size_t)b * gridDim.y + chunk) * (Hn + 1);
+    if (m <= 0) {                                          // the whole workgroup: its zeros, and nothing else
+        if (slot <= Hn) out[slot] = 0;
+        return;
+    }
     const Cam k0 = load_cam(intrinsics + ((size_t)b * 2 + 0) * 16), k1 = load_cam(intrinsics + ((size_t)b * 2 + 1) * 16);
     for (int i = tid; i < m; i += NT) {
         const float* const row = xy + ((size_t)b * N + start + i) * 4;
@@ -191,32 +177,38 @@ __global__ __launch_bounds__(NT) void ransac_score_kernel(const double* __restri
         pts[i][2] = ((double)row[2] - k1.cx) / k1.fx;
         pts[i][3] = ((double)row[3] - k1.cy) / k1.fy;
     }
+    // the slots of this tile that have something to count, packed in slot order: the 5-point solver leaves more than half of
+    // its 10 slots per sample invalid, scattered among the valid ones, and a wave is busy while one of its lanes is
+    bool on = slot <= Hn;
+    if (slot < Hn) on = on && valid[(size_t)b * Hn + slot] != 0;
+    if (slot == Hn) on = on && rel_pose != nullptr;        // the extra slot: rel_pose's own E, where there is one
+    if (slot <= Hn && !on) out[slot] = 0;
+    const unsigned long long wave_on = __ballot(on);
+    const int lane = tid & 63, wave = tid >> 6;
+    if (lane == 0) packed_n[wave] = __popcll(wave_on);
+    __syncthreads();                                       // pts and packed_n are written
+    int first = 0;
+    for (int w = 0; w < wave; ++w) first += packed_n[w];
+    if (on) packed[first + __popcll(wave_on & ((1ull << lane) - 1ull))] = slot;
     __syncthreads();
-    const int slot = blockIdx.x * NT + tid;
-    if (slot > Hn) return;
+    if (tid >= (packed_n[0] + packed_n[1]) + (packed_n[2] + packed_n[3])) return;
+    const int mine = packed[tid];
     double e[9];
-    bool on = m > 0;
-    if (slot < Hn) {
-        const size_t at = (size_t)b * Hn + slot;
-        on = on && valid[at] != 0;
+    if (mine < Hn) {
+        const size_t at = (size_t)b * Hn + mine;
 #pragma unroll
-        for (int c = 0; c < 9; ++c) e[c] = on ? E[at * 9 + c] : 0.0;
-    } else {                                               // the extra slot: rel_pose's own E, where there is one
-        on = on && rel_pose != nullptr;
-        if (on) {
-            const Pose rel = load_pose(rel_pose + (size_t)b * 16);
-            essential(&rel.R[0][0], rel.t, e);
-        }
+        for (int c = 0; c < 9; ++c) e[c] = E[at * 9 + c];
+    } else {
+        const Pose rel = load_pose(rel_pose + (size_t)b * 16);
+        essential(&rel.R[0][0], rel.t, e);
     }
     int cnt = 0;
-    if (on) {
-        for (int i = 0; i < m; ++i) {
-            const Sampson s = sampson_normalised(e, k0, k1, pts[i][0], pts[i][1], pts[i][2], pts[i][3]);
-            const double r = s.n / sqrt(s.D);
-            if (residual_ok(s, r) && fabs(r) <= inlier_px) ++cnt;
-        }
+    for (int i = 0; i < m; ++i) {
+        const Sampson s = sampson_normalised(e, k0, k1, pts[i][0], pts[i][1], pts[i][2], pts[i][3]);
+        const double r = s.n / sqrt(s.D);
+        if (residual_ok(s, r) && fabs(r) <= inlier_px) ++cnt;
     }
-    partial[((size_t)b * gridDim.y + chunk) * (Hn + 1) + slot] = cnt;
+    out[mine] = cnt;
 }
 
 // ---- finish

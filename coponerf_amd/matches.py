@@ -10,7 +10,8 @@ round.  The reference uses them for the cycle loss and a warped panel only.  Her
   Matches       xy (x0, y0, x1, y1) / err (cycle, epi) / count on the device; numpy(b) is the one host read
   refine_pose   robust Gauss-Newton of the relative pose on the Sampson residuals of the matches: cpn_refine_pose, one launch
   ransac_pose   the relative pose from the matches ALONE: 8-point RANSAC, cpn_ransac_hypotheses / _score / _finish, three
-                launches; with it the inlier count of rel_pose under the same rule and an inlier mask
+                launches; with it the inlier count of rel_pose under the same rule and an inlier mask; solver="5pt" takes
+                minimal samples instead (cpn_ransac_hypotheses5, up to 10 solutions each)
   from_pair     get_z once, then the three above (and ransac_pose with ransac={...})
   photo_coords  host: matches of a prepare_pair dict in the coordinates of the original photos
 
@@ -24,6 +25,9 @@ refine_pose is a local method: from a rel_pose 30 degrees off it does not move. 
 look at rel_pose to find its pose, so the pose head cannot spoil it; `ransac={..., "start": "ransac" | "best"}` lets from_flows
 and from_pair refine from it.  Its sampler, solver, threshold and hypothesis count are this package's definitions as well and
 are as untried on a trained checkpoint; the linear 8-point solver is degenerate for a planar scene and for a pure rotation.
+solver="5pt" (round 21 of the header) is not degenerate on a plane - a wall, a floor -, where the 8-point solver returns a wrong
+pose with as many inliers as the true one; a purely planar scene keeps a two-fold ambiguity that only the vote on the depths
+breaks, and a pure rotation gives E = 0 for either solver.
 """
 from __future__ import annotations
 
@@ -196,7 +200,7 @@ def refine_pose(matches: Matches, intrinsics: torch.Tensor, rel_pose: torch.Tens
 
 @torch.no_grad()
 def ransac_pose(matches: Matches, intrinsics: torch.Tensor, rel_pose: Optional[torch.Tensor] = None, hypotheses: int = 1024,
-                inlier_px: float = 1.0, seed: int = 0) -> Dict[str, torch.Tensor]:
+                inlier_px: float = 1.0, seed: int = 0, solver: str = "8pt") -> Dict[str, torch.Tensor]:
     """cpn_ransac_hypotheses, cpn_ransac_score, cpn_ransac_finish: `hypotheses` linear 8-point solutions from samples drawn by
     a counter hash of (seed, hypothesis, draw) - the same for every pair -, each scored by its matches within inlier_px of
     Sampson residual, the best split into the pose that puts its inliers in front of both cameras.  float64 inside, three
@@ -205,7 +209,17 @@ def ransac_pose(matches: Matches, intrinsics: torch.Tensor, rel_pose: Optional[t
     float64: the winner's inliers, the usable matches, the winner's index, the valid hypotheses, the inliers of rel_pose under
     the same rule (-1 without one), the angles in degrees between the pose and rel_pose (rotation, translation direction), the
     status (0 ok, 1 no valid hypothesis, 2 nothing to do: fewer than 8 usable matches or hypotheses == 0 - pose is rel_pose,
-    or the identity without one).  rel_pose is only measured against, never searched from."""
+    or the identity without one).  rel_pose is only measured against, never searched from.
+    solver="5pt" (cpn_ransac_hypotheses5, round 21 of the header) draws `hypotheses` samples of 5 matches - the first 5 of the
+    8-point sample of the same index - and solves each for up to 10 essential matrices, the real roots of a degree-10
+    polynomial: the hypothesis buffers hold 10 slots per sample, slot 10 h + r is root r of sample h, stats[2] is the winning
+    SLOT (its sample is stats[2] // 10) and stats[3] the number of valid slots.  Unlike the 8-point solver it is not degenerate
+    where the matches lie on one plane (a wall, a floor); a purely planar scene keeps a two-fold ambiguity that only the vote
+    on the depths breaks, and a pure rotation gives E = 0 for either solver.  Status 2 stays "fewer than 8 usable matches".
+    Three launches as well, with 10 times the slots to score."""
+    if solver not in _SOLVERS:
+        raise ValueError(f"ransac_pose: solver must be one of {_SOLVERS}, got {solver!r}")
+    per = 10 if solver == "5pt" else 1                              # hypothesis slots per sample
     xy, count = matches.xy, matches.count
     named = [("matches.xy", xy, torch.float32, None), ("intrinsics", intrinsics, torch.float32, None)]
     if rel_pose is not None:
@@ -218,18 +232,20 @@ def ransac_pose(matches: Matches, intrinsics: torch.Tensor, rel_pose: Optional[t
         raise ValueError(f"ransac_pose: rel_pose must be (B, 4, 4) with B = {B}, got {tuple(rel_pose.shape)}")
     Hn, px, seed = int(hypotheses), float(inlier_px), int(seed)
     chunks = -(-N // _hip.CONSTANTS["RANSAC_CHUNK"])
-    if not 0 <= Hn <= 2 ** 20 or not 1 <= B <= 32767 or N > 2 ** 24 or B * chunks * (Hn + 1) >= 2 ** 31:
-        raise ValueError(f"ransac_pose: need 0 <= hypotheses <= 2^20, 1 <= B <= 32767, N <= 2^24 and B ceil(N / "
-                         f"{_hip.CONSTANTS['RANSAC_CHUNK']}) (hypotheses + 1) < 2^31, got hypotheses = {hypotheses}, B = {B}, N = {N}")
+    slots = per * Hn
+    if not 0 <= slots <= 2 ** 20 or not 1 <= B <= 32767 or N > 2 ** 24 or B * chunks * (slots + 1) >= 2 ** 31:
+        what = "hypotheses" if per == 1 else f"{per} hypotheses"
+        raise ValueError(f"ransac_pose: need 0 <= {what} <= 2^20, 1 <= B <= 32767, N <= 2^24 and B ceil(N / "
+                         f"{_hip.CONSTANTS['RANSAC_CHUNK']}) ({what} + 1) < 2^31, got hypotheses = {hypotheses}, B = {B}, N = {N}")
     if not 0.0 <= px < float("inf"):
         raise ValueError(f"ransac_pose: need a finite inlier_px >= 0, got {inlier_px}")
     if not -2 ** 63 <= seed < 2 ** 63:
         raise ValueError(f"ransac_pose: seed must fit 64 bits, got {seed}")
     dev = xy.device
-    E = torch.empty(B, max(Hn, 1), 9, dtype=torch.float64, device=dev)
-    sample = torch.empty(B, max(Hn, 1), 8, dtype=torch.int32, device=dev)
-    valid = torch.empty(B, max(Hn, 1), dtype=torch.uint8, device=dev)
-    partial = torch.empty(B, chunks, Hn + 1, dtype=torch.int32, device=dev)
+    E = torch.empty(B, max(slots, 1), 9, dtype=torch.float64, device=dev)
+    sample = torch.empty(B, max(Hn, 1), 5 if per == 10 else 8, dtype=torch.int32, device=dev)
+    valid = torch.empty(B, max(slots, 1), dtype=torch.uint8, device=dev)
+    partial = torch.empty(B, chunks, slots + 1, dtype=torch.int32, device=dev)
     pose = torch.empty(B, 4, 4, dtype=torch.float32, device=dev)
     inlier = torch.empty(B, N, dtype=torch.uint8, device=dev)
     stats = torch.empty(B, 8, dtype=torch.float64, device=dev)
@@ -237,16 +253,17 @@ def ransac_pose(matches: Matches, intrinsics: torch.Tensor, rel_pose: Optional[t
     with torch.cuda.device(dev):
         s = _hip.stream_handle()
         if Hn:
-            _hip.call("cpn_ransac_hypotheses", xy.data_ptr(), count.data_ptr(), intrinsics.data_ptr(), B, N, Hn, seed, E.data_ptr(),
-                      sample.data_ptr(), valid.data_ptr(), s)
+            _hip.call("cpn_ransac_hypotheses5" if per == 10 else "cpn_ransac_hypotheses", xy.data_ptr(), count.data_ptr(),
+                      intrinsics.data_ptr(), B, N, Hn, seed, E.data_ptr(), sample.data_ptr(), valid.data_ptr(), s)
         _hip.call("cpn_ransac_score", E.data_ptr(), valid.data_ptr(), xy.data_ptr(), count.data_ptr(), intrinsics.data_ptr(), rel, B, N,
-                  Hn, px, partial.data_ptr(), s)
+                  slots, px, partial.data_ptr(), s)
         _hip.call("cpn_ransac_finish", E.data_ptr(), valid.data_ptr(), partial.data_ptr(), xy.data_ptr(), count.data_ptr(),
-                  intrinsics.data_ptr(), rel, B, N, Hn, px, pose.data_ptr(), inlier.data_ptr(), stats.data_ptr(), s)
+                  intrinsics.data_ptr(), rel, B, N, slots, px, pose.data_ptr(), inlier.data_ptr(), stats.data_ptr(), s)
     return {"pose": pose, "inlier": inlier, "stats": stats}
 
 
 _STARTS = ("network", "ransac", "best")
+_SOLVERS = ("8pt", "5pt")
 
 
 def _ransac_keywords(who: str, ransac: Dict) -> Tuple[Dict, str]:
@@ -256,9 +273,11 @@ def _ransac_keywords(who: str, ransac: Dict) -> Tuple[Dict, str]:
     start = kw.pop("start", "network")
     if start not in _STARTS:
         raise ValueError(f"{who}: ransac['start'] must be one of {_STARTS}, got {start!r}")
-    unknown = set(kw) - {"hypotheses", "inlier_px", "seed"}
+    unknown = set(kw) - {"hypotheses", "inlier_px", "seed", "solver"}
     if unknown:
         raise ValueError(f"{who}: ransac holds unknown keywords {sorted(unknown)}")
+    if kw.get("solver", "8pt") not in _SOLVERS:
+        raise ValueError(f"{who}: ransac['solver'] must be one of {_SOLVERS}, got {kw['solver']!r}")
     return kw, start
 
 
@@ -267,7 +286,7 @@ def from_flows(flow: Sequence[torch.Tensor], intrinsics: torch.Tensor, rel_pose:
                max_cycle_px: float = 10.0, max_epi_px: Optional[float] = None, stride: int = 4, iters: int = 10,
                scale_px: float = 2.0, ransac: Optional[Dict] = None) -> Dict:
     """from_pair's second half, for flows and a pose that get_z has already returned: four launches and the mask between them,
-    no host read.  ransac: None, or a dict of ransac_pose's keywords (hypotheses, inlier_px, seed) and `start`: three more
+    no host read.  ransac: None, or a dict of ransac_pose's keywords (hypotheses, inlier_px, seed, solver) and `start`: three more
     launches, and the result gains the key `ransac` (ransac_pose's dict).  start="network" (the default) refines from rel_pose
     as without it, "ransac" from RANSAC's pose, "best" per pair from the one with more inliers under ransac_pose's rule (a tie
     and a status other than 0 go to rel_pose; chosen by torch.where on the device)."""

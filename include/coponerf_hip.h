@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define CPN_ABI_VERSION 12   /* cpn_attend_units (round 7), cpn_ssim_warp* (round 8), cpn_image_metrics* (round 9), summaries.hip (round 10), lpips.hip (round 11), novel_views.hip (round 12), epipolar.hip (round 13), cpn_lpips_*_bwd (round 14), point_cloud.hip (round 15), matches.hip (round 16), splat.hip (round 17), mesh.hip (round 18), raster.hip (round 19) and ransac.hip (round 20) are additive - symbols added, none altered: the version stays */
+#define CPN_ABI_VERSION 12   /* cpn_attend_units (round 7), cpn_ssim_warp* (round 8), cpn_image_metrics* (round 9), summaries.hip (round 10), lpips.hip (round 11), novel_views.hip (round 12), epipolar.hip (round 13), cpn_lpips_*_bwd (round 14), point_cloud.hip (round 15), matches.hip (round 16), splat.hip (round 17), mesh.hip (round 18), raster.hip (round 19), ransac.hip (round 20) and ransac5.hip (round 21) are additive - symbols added, none altered: the version stays */
 
 #define CPN_E_ARG   (-1)   /* bad argument (null pointer, size, alignment) */
 #define CPN_E_SHAPE (-2)   /* shape not supported by the compiled tiles    */
@@ -1083,7 +1083,7 @@ int cpn_raster_resolve(const unsigned long long* zbuf, const float* xyz, const u
  * inlier count of rel_pose under the same rule, and an inlier mask.  The symbols are additive: the ABI version stays.  The
  * sampler, the solver, the threshold, the scoring and the choice among the four poses are THIS LIBRARY'S definitions.  There is
  * no local optimisation inside the loop (cpn_refine_pose afterwards is that step), no adaptive stopping, no MSAC / MAGSAC
- * scoring and no 5-point solver; the linear 8-point solver is degenerate for a planar scene and for a pure rotation.
+ * scoring; the linear 8-point solver is degenerate for a planar scene and for a pure rotation (round 21 adds the 5-point solver).
  * Conventions: round 16's.  xy (B, N, 4) fp32 = (x0, y0, x1, y1) with count (B) int32 on the device, n = min(max(count, 0), N);
  *   rows at and beyond n are never read.  a = ((x0 - cx0) / fx0, (y0 - cy0) / fy0, 1), b likewise of view 1, float64 from the
  *   fp32 inputs.  X0 = R X1 + t, E = [t]x R, a^T E b = 0; E (.., 9) float64 row-major.  One rounding per operation, sums left to
@@ -1142,6 +1142,61 @@ int cpn_ransac_score(const double* E, const uint8_t* valid, const float* xy, con
 int cpn_ransac_finish(const double* E, const uint8_t* valid, const int* partial, const float* xy, const int* count,
                       const float* intrinsics, const float* rel_pose, int B, int N, int Hn, double inlier_px, float* pose,
                       uint8_t* inlier, double* stats, void* stream);
+
+/* ==== the 5-point solver for round 20's RANSAC: minimal samples (round 21) ================================================
+ * The linear 8-point solver is degenerate where the matches lie on one plane; the 5-point solver is not.  One additive symbol:
+ * the ABI version stays.  It fills the hypothesis buffers that cpn_ransac_score and cpn_ransac_finish take, with 10 SLOTS per
+ * sample: call those two unchanged with Hn' = 10 Hn, E (B, 10 Hn, 9) and valid (B, 10 Hn); slot 10 h + r is root r of sample h,
+ * stats [2] is then the winning slot (its sample is stats [2] / 10 rounded down) and stats [3] the number of valid slots.
+ * Status 2 of cpn_ransac_finish stays "usable < 8" for both solvers.  Conventions, the draw, the system's rows and the norm and
+ * sign of E: round 20's.  1 <= B <= 32767, 1 <= N <= 2^24, 1 <= 10 Hn <= 2^20 and B ceil(N / CPN_RANSAC_CHUNK) (10 Hn + 1) <
+ * 2^31 (CPN_E_SHAPE otherwise).  A planar scene has a two-fold ambiguity that only the depth vote of cpn_ransac_finish breaks;
+ * a pure rotation gives E = 0 for any solver.  THIS LIBRARY'S definitions, all float64, one rounding per operation, only
+ * + - * / sqrt and comparisons, every trip count fixed:
+ * cpn_ransac_hypotheses5: ONE launch, one thread per (pair, sample index h).
+ *   The draw is round 20's stopped at 5 distinct rows: for equal (seed, h, n) they are the first 5 of cpn_ransac_hypotheses'
+ *   8.  The sample is invalid after 64 draws without 5 distinct indices (always so for n < 5) and where one of the four values
+ *   of a sampled row is not finite.  sample (B, Hn, 5) int32: the indices in the order drawn, -1 where none was.
+ *   The null space: the 5 x 9 system of round 20's rows, round 20's elimination with complete pivoting for steps k = 0 .. 4
+ *   (rows k .. 4, columns k .. 8) with its RANK TEST |p_k| > 1e-9 |p_0|.  For v = 0 .. 3 the unknown of permuted column 5 + v
+ *   is 1, the other three of columns 5 .. 8 are 0, and x_r = -((A_r,r+1 x_r+1 + A_r,r+2 x_r+2) + .. + A_r8 x_8) / A_rr for
+ *   r = 4 .. 0; with the exchanges of columns undone these are X, Y, Z, W (v = 0, 1, 2, 3).  E = x X + y Y + z Z + W.
+ *   Polynomials: a linear form is its 4 coefficients of (x, y, z, 1) = variables 0 .. 3; a quadratic its 10 coefficients of the
+ *   pairs i <= j, a cubic its 20 of the triples.  lin * lin: every coefficient starts at 0 and takes + a_i b_j for i = 0 .. 3
+ *   (outer), j = 0 .. 3 (inner) at the pair {i, j}.  quad * lin: from 0, + a_m b_k for m = the pairs in lexicographic order
+ *   (00, 01, 02, 03, 11, 12, 13, 22, 23, 33; outer), k = 0 .. 3 (inner) at the triple.  Sums of polynomials are coefficient-wise.
+ *   The constraints, a 10 x 20 matrix M with the columns
+ *     x^3 y^3 x^2y xy^2 x^2z x^2 y^2z y^2 xyz xy | xz^2 xz x yz^2 yz y z^3 z^2 z 1:
+ *   row 0 is det E = (q0 E_0 - q1 E_1) + q2 E_2 with q0 = E_4 E_8 - E_5 E_7, q1 = E_3 E_8 - E_5 E_6, q2 = E_3 E_7 - E_4 E_6
+ *   (entries of E row-major); with G_ij = (E_3i E_3j + E_3i+1 E_3j+1) + E_3i+2 E_3j+2 (i <= j, G symmetric),
+ *   half = 0.5 ((G_00 + G_11) + G_22) and L = G with half subtracted from its three diagonal entries, row 1 + 3 i + j is entry
+ *   (i, j) of E E^T E - tr(E E^T) E / 2: (L_i0 E_j + L_i1 E_3+j) + L_i2 E_6+j.
+ *   Gauss-Jordan elimination, step k = 0 .. 9: the pivot is the entry of the largest magnitude of column k in rows k .. 9, the
+ *   first on ties; its row is exchanged with row k; RANK TEST: the sample is invalid unless p_k is finite and
+ *   |p_k| > 1e-10 |p_0|; row k is divided by p_k on the columns beyond k; then every row r > k, and every row r with
+ *   4 <= r < k, becomes row_r - M_rk row_k on the columns beyond k (rows 0 .. 3 are never read again and are not reduced
+ *   upwards).  Rows 4 .. 9 then state x^2z, x^2, y^2z, y^2, xyz, xy by the last ten columns.
+ *   B(z): for i = 0, 1, 2 with a = row 4 + 2 i, b = row 5 + 2 i, a - z b = x B_i0(z) + y B_i1(z) + B_i2(z), ascending in z:
+ *   B_i0 = (a_12, a_11 - b_12, a_10 - b_11, -b_10), B_i1 = (a_15, a_14 - b_15, a_13 - b_14, -b_13),
+ *   B_i2 = (a_19, a_18 - b_19, a_17 - b_18, a_16 - b_17, -b_16).  A product of polynomials in z: from 0, + a_i b_j at i + j, i
+ *   outer, j inner.  p1 = B_01 B_12 - B_11 B_02, p2 = B_10 B_02 - B_00 B_12, p3 = B_00 B_11 - B_10 B_01 (the factors in this
+ *   order), f = (p1 B_20 + p2 B_21) + p3 B_22, of degree 10.
+ *   The Sturm chain: f_0 = f / |f's coefficient 10|; f_1 = f_0' (coefficient k - 1 is k f_0,k); for i = 1 .. 9, with n the
+ *   degree of f_(i-1): r = f_(i-1); q = r_n / g with g the leading coefficient of f_i, r_(k+1) -= q f_i,k for k = 0 .. n - 2;
+ *   q = r_(n-1) / g, r_k -= q f_i,k for k = 0 .. n - 2; f_(i+1),k = -(r_k / |r_(n-2)|) for k = 0 .. n - 2.  The sample is
+ *   invalid where |f's coefficient 10| or an |r_(n-2)| is 0 or not finite.  A polynomial's value is Horner's: v = c_d, then
+ *   v = v z + c_k for k = d - 1 .. 0.  V(z) is the number of sign changes of f_0(z) .. f_10(z), zeros skipped; V(-inf) and
+ *   V(+inf) are those of the leading coefficients, negated for odd i at -inf.  The number of real roots is
+ *   min(max(V(-inf) - V(+inf), 0), 10).
+ *   The roots: the real line is z(t) = t / (1 - |t|) for t in (-1, 1).  Root r = 0, 1, .. is found by 40 halvings from
+ *   (lo, hi) = (-1, 1): mid = (lo + hi) 0.5; hi = mid where V(-inf) - V(z(mid)) >= r + 1, otherwise lo = mid.  Then
+ *   z = z((lo + hi) 0.5) and 4 Newton steps z' = z - f_0(z) / f_1(z), each taken only where z(lo) <= z' <= z(hi).
+ *   x = p1(z) / p3(z), y = p2(z) / p3(z), E = ((x X + y Y) + z Z) + W entry by entry, normalised and signed as in round 20.
+ *   Slot r of the sample is valid iff the sample is valid, r is below the number of real roots and all nine values of E are
+ *   finite; the roots ascend with r.  E (B, Hn, 10, 9) float64, all 0 where invalid; valid (B, Hn, 10) bytes 0 / 1.  Every
+ *   element of the three outputs is written.  No atomics: bit-reproducible, and a pair's result does not depend on the batch. */
+int cpn_ransac_hypotheses5(const float* xy, const int* count, const float* intrinsics, int B, int N, int Hn, long long seed,
+                           double* E, int* sample, uint8_t* valid, void* stream);
 
 #ifdef __cplusplus
 }

@@ -16,9 +16,15 @@ refine_pose still converges from it: what it does with outliers is tests/test_ra
   (c) what came out: inliers of the winner against rel_pose's, degrees from the truth before and after refine_pose, and the
       winner's count of the stock form.
 
+  (d) the 5-point solver (csrc/ransac5.hip) in the same process, written to --out5: cpn_ransac_hypotheses5 on
+      its own; cpn_ransac_score and cpn_ransac_finish at 10 HN slots - with the solver's own validity, with the valid slots
+      packed to the front of the buffer (what the invalid lanes between them cost: a wave is busy while one of its lanes is)
+      and with every slot invalid (the launch's fixed part); ransac_pose(solver="5pt") at HN and at HN / 4 samples and
+      from_flows with it, beside the 8-point figures of (a); and what came out.
+
 There is no pass / fail time: the numbers are recorded.
 
-    python tools/ransac_time.py [--rounds 5] [--iters 20] [--out profiles/r20_ransac.json]
+    python tools/ransac_time.py [--rounds 5] [--iters 20] [--out profiles/r20_ransac.json] [--out5 profiles/r21_ransac5.json]
 """
 import argparse
 import json
@@ -95,11 +101,61 @@ def windows(fn, rounds, iters):
     return spread([time_form(fn, iters)[0] for _ in range(rounds)])
 
 
+def five_point(m, flows, intr, pose, true, counts, sel, args, eight):
+    """(d) of the module's docstring -> the dict written to --out5; `eight` holds (a)'s kernels and calls."""
+    dev, N, SL = intr.device, int(m.xy.shape[1]), 10 * HN
+    chunks = -(-N // _hip.CONSTANTS["RANSAC_CHUNK"])
+    E = torch.empty(B, SL, 9, dtype=torch.float64, device=dev)
+    sample = torch.empty(B, HN, 5, dtype=torch.int32, device=dev)
+    valid = torch.empty(B, SL, dtype=torch.uint8, device=dev)
+    partial = torch.empty(B, chunks, SL + 1, dtype=torch.int32, device=dev)
+    po, inl = torch.empty(B, 4, 4, device=dev), torch.empty(B, N, dtype=torch.uint8, device=dev)
+    st = torch.empty(B, 8, dtype=torch.float64, device=dev)
+    s = _hip.stream_handle()
+    xy, cn, K, P = m.xy.data_ptr(), m.count.data_ptr(), intr.data_ptr(), pose.data_ptr()
+    hyp = lambda: _hip.call("cpn_ransac_hypotheses5", xy, cn, K, B, N, HN, SEED, E.data_ptr(), sample.data_ptr(), valid.data_ptr(), s)
+    hyp()
+    order = torch.argsort(valid, dim=1, descending=True, stable=True)
+    packed_E = torch.gather(E, 1, order[..., None].expand(-1, -1, 9)).contiguous()
+    packed_v, none_v = torch.gather(valid, 1, order).contiguous(), torch.zeros_like(valid)
+
+    def score(Eb, vb):
+        return lambda: _hip.call("cpn_ransac_score", Eb.data_ptr(), vb.data_ptr(), xy, cn, K, P, B, N, SL, PX, partial.data_ptr(), s)
+    kernels = {"ransac_hypotheses5_ms": hyp, "ransac_score_10x_slots_ms": score(E, valid),
+               "ransac_score_valid_slots_packed_ms": score(packed_E, packed_v), "ransac_score_no_valid_slot_ms": score(E, none_v)}
+    out = {"kernels": {k: windows(fn, args.rounds, args.iters) for k, fn in kernels.items()}}
+    score(E, valid)()
+    out["kernels"]["ransac_finish_10x_slots_ms"] = windows(
+        lambda: _hip.call("cpn_ransac_finish", E.data_ptr(), valid.data_ptr(), partial.data_ptr(), xy, cn, K, P, B, N, SL, PX,
+                          po.data_ptr(), inl.data_ptr(), st.data_ptr(), s), args.rounds, args.iters)
+    opts = {"hypotheses": HN, "inlier_px": PX, "seed": SEED, "start": "ransac", "solver": "5pt"}
+    forms = {"ransac_pose_5pt_ms": lambda: mt.ransac_pose(m, intr, pose, HN, PX, SEED, solver="5pt"),
+             "ransac_pose_5pt_quarter_samples_ms": lambda: mt.ransac_pose(m, intr, pose, HN // 4, PX, SEED, solver="5pt"),
+             "refine_pose_ms": lambda: mt.refine_pose(m, intr, pose),
+             "from_flows_with_ransac_5pt_ms": lambda: mt.from_flows(flows, intr, pose, S, ransac=opts, **sel)}
+    out["calls"] = {k: windows(fn, args.rounds, args.iters) for k, fn in forms.items()}
+    out["eight_point_same_process"] = eight
+    ours = mt.from_flows(flows, intr, pose, S, ransac=opts, **sel)
+    quarter = mt.ransac_pose(m, intr, pose, HN // 4, PX, SEED, solver="5pt")
+
+    def off(Pm):
+        return [[angle_deg(Pm[b, :3, :3], true[b, :3, :3]), dir_deg(Pm[b, :3, 3], true[b, :3, 3])] for b in range(B)]
+    out["result"] = {"valid_slots_of": SL, "valid_slots": [int(v) for v in valid.sum(1).cpu()],
+                     "valid_samples": [int(v) for v in valid.view(B, HN, 10).any(2).sum(1).cpu()],
+                     "ransac_stats": [[float(v) for v in row] for row in ours["ransac"]["stats"].cpu()],
+                     "ransac_stats_quarter_samples": [[float(v) for v in row] for row in quarter["stats"].cpu()],
+                     "matches_per_pair": counts,
+                     "degrees_from_truth": {"ransac_5pt": off(ours["ransac"]["pose"]), "refined_from_ransac_5pt": off(ours["pose"]),
+                                            "ransac_5pt_quarter_samples": off(quarter["pose"])}}
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--out5", default=None)
     args = ap.parse_args()
     assert torch.cuda.is_available(), "ransac_time.py measures on a HIP device"
     dev = torch.device("cuda:0")
@@ -156,10 +212,14 @@ def main():
                      "degrees_from_truth": {"rel_pose": off(pose), "refined_from_rel_pose": off(plain["pose"]),
                                             "ransac": off(ours["ransac"]["pose"]), "refined_from_ransac": off(ours["pose"])}}
     print(json.dumps(res, indent=1))
-    if args.out:
-        with open(args.out, "w") as f:
-            json.dump(res, f, indent=1)
-            f.write("\n")
+    res5 = dict({k: res[k] for k in ("device", "pairs", "side", "flow_side", "hypotheses", "inlier_px", "seed", "rounds", "iters", "ms")},
+                **five_point(m, (f0, f1), intr, pose, true, counts, sel, args, {"kernels": res["kernels"], "calls": res["calls"]}))
+    print(json.dumps(res5, indent=1))
+    for path, what in ((args.out, res), (args.out5, res5)):
+        if path:
+            with open(path, "w") as f:
+                json.dump(what, f, indent=1)
+                f.write("\n")
 
 
 if __name__ == "__main__":
