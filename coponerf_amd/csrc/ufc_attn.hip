@@ -744,8 +744,11 @@ __global__ __launch_bounds__(256) void cva_kd_kernel(const float* __restrict__ k
         float acc = 0.0f;
         if (p < P) {
             const int y = p / hs, x = p - y * hs;
-            const int Y0 = max(0, (int)floorf((float)(y - 1) * inv_s) - 1), Y1 = min(fs - 1, (int)ceilf((float)(y + 1) * inv_s) + 1);
-            const int X0 = max(0, (int)floorf((float)(x - 1) * inv_s) - 1), X1 = min(fs - 1, (int)ceilf((float)(x + 1) * inv_s) + 1);
+            // one low-res point (sc == 0): every token lands on it, the window is the whole axis, as in the resize adjoint
+            const int Y0 = sc > 0.0f ? max(0, (int)floorf((float)(y - 1) * inv_s) - 1) : 0;
+            const int Y1 = sc > 0.0f ? min(fs - 1, (int)ceilf((float)(y + 1) * inv_s) + 1) : fs - 1;
+            const int X0 = sc > 0.0f ? max(0, (int)floorf((float)(x - 1) * inv_s) - 1) : 0;
+            const int X1 = sc > 0.0f ? min(fs - 1, (int)ceilf((float)(x + 1) * inv_s) + 1) : fs - 1;
             for (int Y = Y0; Y <= Y1; ++Y) {
                 const float wy = w1d(Y, y);
                 if (wy == 0.0f) continue;
