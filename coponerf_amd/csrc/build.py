@@ -9,9 +9,10 @@ sampling coordinates of the flow warp (its window sums name their FMAs), and sum
 novel_views.hip for the one-rounding-per-operation sums of its resample and its byte pack; epipolar.hip for the float64
 operation sequence of its fundamental matrices and line end points; point_cloud.hip for that of its points and votes; matches.hip
 for the flow warp's fp32 sequence and the float64 sequence of its residuals, Jacobians and sums; splat.hip for the float64
-sequence of its projection; ransac.hip for that of its 8-point systems, its residuals (sampson.h, shared with matches.hip) and
-its split of the essential matrix; ransac5.hip for that of its 5-point solver, which tests/ransac5_ref.py follows bit for bit
-(both take their sampler from ransac_draw.h); mesh.hip for that of its signed distances and vertices; raster.hip for that of its projection,
+sequence of its projection; ransac.hip for that of its 8-point systems, its residuals (sampson.h, shared with matches.hip, as
+is pose_out.h: rel_pose's use and the pose written out) and its split of the essential matrix; ransac5.hip for that of its 5-point
+solver, which tests/ransac5_ref.py follows bit for bit (both take their sampler and shape rule from ransac_common.h and their
+system, elimination and null vectors from epipolar_system.h); mesh.hip for that of its signed distances and vertices; raster.hip for that of its projection,
 depths and colours.  The last five share pinhole.h (the float64 camera; its bodies also switch contraction off by pragma) and
 splat and raster zbuffer.h (the key, its atomic minimum, the resolve stores, the clear and the image checks).
 """

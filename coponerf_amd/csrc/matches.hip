@@ -15,11 +15,13 @@
 //
 // The residual is float64 from the fp32 inputs, one rounding per operation (-ffp-contract=off), sums left to right:
 // tests/matches_ref.py restates all three in numpy.  Cam and Pose are pinhole.h's; essential, sampson and residual_ok are sampson.h's,
-// which ransac.hip shares.
+// the use of rel_pose and the pose written out pose_out.h's, the count clamp ransac_common.h's: ransac.hip shares all three.
 #include "common.h"
 #include "compact.h"
 #include "flow_warp.h"
 #include "pinhole.h"
+#include "pose_out.h"
+#include "ransac_common.h"
 #include "sampson.h"
 
 #include <math.h>
@@ -201,23 +203,16 @@ __global__ __launch_bounds__(NT) void refine_pose_kernel(const float* __restrict
     __shared__ RefineState st;
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const float* const P = rel_pose + (size_t)b * 16;
-    int n = count[b];
-    n = n < 0 ? 0 : (n > N ? N : n);
+    const int n = clamp_count(count[b], N);
     double len0 = 0.0, cost0 = 0.0;
     if (tid == 0) {
-        const Pose rel = load_pose(P);
-        bool fin = true;                                   // finite64, this unit's test: not pinhole.h's pose_finite
-        for (int r = 0; r < 3; ++r) {
-            for (int c = 0; c < 3; ++c) {
-                st.R[3 * r + c] = rel.R[r][c];
-                fin = fin && finite64(rel.R[r][c]);
-            }
-            fin = fin && finite64(rel.t[r]);
-        }
-        len0 = sqrt((rel.t[0] * rel.t[0] + rel.t[1] * rel.t[1]) + rel.t[2] * rel.t[2]);
-        st.go = (fin && len0 > 0.0 && finite64(len0) && n > 0 && iters > 0) ? 1 : 0;
+        const RelStart start = rel_start(P);
+        len0 = start.len0;
+        st.go = (start.ok && n > 0 && iters > 0) ? 1 : 0;
+        for (int r = 0; r < 3; ++r)                         // whether or not the pair goes on, as ever: the compiler's schedule
+            for (int c = 0; c < 3; ++c) st.R[3 * r + c] = start.rel.R[r][c];        // of the match loop below turns on it
         if (st.go) {
-            for (int r = 0; r < 3; ++r) st.t[r] = rel.t[r] / len0;
+            for (int r = 0; r < 3; ++r) st.t[r] = start.rel.t[r] / len0;
             set_matrices(st);
         }
     }
@@ -302,29 +297,16 @@ __global__ __launch_bounds__(NT) void refine_pose_kernel(const float* __restrict
             }
             st.go = more ? 1 : 0;
             if (!more) {
-                float* const o = pose + (size_t)b * 16;
-                double dR = 0.0, dt = 0.0;
-                for (int r = 0; r < 3; ++r) {
-                    for (int c = 0; c < 3; ++c) {
-                        o[4 * r + c] = (float)st.R[3 * r + c];
-                        const double e = st.R[3 * r + c] - (double)P[4 * r + c];
-                        dR += e * e;
-                    }
-                    o[4 * r + 3] = (float)(len0 * st.t[r]);
-                    const double e = st.t[r] - (double)P[4 * r + 3] / len0;
-                    dt += e * e;
-                    o[12 + r] = 0.0f;
-                }
-                o[15] = 1.0f;
-                // |R - R0|_F = 2 sqrt(2) sin(angle / 2), |t - t0| = 2 sin(angle / 2): exact down to the smallest angles
-                const double deg = 57.29577951308232;
+                double deg_R, deg_t;
+                pose_angles(st.R, st.t, load_pose(P), len0, deg_R, deg_t);     // rel_pose read again: not held over the passes
+                store_pose(pose + (size_t)b * 16, st.R, st.t, len0);
                 double* const so = stats + (size_t)b * 8;
                 so[0] = cost0;
                 so[1] = sum[27];
                 so[2] = sum[28];
                 so[3] = sum[29];
-                so[4] = 2.0 * asin(fmin(sqrt(dR) / 2.8284271247461903, 1.0)) * deg;
-                so[5] = 2.0 * asin(fmin(sqrt(dt) / 2.0, 1.0)) * deg;
+                so[4] = deg_R;
+                so[5] = deg_t;
                 so[6] = (double)done;
                 so[7] = (double)status;
             }

@@ -1,10 +1,11 @@
 // The relative pose of two photos from their matches alone (coponerf_amd/matches.py: ransac_pose): 8-point RANSAC.
 //
 //   ransac_hypotheses_kernel  cpn_ransac_hypotheses: one thread per hypothesis index h (workgroups of 64), every pair in the
-//                             launch.  The thread draws 8 distinct rows by a counter hash of (seed, h, draw), forms the 8 x 9
-//                             system of a^T E b = 0 and eliminates it with complete pivoting.  The 72 doubles, the solution and
-//                             the column permutation live in LDS, one column per lane ([entry][lane]: a lane's accesses never
-//                             meet another lane's bank), so that the pivot's runtime indices never touch a private array.
+//                             launch.  The thread draws 8 distinct rows by a counter hash of (seed, h, draw) (ransac_common.h),
+//                             forms the 8 x 9 system of a^T E b = 0, eliminates it with complete pivoting and takes its null
+//                             vector (epipolar_system.h, which ransac5.hip shares).  The 72 doubles, the solution and the column
+//                             permutation live in LDS, one column per lane ([entry][lane]: a lane's accesses never meet another
+//                             lane's bank), so that the pivot's runtime indices never touch a private array.
 //   ransac_score_kernel       cpn_ransac_score: grid (tiles of 256 hypotheses, chunks of CPN_RANSAC_CHUNK matches, pairs).  The
 //                             workgroup normalises its chunk into LDS once and packs the tile's valid slots to its first
 //                             lanes (a ballot and four counts: invalid slots, most of the 5-point solver's, write their 0 and
@@ -14,10 +15,13 @@
 //                             splits its E by a one-sided Jacobi SVD, all threads mark the inliers and vote on the four poses.
 //
 // Every decision is an integer or a comparison of values that tests/ransac_ref.py forms in the same float64 sequence
-// (-ffp-contract=off): no atomics, integer sums only, the same bytes every run.  The residual is sampson.h's.
+// (-ffp-contract=off): no atomics, integer sums only, the same bytes every run.  The residual and the inlier rule are
+// sampson.h's; the use of rel_pose, the pose's 16 floats and its angles are pose_out.h's, which matches.hip's refinement shares.
 #include "common.h"
+#include "epipolar_system.h"
 #include "pinhole.h"
-#include "ransac_draw.h"
+#include "pose_out.h"
+#include "ransac_common.h"
 #include "sampson.h"
 
 #include "../../include/coponerf_hip.h"
@@ -26,13 +30,10 @@
 
 namespace {
 
+namespace es = epipolar_system;
 constexpr int NT = 256;
 constexpr int HT = 64;                                     // hypotheses: threads per workgroup
-constexpr int CH = CPN_RANSAC_CHUNK;
 constexpr int SWEEPS = 8;
-constexpr double RANK_TOL = 1e-9;
-using ransac_draw::clamp_count;
-using ransac_draw::finite32;
 
 __global__ __launch_bounds__(HT) void ransac_hypotheses_kernel(const float* __restrict__ xy, const int* __restrict__ count,
                                                                const float* __restrict__ intrinsics, int N, int Hn,
@@ -52,102 +53,21 @@ __global__ __launch_bounds__(HT) void ransac_hypotheses_kernel(const float* __re
 #pragma unroll
     for (int j = 0; j < 8; ++j) sample[at * 8 + j] = s[j];
 
-    // ---- the system
+    // ---- the system, its elimination and the null vector: back substitution with the free (last) unknown 1
     bool ok = got == 8;
     if (ok) {
         const Cam k0 = load_cam(intrinsics + ((size_t)b * 2 + 0) * 16), k1 = load_cam(intrinsics + ((size_t)b * 2 + 1) * 16);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const float* const m = xy + ((size_t)b * N + s[j]) * 4;
-            const float x0 = m[0], y0 = m[1], x1 = m[2], y1 = m[3];
-            ok = ok && finite32(x0) && finite32(y0) && finite32(x1) && finite32(y1);
-            const double a0 = ((double)x0 - k0.cx) / k0.fx, a1 = ((double)y0 - k0.cy) / k0.fy;
-            const double b0 = ((double)x1 - k1.cx) / k1.fx, b1 = ((double)y1 - k1.cy) / k1.fy;
-            A[9 * j + 0][l] = a0 * b0;
-            A[9 * j + 1][l] = a0 * b1;
-            A[9 * j + 2][l] = a0;
-            A[9 * j + 3][l] = a1 * b0;
-            A[9 * j + 4][l] = a1 * b1;
-            A[9 * j + 5][l] = a1;
-            A[9 * j + 6][l] = b0;
-            A[9 * j + 7][l] = b1;
-            A[9 * j + 8][l] = 1.0;
-        }
+        ok = es::fill_rows<8>(A, l, xy + (size_t)b * N * 4, s, k0, k1);
     }
-    // ---- elimination with complete pivoting
-    if (ok) {
-        for (int c = 0; c < 9; ++c) perm[c][l] = c;
-        double p0 = 0.0;
-        for (int k = 0; k < 8 && ok; ++k) {
-            double best = -1.0;
-            int pr = k, pc = k;
-            for (int r = k; r < 8; ++r)
-                for (int c = k; c < 9; ++c) {
-                    const double v = fabs(A[9 * r + c][l]);
-                    if (v > best) {                        // the first largest in (row, column) order; never a NaN
-                        best = v;
-                        pr = r;
-                        pc = c;
-                    }
-                }
-            if (pr != k)
-                for (int c = 0; c < 9; ++c) {
-                    const double v = A[9 * k + c][l];
-                    A[9 * k + c][l] = A[9 * pr + c][l];
-                    A[9 * pr + c][l] = v;
-                }
-            if (pc != k) {
-                for (int r = 0; r < 8; ++r) {
-                    const double v = A[9 * r + k][l];
-                    A[9 * r + k][l] = A[9 * r + pc][l];
-                    A[9 * r + pc][l] = v;
-                }
-                const int v = perm[k][l];
-                perm[k][l] = perm[pc][l];
-                perm[pc][l] = v;
-            }
-            const double p = A[9 * k + k][l];
-            if (k == 0) p0 = fabs(p);
-            ok = finite64(p) && fabs(p) > RANK_TOL * p0;   // the rank test
-            if (!ok) break;
-            for (int r = k + 1; r < 8; ++r) {
-                const double m = A[9 * r + k][l] / p;
-                for (int c = k + 1; c < 9; ++c) A[9 * r + c][l] = A[9 * r + c][l] - m * A[9 * k + c][l];
-            }
-        }
-    }
-    // ---- back substitution with the free (last) unknown 1, the norm and the sign
+    if (ok) ok = es::eliminate<8>(A, perm, l, es::RANK_TOL);
     double e[9];
 #pragma unroll
     for (int c = 0; c < 9; ++c) e[c] = 0.0;
     if (ok) {
-        X[8][l] = 1.0;
-        for (int r = 7; r >= 0; --r) {
-            double sum = A[9 * r + r + 1][l] * X[r + 1][l];
-            for (int c = r + 2; c < 9; ++c) sum = sum + A[9 * r + c][l] * X[c][l];
-            X[r][l] = -sum / A[9 * r + r][l];
-        }
-        for (int c = 0; c < 9; ++c) A[perm[c][l]][l] = X[c][l];           // the system is spent: entries 0 .. 8 take E
+        es::null_vector<8>(A, X, perm, l, 0, A);            // the system is spent: entries 0 .. 8 take E
 #pragma unroll
         for (int c = 0; c < 9; ++c) e[c] = A[c][l];
-        double ss = e[0] * e[0];
-#pragma unroll
-        for (int c = 1; c < 9; ++c) ss = ss + e[c] * e[c];
-        const double nrm = sqrt(ss);
-        double big = -1.0, lead = 0.0;
-#pragma unroll
-        for (int c = 0; c < 9; ++c) {
-            e[c] = e[c] / nrm;
-            if (fabs(e[c]) > big) {
-                big = fabs(e[c]);
-                lead = e[c];
-            }
-        }
-#pragma unroll
-        for (int c = 0; c < 9; ++c) {
-            if (lead < 0.0) e[c] = -e[c];
-            ok = ok && finite64(e[c]);
-        }
+        ok = es::unit_essential(e);
     }
 #pragma unroll
     for (int c = 0; c < 9; ++c) E[at * 9 + c] = ok ? e[c] : 0.0;
@@ -204,9 +124,7 @@ __global__ __launch_bounds__(NT) void ransac_score_kernel(const double* __restri
     }
     int cnt = 0;
     for (int i = 0; i < m; ++i) {
-        const Sampson s = sampson_normalised(e, k0, k1, pts[i][0], pts[i][1], pts[i][2], pts[i][3]);
-        const double r = s.n / sqrt(s.D);
-        if (residual_ok(s, r) && fabs(r) <= inlier_px) ++cnt;
+        if (within(sampson_normalised(e, k0, k1, pts[i][0], pts[i][1], pts[i][2], pts[i][3]), inlier_px)) ++cnt;
     }
     out[mine] = cnt;
 }
@@ -368,8 +286,7 @@ __global__ __launch_bounds__(NT) void ransac_finish_kernel(const double* __restr
         if (solved && i < n) {
             const float* const m = rows + (size_t)i * 4;
             const Sampson s = sampson(st.E, k0, k1, (double)m[0], (double)m[1], (double)m[2], (double)m[3]);
-            const double r = s.n / sqrt(s.D);
-            in = residual_ok(s, r) && fabs(r) <= inlier_px;
+            in = within(s, inlier_px);
             if (in) {
                 const double a[3] = {s.a0, s.a1, 1.0};
 #pragma unroll
@@ -393,20 +310,6 @@ __global__ __launch_bounds__(NT) void ransac_finish_kernel(const double* __restr
     for (int k = 0; k < 4; ++k) votes[k] = block_all(votes[k], add, st.red);
     if (tid != 0) return;
 
-    // rel_pose: its length where it is finite and not zero, its inliers under the same rule
-    double len0 = 0.0;
-    bool rel_ok = false;
-    Pose rel;
-    if (P) {
-        rel = load_pose(P);
-        rel_ok = true;
-        for (int r = 0; r < 3; ++r) {
-            for (int c = 0; c < 3; ++c) rel_ok = rel_ok && finite64(rel.R[r][c]);
-            rel_ok = rel_ok && finite64(rel.t[r]);
-        }
-        len0 = sqrt((rel.t[0] * rel.t[0] + rel.t[1] * rel.t[1]) + rel.t[2] * rel.t[2]);
-        rel_ok = rel_ok && len0 > 0.0 && finite64(len0);
-    }
     const bool nothing = usable < 8 || Hn == 0;
     if (nothing || !solved) {                              // status 2, or 1: no valid hypothesis
         for (int k = 0; k < 16; ++k) o[k] = P ? P[k] : ((k % 5 == 0) ? 1.0f : 0.0f);
@@ -420,41 +323,22 @@ __global__ __launch_bounds__(NT) void ransac_finish_kernel(const double* __restr
     for (int k = 1; k < 4; ++k)
         if (votes[k] > votes[pick]) pick = k;              // most votes, the lowest candidate on ties
     const double* const R = st.R[pick >> 1];
-    const double sign = (pick & 1) ? -1.0 : 1.0, scale = rel_ok ? len0 : 1.0;
-    double dR = 0.0, dt = 0.0;
-    for (int r = 0; r < 3; ++r) {
-        const double tr = sign * st.t[r];
-        for (int c = 0; c < 3; ++c) {
-            o[4 * r + c] = (float)R[3 * r + c];
-            if (rel_ok) {
-                const double e = R[3 * r + c] - rel.R[r][c];
-                dR += e * e;
-            }
-        }
-        o[4 * r + 3] = (float)(scale * tr);
-        if (rel_ok) {
-            const double e = tr - rel.t[r] / len0;
-            dt += e * e;
-        }
-        o[12 + r] = 0.0f;
-    }
-    o[15] = 1.0f;
-    const double deg = 57.29577951308232;
+    const double sign = (pick & 1) ? -1.0 : 1.0;
+    const double t[3] = {sign * st.t[0], sign * st.t[1], sign * st.t[2]};
+    // rel_pose, where it is finite and not zero: its length scales t, and the angles are measured from it (0 where it is not)
+    const RelStart start = rel_start(P);
+    store_pose(o, R, t, start.ok ? start.len0 : 1.0);
+    double deg_R = 0.0, deg_t = 0.0;
+    if (start.ok) pose_angles(R, t, start.rel, start.len0, deg_R, deg_t);
     so[0] = (double)winner_count;
     so[1] = (double)usable;
     so[2] = (double)winner;
     so[3] = (double)n_valid;
     so[4] = P ? (double)rel_count : -1.0;
-    so[5] = 2.0 * asin(fmin(sqrt(dR) / 2.8284271247461903, 1.0)) * deg;
-    so[6] = 2.0 * asin(fmin(sqrt(dt) / 2.0, 1.0)) * deg;
+    so[5] = deg_R;
+    so[6] = deg_t;
     so[7] = 0.0;
 }
-
-bool shape_ok(int B, int N, int Hn) {
-    return B >= 1 && B <= 32767 && N >= 1 && N <= (1 << 24) && Hn >= 0 && Hn <= (1 << 20) &&
-           (long long)B * cpn_cdiv(N, CH) * (Hn + 1LL) < (1LL << 31);
-}
-bool px_ok(double px) { return px >= 0.0 && px <= 1.79769313486231570815e308; }
 
 }  // namespace
 

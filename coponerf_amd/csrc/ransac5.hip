@@ -1,8 +1,9 @@
 // The minimal solver of coponerf_amd/matches.py: ransac_pose(solver="5pt"): up to 10 essential matrices from 5 matches.
 //
 //   ransac_hypotheses5_kernel  cpn_ransac_hypotheses5: one thread per sample index h (workgroups of 32), every pair in the launch.
-//                              The thread draws 5 distinct rows (ransac_draw.h: the first 5 of round 20's 8), eliminates the
-//                              5 x 9 system with complete pivoting, takes the four null vectors by back substitution, forms the
+//                              The thread draws 5 distinct rows (ransac_common.h: the first 5 of round 20's 8), eliminates the
+//                              5 x 9 system with complete pivoting and takes the four null vectors by back substitution
+//                              (epipolar_system.h: the 8-point solver's code with 5 rows, its norm and sign too), forms the
 //                              ten cubic constraints on E = x X + y Y + z Z + W as a 10 x 20 matrix, reduces it by Gauss-Jordan
 //                              elimination, and finds the real roots of the degree-10 determinant in z by a Sturm chain,
 //                              bisection and Newton steps.  cpn_ransac_score and cpn_ransac_finish (ransac.hip) take the 10 Hn
@@ -18,8 +19,9 @@
 // Every operation is one of + - * / sqrt or a comparison, with one rounding (-ffp-contract=off) and fixed trip counts, in the
 // sequence of tests/ransac5_ref.py: the kernel's bits are the restatement's.
 #include "common.h"
+#include "epipolar_system.h"
 #include "pinhole.h"
-#include "ransac_draw.h"
+#include "ransac_common.h"
 #include "sampson.h"
 
 #include "../../include/coponerf_hip.h"
@@ -28,10 +30,9 @@
 
 namespace {
 
+namespace es = epipolar_system;
 constexpr int L5 = 32;                                     // samples (lanes) per workgroup
-constexpr int CH = CPN_RANSAC_CHUNK;
-constexpr double RANK_TOL = 1e-9;                          // the 5 x 9 elimination: round 20's
-constexpr double RANK_TOL10 = 1e-10;                       // the 10 x 20 elimination
+constexpr double RANK_TOL10 = 1e-10;                       // the 10 x 20 elimination; the 5 x 9 one keeps round 20's
 constexpr int BISECT = 40;
 constexpr int NEWTON = 4;
 // LDS entries per lane
@@ -43,9 +44,6 @@ constexpr int S_R = 66;                                    // a remainder at wor
 constexpr int S_P1 = 80, S_P2 = 88, S_P3 = 96;             // the cross product of rows 0 and 1 of B(z): 8, 8 and 7 coefficients
 constexpr int S_N = 200;                                   // the four null vectors, entry 9 v + c
 constexpr int S_ALL = 236;
-
-using ransac_draw::clamp_count;
-using ransac_draw::finite32;
 
 // ---- the monomials: variables 0 = x, 1 = y, 2 = z, 3 = 1; pairs and triples in lexicographic order
 __device__ __forceinline__ constexpr int pair_at(int i, int j) {                 // i <= j
@@ -177,82 +175,15 @@ __global__ __launch_bounds__(L5) void ransac_hypotheses5_kernel(const float* __r
 #pragma unroll
     for (int j = 0; j < 5; ++j) sample[at * 5 + j] = s[j];
 
-    // ---- the system
+    // ---- the system, 5 steps of elimination, and the four null vectors: the free unknown 5 + v is 1, the other three 0
     bool ok = got == 5;
     if (ok) {
         const Cam k0 = load_cam(intrinsics + ((size_t)b * 2 + 0) * 16), k1 = load_cam(intrinsics + ((size_t)b * 2 + 1) * 16);
-#pragma unroll
-        for (int j = 0; j < 5; ++j) {
-            const float* const m = xy + ((size_t)b * N + s[j]) * 4;
-            const float x0 = m[0], y0 = m[1], x1 = m[2], y1 = m[3];
-            ok = ok && finite32(x0) && finite32(y0) && finite32(x1) && finite32(y1);
-            const double a0 = ((double)x0 - k0.cx) / k0.fx, a1 = ((double)y0 - k0.cy) / k0.fy;
-            const double b0 = ((double)x1 - k1.cx) / k1.fx, b1 = ((double)y1 - k1.cy) / k1.fy;
-            S[S_A + 9 * j + 0][l] = a0 * b0;
-            S[S_A + 9 * j + 1][l] = a0 * b1;
-            S[S_A + 9 * j + 2][l] = a0;
-            S[S_A + 9 * j + 3][l] = a1 * b0;
-            S[S_A + 9 * j + 4][l] = a1 * b1;
-            S[S_A + 9 * j + 5][l] = a1;
-            S[S_A + 9 * j + 6][l] = b0;
-            S[S_A + 9 * j + 7][l] = b1;
-            S[S_A + 9 * j + 8][l] = 1.0;
-        }
+        ok = es::fill_rows<5>(S + S_A, l, xy + (size_t)b * N * 4, s, k0, k1);
     }
-    // ---- 5 steps of elimination with complete pivoting
-    if (ok) {
-        for (int c = 0; c < 9; ++c) perm[c][l] = c;
-        double p0 = 0.0;
-        for (int k = 0; k < 5; ++k) {
-            double best = -1.0;
-            int pr = k, pc = k;
-            for (int r = k; r < 5; ++r)
-                for (int c = k; c < 9; ++c) {
-                    const double v = fabs(S[S_A + 9 * r + c][l]);
-                    if (v > best) {                        // the first largest in (row, column) order; never a NaN
-                        best = v;
-                        pr = r;
-                        pc = c;
-                    }
-                }
-            if (pr != k)
-                for (int c = 0; c < 9; ++c) {
-                    const double v = S[S_A + 9 * k + c][l];
-                    S[S_A + 9 * k + c][l] = S[S_A + 9 * pr + c][l];
-                    S[S_A + 9 * pr + c][l] = v;
-                }
-            if (pc != k) {
-                for (int r = 0; r < 5; ++r) {
-                    const double v = S[S_A + 9 * r + k][l];
-                    S[S_A + 9 * r + k][l] = S[S_A + 9 * r + pc][l];
-                    S[S_A + 9 * r + pc][l] = v;
-                }
-                const int v = perm[k][l];
-                perm[k][l] = perm[pc][l];
-                perm[pc][l] = v;
-            }
-            const double p = S[S_A + 9 * k + k][l];
-            if (k == 0) p0 = fabs(p);
-            ok = finite64(p) && fabs(p) > RANK_TOL * p0;   // the rank test
-            if (!ok) break;
-            for (int r = k + 1; r < 5; ++r) {
-                const double m = S[S_A + 9 * r + k][l] / p;
-                for (int c = k + 1; c < 9; ++c) S[S_A + 9 * r + c][l] = S[S_A + 9 * r + c][l] - m * S[S_A + 9 * k + c][l];
-            }
-        }
-    }
-    // ---- the four null vectors: the free unknown 5 + v is 1, the other three 0
-    if (ok) {
-        for (int v = 0; v < 4; ++v) {
-            for (int c = 5; c < 9; ++c) S[S_X + c][l] = c == 5 + v ? 1.0 : 0.0;
-            for (int r = 4; r >= 0; --r) {
-                double sum = S[S_A + 9 * r + r + 1][l] * S[S_X + r + 1][l];
-                for (int c = r + 2; c < 9; ++c) sum = sum + S[S_A + 9 * r + c][l] * S[S_X + c][l];
-                S[S_X + r][l] = -sum / S[S_A + 9 * r + r][l];
-            }
-            for (int c = 0; c < 9; ++c) S[S_N + 9 * v + perm[c][l]][l] = S[S_X + c][l];
-        }
-    }
+    if (ok) ok = es::eliminate<5>(S + S_A, perm, l, es::RANK_TOL);
+    if (ok)
+        for (int v = 0; v < 4; ++v) es::null_vector<5>(S + S_A, S + S_X, perm, l, v, S + S_N + 9 * v);
     // ---- the ten cubic constraints on E = x X + y Y + z Z + W
     if (ok) {
         double e[9][4];                                    // entry c of E as a linear form in (x, y, z, 1)
@@ -420,24 +351,7 @@ __global__ __launch_bounds__(L5) void ransac_hypotheses5_kernel(const float* __r
 #pragma unroll
             for (int c = 0; c < 9; ++c)
                 e[c] = ((x * S[S_N + c][l] + y * S[S_N + 9 + c][l]) + z * S[S_N + 18 + c][l]) + S[S_N + 27 + c][l];
-            double ss = e[0] * e[0];
-#pragma unroll
-            for (int c = 1; c < 9; ++c) ss = ss + e[c] * e[c];
-            const double nrm = sqrt(ss);
-            double big = -1.0, lead = 0.0;
-#pragma unroll
-            for (int c = 0; c < 9; ++c) {
-                e[c] = e[c] / nrm;
-                if (fabs(e[c]) > big) {
-                    big = fabs(e[c]);
-                    lead = e[c];
-                }
-            }
-#pragma unroll
-            for (int c = 0; c < 9; ++c) {
-                if (lead < 0.0) e[c] = -e[c];
-                on = on && finite64(e[c]);
-            }
+            on = es::unit_essential(e);
         }
 #pragma unroll
         for (int c = 0; c < 9; ++c) E[(at * 10 + r) * 9 + c] = on ? e[c] : 0.0;
@@ -450,9 +364,7 @@ __global__ __launch_bounds__(L5) void ransac_hypotheses5_kernel(const float* __r
 extern "C" int cpn_ransac_hypotheses5(const float* xy, const int* count, const float* intrinsics, int B, int N, int Hn, long long seed,
                                       double* E, int* sample, uint8_t* valid, void* stream) {
     CPN_REQUIRE(xy && count && intrinsics && E && sample && valid, CPN_E_ARG, "cpn_ransac_hypotheses5: null pointer");
-    CPN_REQUIRE(B >= 1 && B <= 32767 && N >= 1 && N <= (1 << 24) && Hn >= 1 && 10LL * Hn <= (1 << 20) &&
-                    (long long)B * cpn_cdiv(N, CH) * (10LL * Hn + 1) < (1LL << 31),
-                CPN_E_SHAPE,
+    CPN_REQUIRE(shape_ok(B, N, 10LL * Hn) && Hn >= 1, CPN_E_SHAPE,
                 "cpn_ransac_hypotheses5: need 1 <= B <= 32767, 1 <= N <= 2^24, 1 <= 10 Hn <= 2^20 and B chunks (10 Hn + 1) < 2^31 (got "
                 "B %d, N %d, Hn %d)", B, N, Hn);
     hipLaunchKernelGGL(ransac_hypotheses5_kernel, dim3(cpn_cdiv(Hn, L5), B), dim3(L5), 0, (hipStream_t)stream, xy, count, intrinsics,

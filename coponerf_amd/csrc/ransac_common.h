@@ -1,8 +1,26 @@
-// The sampler of the RANSAC kernels (ransac.hip: 8 rows, ransac5.hip: 5 rows): the counter hash of include/coponerf_hip.h, round
-// 20.  For equal (seed, h, n) the K rows are the first K of any longer draw: the loop stops at K distinct rows, nothing else.
+// What ransac.hip and ransac5.hip share beside their arithmetic (epipolar_system.h, sampson.h): the sampler - the counter hash of
+// include/coponerf_hip.h, round 20 -, the count clamp (matches.hip's refinement takes it too), the fp32 finite test, and the
+// chunk and shape rule of the entry points.
 #pragma once
 #include "common.h"
 
+namespace {
+
+constexpr int CH = CPN_RANSAC_CHUNK;
+
+__device__ __forceinline__ int clamp_count(int c, int N) { return c < 0 ? 0 : (c > N ? N : c); }
+__device__ __forceinline__ bool finite32(float v) { return fabsf(v) <= 3.402823466e38f; }               // false for NaN
+
+// B pairs of N rows and `slots` hypothesis slots (the 5-point solver's are 10 per sample): what the grids and the partial counts hold
+inline bool shape_ok(int B, int N, long long slots) {
+    return B >= 1 && B <= 32767 && N >= 1 && N <= (1 << 24) && slots >= 0 && slots <= (1 << 20) &&
+           (long long)B * cpn_cdiv(N, CH) * (slots + 1) < (1LL << 31);
+}
+inline bool px_ok(double px) { return px >= 0.0 && px <= 1.79769313486231570815e308; }
+
+}  // namespace
+
+// For equal (seed, h, n) the K rows are the first K of any longer draw: the loop stops at K distinct rows, nothing else.
 namespace ransac_draw {
 
 constexpr int DRAWS = 64;
@@ -13,8 +31,6 @@ __device__ __forceinline__ unsigned long long mix64(unsigned long long z) {     
     z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
     return z ^ (z >> 31);
 }
-__device__ __forceinline__ int clamp_count(int c, int N) { return c < 0 ? 0 : (c > N ? N : c); }
-__device__ __forceinline__ bool finite32(float v) { return fabsf(v) <= 3.402823466e38f; }               // false for NaN
 
 // K distinct rows below n for hypothesis h in the order drawn, -1 where none was -> the number drawn
 template <int K>

@@ -1,6 +1,7 @@
-// The essential matrix and the Sampson residual of matches.hip and ransac.hip, once: include/coponerf_hip.h (round 16) states
-// the sequence, tests/matches_ref.py restates it.  float64 from the fp32 inputs, one rounding per operation, sums left to right
-// as the parentheses say; the units that include this are built with -ffp-contract=off.  Cam is pinhole.h's.
+// The essential matrix, the Sampson residual and the inlier rule of matches.hip, ransac.hip and ransac5.hip, once:
+// include/coponerf_hip.h (round 16) states the sequence, tests/matches_ref.py restates it.  float64 from the fp32 inputs, one
+// rounding per operation, sums left to right as the parentheses say; the units that include this are built with
+// -ffp-contract=off.  Cam is pinhole.h's.
 #pragma once
 #include "pinhole.h"
 
@@ -53,6 +54,11 @@ __device__ __forceinline__ bool finite64(double v) { return fabs(v) <= 1.7976931
 // the residual n / sqrt(D) counts iff D > 0 and n, D and the quotient are finite
 __device__ __forceinline__ bool residual_ok(const Sampson& s, double r) {
     return s.D > 0.0 && finite64(s.D) && finite64(s.n) && finite64(r);
+}
+// .. and the match is an inlier iff it counts and lies within px pixels
+__device__ __forceinline__ bool within(const Sampson& s, double px) {
+    const double r = s.n / sqrt(s.D);
+    return residual_ok(s, r) && fabs(r) <= px;
 }
 
 }  // namespace

@@ -41,10 +41,10 @@ from ._args import device_tensors, one_device
 from .shards import crop_window
 
 
-def _cameras(who: str, intrinsics: torch.Tensor, rel_pose: torch.Tensor, B: int) -> None:
+def _cameras(who: str, intrinsics: torch.Tensor, rel_pose: Optional[torch.Tensor], B: int) -> None:
     if tuple(intrinsics.shape) != (B, 2, 4, 4):
         raise ValueError(f"{who}: intrinsics must be (B, 2, 4, 4) with B = {B} (`context.intrinsics`), got {tuple(intrinsics.shape)}")
-    if tuple(rel_pose.shape) != (B, 4, 4):
+    if rel_pose is not None and tuple(rel_pose.shape) != (B, 4, 4):
         raise ValueError(f"{who}: rel_pose must be (B, 4, 4) with B = {B}, got {tuple(rel_pose.shape)}")
 
 
@@ -226,10 +226,7 @@ def ransac_pose(matches: Matches, intrinsics: torch.Tensor, rel_pose: Optional[t
         named.append(("rel_pose", rel_pose, torch.float32, None))
     device_tensors("ransac_pose", tuple(named))
     B, N = _matches_args("ransac_pose", matches)
-    if tuple(intrinsics.shape) != (B, 2, 4, 4):
-        raise ValueError(f"ransac_pose: intrinsics must be (B, 2, 4, 4) with B = {B} (`context.intrinsics`), got {tuple(intrinsics.shape)}")
-    if rel_pose is not None and tuple(rel_pose.shape) != (B, 4, 4):
-        raise ValueError(f"ransac_pose: rel_pose must be (B, 4, 4) with B = {B}, got {tuple(rel_pose.shape)}")
+    _cameras("ransac_pose", intrinsics, rel_pose, B)
     Hn, px, seed = int(hypotheses), float(inlier_px), int(seed)
     chunks = -(-N // _hip.CONSTANTS["RANSAC_CHUNK"])
     slots = per * Hn

@@ -29,9 +29,7 @@ from tests import matches_ref as mr
 from tests import ransac_ref as rr
 
 E = mr.E
-DRAWS = 64
-RANK_TOL = 1e-9            # the 5 x 9 elimination: round 20's
-RANK_TOL10 = 1e-10         # the 10 x 20 elimination
+RANK_TOL10 = 1e-10         # the 10 x 20 elimination; the 5 x 9 one keeps round 20's (rr.RANK_TOL)
 BISECT = 40
 NEWTON = 4
 SAMPLE_OPS = 2000
@@ -48,60 +46,15 @@ COLUMNS = [(0, 0, 0), (1, 1, 1), (0, 0, 1), (0, 1, 1), (0, 0, 2), (0, 0, 3), (1,
 # ------------------------------------------------------------------------------------------------------------- the sampler
 def draw_samples5(seed, Hn, n, defect=None):
     """Round 20's draw stopped at 5 distinct rows -> (sample (Hn, 5) int32, -1 where none was; got (Hn))."""
-    sample = np.full((Hn, 5), -1, dtype=np.int32)
-    got = np.zeros(Hn, dtype=np.int64)
-    h = np.arange(Hn)
-    if n > 0:
-        for d in range(DRAWS):
-            idx = rr.draw_index(seed, h, d, n)
-            dup = (sample == idx[:, None]).any(axis=1)
-            if defect == "no redraw":
-                dup[:] = False
-            take = ~dup & (got < 5)
-            sample[h[take], got[take]] = idx[take]
-            got[take] += 1
-    return sample, got
+    return rr.draw_samples(seed, Hn, n, defect=defect, k=5)
 
 
 # ----------------------------------------------------------------------------------------------------------- the null space
 def null_basis(A, defect=None):
-    """A (H, 5, 9) -> (basis (H, 4, 9): the null vectors with the permuted unknowns 5, 6, 7, 8 set to 1 one at a time; valid)."""
-    A = np.array(A, dtype=np.float64)
-    H = len(A)
-    ar = np.arange(H)
-    perm = np.tile(np.arange(9), (H, 1))
-    valid = np.ones(H, dtype=bool)
-    p0 = None
-    with np.errstate(all="ignore"):
-        for k in range(5):
-            sub = np.abs(A[:, k:, k:])
-            sub = np.where(np.isnan(sub), -1.0, sub)
-            flat = sub.reshape(H, -1).argmax(axis=1)
-            pr, pc = k + flat // (9 - k), k + flat % (9 - k)
-            rk, rp = A[ar, k, :].copy(), A[ar, pr, :].copy()
-            A[ar, pr, :], A[ar, k, :] = rk, rp
-            ck, cp = A[ar, :, k].copy(), A[ar, :, pc].copy()
-            A[ar, :, pc], A[ar, :, k] = ck, cp
-            qk, qp = perm[ar, k].copy(), perm[ar, pc].copy()
-            perm[ar, pc], perm[ar, k] = qk, qp
-            p = A[:, k, k].copy()
-            if k == 0:
-                p0 = np.abs(p)
-            if defect != "no rank test":
-                valid &= np.isfinite(p) & (np.abs(p) > RANK_TOL * p0)
-            m = A[:, k + 1:, k] / p[:, None]
-            A[:, k + 1:, k + 1:] = A[:, k + 1:, k + 1:] - m[:, :, None] * A[:, k, None, k + 1:]
-        basis = np.zeros((H, 4, 9))
-        for j in range(4):
-            x = np.zeros((H, 9))
-            x[:, 5 + j] = 1.0
-            for r in range(4, -1, -1):
-                s = A[:, r, r + 1] * x[:, r + 1]
-                for c in range(r + 2, 9):
-                    s = s + A[:, r, c] * x[:, c]
-                x[:, r] = -s / A[:, r, r]
-            basis[ar[:, None], j, perm] = x
-    return basis, valid
+    """A (H, 5, 9) -> (basis (H, 4, 9): the null vectors with the permuted unknowns 5, 6, 7, 8 set to 1 one at a time; valid):
+    round 20's elimination stopped after 5 steps, and four of its back substitutions."""
+    A, perm, valid = rr.eliminate(A, 5, defect)
+    return np.stack([rr.back_substitute(A, perm, 5, free=5 + j) for j in range(4)], axis=1), valid
 
 
 # ---------------------------------------------------------------------------------------------------------- the constraints

@@ -58,10 +58,10 @@ def draw_index(seed, h, d, n, pair=0, defect=None):
         return (((u >> np.uint64(32)) * np.uint64(n)) >> np.uint64(32)).astype(np.int64)
 
 
-def draw_samples(seed, Hn, n, pair=0, defect=None):
-    """-> (sample (Hn, 8) int32 in the order drawn, -1 where none was; got (Hn) the number drawn).  defect="no redraw": a
-    repeated index is taken."""
-    sample = np.full((Hn, 8), -1, dtype=np.int32)
+def draw_samples(seed, Hn, n, pair=0, defect=None, k=8):
+    """-> (sample (Hn, k) int32 in the order drawn, -1 where none was; got (Hn) the number drawn): the draw stops at k distinct
+    rows, so a shorter sample is the head of a longer one.  defect="no redraw": a repeated index is taken."""
+    sample = np.full((Hn, k), -1, dtype=np.int32)
     got = np.zeros(Hn, dtype=np.int64)
     h = np.arange(Hn)
     if n > 0:
@@ -70,7 +70,7 @@ def draw_samples(seed, Hn, n, pair=0, defect=None):
             dup = (sample == idx[:, None]).any(axis=1)
             if defect == "no redraw":
                 dup[:] = False
-            take = ~dup & (got < 8)
+            take = ~dup & (got < k)
             sample[h[take], got[take]] = idx[take]
             got[take] += 1
     return sample, got
@@ -89,9 +89,9 @@ def system(a0, a1, b0, b1):
         return np.stack((a0 * b0, a0 * b1, a0, a1 * b0, a1 * b1, a1, b0, b1, np.ones_like(a0)), axis=-1)
 
 
-def null_vector(A, defect=None):
-    """A (H, 8, 9) -> (e (H, 9) of Frobenius norm 1 with its largest entry positive, 0 where invalid; valid (H) bool): the
-    header's elimination with complete pivoting, rank test, back substitution, norm and sign.  defect="no rank test"."""
+def eliminate(A, rows, defect=None):
+    """A (H, rows, 9) -> (the systems after `rows` steps of the header's elimination with complete pivoting, perm (H, 9) the column
+    of E at each permuted position, valid (H) bool the rank test).  defect="no rank test"."""
     A = np.array(A, dtype=np.float64)
     H = len(A)
     ar = np.arange(H)
@@ -99,7 +99,7 @@ def null_vector(A, defect=None):
     valid = np.ones(H, dtype=bool)
     p0 = None
     with np.errstate(all="ignore"):
-        for k in range(8):
+        for k in range(rows):
             sub = np.abs(A[:, k:, k:])
             sub = np.where(np.isnan(sub), -1.0, sub)
             flat = sub.reshape(H, -1).argmax(axis=1)               # the first largest in (row, column) order
@@ -117,15 +117,33 @@ def null_vector(A, defect=None):
                 valid &= np.isfinite(p) & (np.abs(p) > RANK_TOL * p0)
             m = A[:, k + 1:, k] / p[:, None]
             A[:, k + 1:, k + 1:] = A[:, k + 1:, k + 1:] - m[:, :, None] * A[:, k, None, k + 1:]
-        x = np.zeros((H, 9))
-        x[:, 8] = 1.0
-        for r in range(7, -1, -1):
+    return A, perm, valid
+
+
+def back_substitute(A, perm, rows, free):
+    """The null vector (H, 9) of eliminate's systems with the permuted unknown `free` (>= rows) set to 1 and the other free ones
+    to 0, in E's column order."""
+    H = len(A)
+    x = np.zeros((H, 9))
+    x[:, free] = 1.0
+    with np.errstate(all="ignore"):
+        for r in range(rows - 1, -1, -1):
             s = A[:, r, r + 1] * x[:, r + 1]
             for c in range(r + 2, 9):
                 s = s + A[:, r, c] * x[:, c]
             x[:, r] = -s / A[:, r, r]
-        e = np.zeros((H, 9))
-        e[ar[:, None], perm] = x
+    e = np.zeros((H, 9))
+    e[np.arange(H)[:, None], perm] = x
+    return e
+
+
+def null_vector(A, defect=None):
+    """A (H, 8, 9) -> (e (H, 9) of Frobenius norm 1 with its largest entry positive, 0 where invalid; valid (H) bool): the
+    header's elimination with complete pivoting, rank test, back substitution, norm and sign.  defect="no rank test"."""
+    A, perm, valid = eliminate(A, 8, defect)
+    ar = np.arange(len(A))
+    with np.errstate(all="ignore"):
+        e = back_substitute(A, perm, 8, free=8)
         ss = e[:, 0] * e[:, 0]
         for c in range(1, 9):
             ss = ss + e[:, c] * e[:, c]
