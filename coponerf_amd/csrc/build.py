@@ -12,7 +12,9 @@ for the flow warp's fp32 sequence and the float64 sequence of its residuals, Jac
 sequence of its projection; ransac.hip for that of its 8-point systems, its residuals (sampson.h, shared with matches.hip, as
 is pose_out.h: rel_pose's use and the pose written out) and its split of the essential matrix; ransac5.hip for that of its 5-point
 solver, which tests/ransac5_ref.py follows bit for bit (both take their sampler and shape rule from ransac_common.h and their
-system, elimination and null vectors from epipolar_system.h); mesh.hip for that of its signed distances and vertices; raster.hip for that of its projection,
+system, elimination and null vectors from epipolar_system.h); ransac_h.hip for that of its homographies, their transfer errors
+and their decomposition, which tests/homography_ref.py follows bit for bit (it shares ransac_score.h's tiling, jacobi_svd.h's
+sweeps and ransac_common.h's winner with ransac.hip); mesh.hip for that of its signed distances and vertices; raster.hip for that of its projection,
 depths and colours.  The last five share pinhole.h (the float64 camera; its bodies also switch contraction off by pragma) and
 splat and raster zbuffer.h (the key, its atomic minimum, the resolve stores, the clear and the image checks).
 """
@@ -64,6 +66,7 @@ UNITS = [
     ("matches.hip", ["-ffp-contract=off"]),                # flow_warp.h's fp32 sequence; float64 residuals, Jacobians and sums
     ("ransac.hip", ["-ffp-contract=off"]),                 # the float64 sequence of its systems, residuals and pose split
     ("ransac5.hip", ["-ffp-contract=off"]),                # the float64 sequence of the 5-point solver, bit for bit
+    ("ransac_h.hip", ["-ffp-contract=off"]),               # the float64 sequence of the homography model, bit for bit
     ("splat.hip", ["-ffp-contract=off"]),                  # one rounding per float64 operation of the projection
     ("mesh.hip", ["-ffp-contract=off"]),                   # one rounding per float64 operation of the TSDF and the vertices
     ("raster.hip", ["-ffp-contract=off"]),                 # one rounding per float64 operation of the projection and the depth

@@ -1,5 +1,6 @@
 // The linear system of a^T E b = 0 over R drawn matches and its null space, once: ransac.hip solves it with R = 8 (one null
-// vector, which is E), ransac5.hip with R = 5 (four, which span E).  include/coponerf_hip.h (round 20) states the sequence,
+// vector, which is E), ransac5.hip with R = 5 (four, which span E); ransac_h.hip fills the 8 x 9 system of a ~ H b instead
+// (fill_rows_h) and takes the same elimination and null vector, which is H.  include/coponerf_hip.h (round 20) states the sequence,
 // tests/ransac_ref.py restates it (eliminate, back_substitute); float64, one rounding per operation - the units that include this
 // are built with -ffp-contract=off.
 //
@@ -39,6 +40,33 @@ __device__ __forceinline__ bool fill_rows(double (*A)[L], int l, const float* __
         A[9 * j + 6][l] = b0;
         A[9 * j + 7][l] = b1;
         A[9 * j + 8][l] = 1.0;
+    }
+    return true;
+}
+
+// the homography's system a ~ H b (ransac_h.hip, round 22): match j of s[0 .. R / 2) gives the rows 2 j = (b0, b1, 1, 0, 0, 0,
+// -a0 b0, -a0 b1, -a0) and 2 j + 1 = (0, 0, 0, b0, b1, 1, -a1 b0, -a1 b1, -a1) -> all of them finite; p[j] takes (a0, a1, b0, b1)
+template <int R, int L>
+__device__ __forceinline__ bool fill_rows_h(double (*A)[L], int l, const float* __restrict__ rows, const int (&s)[R / 2], const Cam& k0,
+                                            const Cam& k1, double (&p)[R / 2][4]) {
+#pragma unroll
+    for (int j = 0; j < R / 2; ++j) {
+        const float* const m = rows + (size_t)s[j] * 4;
+        const float x0 = m[0], y0 = m[1], x1 = m[2], y1 = m[3];
+        if (!(finite32(x0) && finite32(y0) && finite32(x1) && finite32(y1))) return false;
+        const double a0 = ((double)x0 - k0.cx) / k0.fx, a1 = ((double)y0 - k0.cy) / k0.fy;
+        const double b0 = ((double)x1 - k1.cx) / k1.fx, b1 = ((double)y1 - k1.cy) / k1.fy;
+        p[j][0] = a0, p[j][1] = a1, p[j][2] = b0, p[j][3] = b1;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const double bc = c == 0 ? b0 : (c == 1 ? b1 : 1.0);
+            A[18 * j + c][l] = bc;
+            A[18 * j + 3 + c][l] = 0.0;
+            A[18 * j + 6 + c][l] = -(a0 * bc);
+            A[18 * j + 9 + c][l] = 0.0;
+            A[18 * j + 12 + c][l] = bc;
+            A[18 * j + 15 + c][l] = -(a1 * bc);
+        }
     }
     return true;
 }

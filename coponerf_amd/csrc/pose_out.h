@@ -1,4 +1,4 @@
-// What refine_pose_kernel (matches.hip) and ransac_finish_kernel (ransac.hip) do with rel_pose and with the pose they found, once:
+// What refine_pose_kernel (matches.hip) and the finish kernels of ransac.hip and ransac_h.hip do with rel_pose and with the pose they found, once:
 // is rel_pose usable, the pose as 16 floats, and its two angles to rel_pose.  float64, sums left to right as the parentheses say;
 // tests/matches_ref.py and tests/ransac_ref.py restate it.
 #pragma once

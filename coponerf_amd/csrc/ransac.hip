@@ -6,22 +6,22 @@
 //                             vector (epipolar_system.h, which ransac5.hip shares).  The 72 doubles, the solution and the column
 //                             permutation live in LDS, one column per lane ([entry][lane]: a lane's accesses never meet another
 //                             lane's bank), so that the pivot's runtime indices never touch a private array.
-//   ransac_score_kernel       cpn_ransac_score: grid (tiles of 256 hypotheses, chunks of CPN_RANSAC_CHUNK matches, pairs).  The
-//                             workgroup normalises its chunk into LDS once and packs the tile's valid slots to its first
-//                             lanes (a ballot and four counts: invalid slots, most of the 5-point solver's, write their 0 and
-//                             cost no wave); each lane then holds one E in registers and walks the chunk - every lane reads
-//                             the same LDS address, a broadcast - and counts in a register.
-//   ransac_finish_kernel      cpn_ransac_finish: one workgroup per pair sums the partial counts, picks the winner, thread 0
-//                             splits its E by a one-sided Jacobi SVD, all threads mark the inliers and vote on the four poses.
+//   ransac_score_kernel       cpn_ransac_score: ransac_score.h's kernel (tiles of 256 slots, chunks of CPN_RANSAC_CHUNK matches,
+//                             pairs; ransac_h.hip shares it) with SampsonRule: each lane holds one E in registers.
+//   ransac_finish_kernel      cpn_ransac_finish: one workgroup per pair sums the partial counts, picks the winner
+//                             (ransac_common.h), thread 0 splits its E by a one-sided Jacobi SVD (jacobi_svd.h), all threads
+//                             mark the inliers and vote on the four poses.
 //
 // Every decision is an integer or a comparison of values that tests/ransac_ref.py forms in the same float64 sequence
 // (-ffp-contract=off): no atomics, integer sums only, the same bytes every run.  The residual and the inlier rule are
 // sampson.h's; the use of rel_pose, the pose's 16 floats and its angles are pose_out.h's, which matches.hip's refinement shares.
 #include "common.h"
 #include "epipolar_system.h"
+#include "jacobi_svd.h"
 #include "pinhole.h"
 #include "pose_out.h"
 #include "ransac_common.h"
+#include "ransac_score.h"
 #include "sampson.h"
 
 #include "../../include/coponerf_hip.h"
@@ -33,7 +33,6 @@ namespace {
 namespace es = epipolar_system;
 constexpr int NT = 256;
 constexpr int HT = 64;                                     // hypotheses: threads per workgroup
-constexpr int SWEEPS = 8;
 
 __global__ __launch_bounds__(HT) void ransac_hypotheses_kernel(const float* __restrict__ xy, const int* __restrict__ count,
                                                                const float* __restrict__ intrinsics, int N, int Hn,
@@ -74,123 +73,22 @@ __global__ __launch_bounds__(HT) void ransac_hypotheses_kernel(const float* __re
     valid[at] = ok ? 1 : 0;
 }
 
-__global__ __launch_bounds__(NT) void ransac_score_kernel(const double* __restrict__ E, const uint8_t* __restrict__ valid,
-                                                          const float* __restrict__ xy, const int* __restrict__ count,
-                                                          const float* __restrict__ intrinsics, const float* __restrict__ rel_pose,
-                                                          int N, int Hn, double inlier_px, int* __restrict__ partial) {
-    __shared__ double pts[CH][4];
-    __shared__ int packed[NT], packed_n[NT / 64];
-    const int tid = threadIdx.x, chunk = blockIdx.y, b = blockIdx.z;
-    const int n = clamp_count(count[b], N), start = chunk * CH;
-    const int m = n - start < CH ? n - start : CH;         // the rows of this chunk below the count (<= 0: none)
-    const int slot = blockIdx.x * NT + tid;
-    int* const out = partial + ((size_t)b * gridDim.y + chunk) * (Hn + 1);
-    if (m <= 0) {                                          // the whole workgroup: its zeros, and nothing else
-        if (slot <= Hn) out[slot] = 0;
-        return;
-    }
-    const Cam k0 = load_cam(intrinsics + ((size_t)b * 2 + 0) * 16), k1 = load_cam(intrinsics + ((size_t)b * 2 + 1) * 16);
-    for (int i = tid; i < m; i += NT) {
-        const float* const row = xy + ((size_t)b * N + start + i) * 4;
-        pts[i][0] = ((double)row[0] - k0.cx) / k0.fx;
-        pts[i][1] = ((double)row[1] - k0.cy) / k0.fy;
-        pts[i][2] = ((double)row[2] - k1.cx) / k1.fx;
-        pts[i][3] = ((double)row[3] - k1.cy) / k1.fy;
-    }
-    // the slots of this tile that have something to count, packed in slot order: the 5-point solver leaves more than half of
-    // its 10 slots per sample invalid, scattered among the valid ones, and a wave is busy while one of its lanes is
-    bool on = slot <= Hn;
-    if (slot < Hn) on = on && valid[(size_t)b * Hn + slot] != 0;
-    if (slot == Hn) on = on && rel_pose != nullptr;        // the extra slot: rel_pose's own E, where there is one
-    if (slot <= Hn && !on) out[slot] = 0;
-    const unsigned long long wave_on = __ballot(on);
-    const int lane = tid & 63, wave = tid >> 6;
-    if (lane == 0) packed_n[wave] = __popcll(wave_on);
-    __syncthreads();                                       // pts and packed_n are written
-    int first = 0;
-    for (int w = 0; w < wave; ++w) first += packed_n[w];
-    if (on) packed[first + __popcll(wave_on & ((1ull << lane) - 1ull))] = slot;
-    __syncthreads();
-    if (tid >= (packed_n[0] + packed_n[1]) + (packed_n[2] + packed_n[3])) return;
-    const int mine = packed[tid];
+// the rule of cpn_ransac_score for ransac_score.h's kernel: one E in registers, sampson.h's residual and inlier rule
+struct SampsonRule {
+    static constexpr int EXTRA = 1;                        // slot Hn: rel_pose's own E
     double e[9];
-    if (mine < Hn) {
-        const size_t at = (size_t)b * Hn + mine;
+    __device__ __forceinline__ void from_matrix(const double* __restrict__ E) {
 #pragma unroll
-        for (int c = 0; c < 9; ++c) e[c] = E[at * 9 + c];
-    } else {
-        const Pose rel = load_pose(rel_pose + (size_t)b * 16);
+        for (int c = 0; c < 9; ++c) e[c] = E[c];
+    }
+    __device__ __forceinline__ void from_pose(const float* __restrict__ P) {
+        const Pose rel = load_pose(P);
         essential(&rel.R[0][0], rel.t, e);
     }
-    int cnt = 0;
-    for (int i = 0; i < m; ++i) {
-        if (within(sampson_normalised(e, k0, k1, pts[i][0], pts[i][1], pts[i][2], pts[i][3]), inlier_px)) ++cnt;
+    __device__ __forceinline__ bool inlier(const Cam& k0, const Cam& k1, double a0, double a1, double b0, double b1, double px) const {
+        return within(sampson_normalised(e, k0, k1, a0, a1, b0, b1), px);
     }
-    out[mine] = cnt;
-}
-
-// ---- finish
-// a value of every thread of the 256 combined by op, returned in every thread; red: 4 values in LDS
-template <class Op>
-__device__ __forceinline__ long long block_all(long long v, Op op, long long* red) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = op(v, __shfl_xor(v, o));
-    __syncthreads();                                       // red is free of its last use
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return op(op(red[0], red[1]), op(red[2], red[3]));
-}
-
-// one rotation of the one-sided Jacobi method: columns p and q of G (and of V) are turned so that G's become orthogonal
-__device__ __forceinline__ void jacobi_pair(double (&G)[9], double (&V)[9], int p, int q) {
-    const double alpha = (G[p] * G[p] + G[3 + p] * G[3 + p]) + G[6 + p] * G[6 + p];
-    const double beta = (G[q] * G[q] + G[3 + q] * G[3 + q]) + G[6 + q] * G[6 + q];
-    const double gamma = (G[p] * G[q] + G[3 + p] * G[3 + q]) + G[6 + p] * G[6 + q];
-    if (gamma == 0.0) return;
-    const double zeta = (beta - alpha) / (2.0 * gamma);
-    const double root = fabs(zeta) + sqrt(1.0 + zeta * zeta);
-    const double tt = (zeta < 0.0 ? -1.0 : 1.0) / root;
-    const double c = 1.0 / sqrt(1.0 + tt * tt), s = c * tt;
-#pragma unroll
-    for (int r = 0; r < 3; ++r) {
-        const double gp = G[3 * r + p], gq = G[3 * r + q];
-        G[3 * r + p] = c * gp - s * gq;
-        G[3 * r + q] = s * gp + c * gq;
-        const double vp = V[3 * r + p], vq = V[3 * r + q];
-        V[3 * r + p] = c * vp - s * vq;
-        V[3 * r + q] = s * vp + c * vq;
-    }
-}
-__device__ __forceinline__ double norm3(const double* v) { return sqrt((v[0] * v[0] + v[1] * v[1]) + v[2] * v[2]); }
-__device__ __forceinline__ void cross3(const double* a, const double* b, double* o) {
-    o[0] = a[1] * b[2] - a[2] * b[1];
-    o[1] = a[2] * b[0] - a[0] * b[2];
-    o[2] = a[0] * b[1] - a[1] * b[0];
-}
-__device__ __forceinline__ void swap_columns(double (&G)[9], double (&V)[9], double (&sg)[3], int p, int q) {
-    for (int r = 0; r < 3; ++r) {
-        const double g = G[3 * r + p], v = V[3 * r + p];
-        G[3 * r + p] = G[3 * r + q];
-        G[3 * r + q] = g;
-        V[3 * r + p] = V[3 * r + q];
-        V[3 * r + q] = v;
-    }
-    const double x = sg[p];
-    sg[p] = sg[q];
-    sg[q] = x;
-}
-// a right-handed orthonormal frame from columns c0 and c1 of M: f0 = c0 / |c0|, f1 = (c1 - (f0 . c1) f0) / |..|, f2 = f0 x f1
-__device__ __forceinline__ void frame(const double (&M)[9], int c0, int c1, double (&F)[3][3]) {
-    const double a[3] = {M[c0], M[3 + c0], M[6 + c0]}, b[3] = {M[c1], M[3 + c1], M[6 + c1]};
-    const double la = norm3(a);
-    for (int i = 0; i < 3; ++i) F[0][i] = a[i] / la;
-    const double d = (F[0][0] * b[0] + F[0][1] * b[1]) + F[0][2] * b[2];
-    double w[3];
-    for (int i = 0; i < 3; ++i) w[i] = b[i] - d * F[0][i];
-    const double lw = norm3(w);
-    for (int i = 0; i < 3; ++i) F[1][i] = w[i] / lw;
-    cross3(F[0], F[1], F[2]);
-}
+};
 
 struct FinishState {
     double E[9], R[2][9], t[3];
@@ -212,52 +110,25 @@ __global__ __launch_bounds__(NT) void ransac_finish_kernel(const double* __restr
     uint8_t* const mask = inlier + (size_t)b * N;
     float* const o = pose + (size_t)b * 16;
     double* const so = stats + (size_t)b * 8;
-    const auto add = [](long long x, long long y) { return x + y; };
-    const auto larger = [](long long x, long long y) { return x > y ? x : y; };
+    const long long usable = usable_rows(rows, n, st.red);
 
-    long long mine = 0;
-    for (int i = tid; i < n; i += NT) {
-        const float* const m = rows + (size_t)i * 4;
-        mine += (finite32(m[0]) && finite32(m[1]) && finite32(m[2]) && finite32(m[3])) ? 1 : 0;
-    }
-    const long long usable = block_all(mine, add, st.red);
-
-    // the winner: most inliers, the lower index on ties - the largest of count << 32 | ~index
+    // the winner: most inliers, the lower index on ties
     const int used = (n + CH - 1) / CH;                    // the chunks beyond hold zeros
     const int* const part = partial + (size_t)b * chunks * (Hn + 1);
-    long long best = -1, n_valid = 0, rel_count = 0;
-    for (int h = tid; h < Hn; h += NT) {
-        if (!valid[(size_t)b * Hn + h]) continue;
-        ++n_valid;
-        if (usable < 8) continue;
-        long long sum = 0;
-        for (int c = 0; c < used; ++c) sum += part[(size_t)c * (Hn + 1) + h];
-        best = larger(best, (sum << 32) | (long long)(0x7FFFFFFF - h));
-    }
+    long long n_valid = 0, rel_count = 0;
+    const long long best = best_hypothesis(valid + (size_t)b * Hn, part, Hn, Hn + 1, used, usable >= 8, st.red, n_valid);
     if (P)
         for (int c = tid; c < used; c += NT) rel_count += part[(size_t)c * (Hn + 1) + Hn];
-    best = block_all(best, larger, st.red);
-    n_valid = block_all(n_valid, add, st.red);
-    rel_count = block_all(rel_count, add, st.red);
+    rel_count = block_all(rel_count, add_ll, st.red);
     const int winner = best < 0 ? 0 : 0x7FFFFFFF - (int)(best & 0x7FFFFFFF);
     const long long winner_count = best < 0 ? 0 : best >> 32;
 
     if (tid == 0) {
         st.ok = 0;
         if (best >= 0) {
-            double G[9], V[9] = {1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0};
+            double G[9], V[9], sg[3];
             for (int c = 0; c < 9; ++c) G[c] = st.E[c] = E[((size_t)b * Hn + winner) * 9 + c];
-            for (int sweep = 0; sweep < SWEEPS; ++sweep) {
-                jacobi_pair(G, V, 0, 1);
-                jacobi_pair(G, V, 0, 2);
-                jacobi_pair(G, V, 1, 2);
-            }
-            // the columns by descending norm (three compare-and-swaps, a swap only where strictly smaller comes first)
-            double sg[3];
-            for (int c = 0; c < 3; ++c) sg[c] = sqrt((G[c] * G[c] + G[3 + c] * G[3 + c]) + G[6 + c] * G[6 + c]);
-            if (sg[0] < sg[1]) swap_columns(G, V, sg, 0, 1);
-            if (sg[1] < sg[2]) swap_columns(G, V, sg, 1, 2);
-            if (sg[0] < sg[1]) swap_columns(G, V, sg, 0, 1);
+            jacobi_svd(G, V, sg);
             double U[3][3], W[3][3];                       // the frames' vectors by rows: U[k] = u_k, W[k] = v_k
             frame(G, 0, 1, U);
             frame(V, 0, 1, W);
@@ -307,7 +178,7 @@ __global__ __launch_bounds__(NT) void ransac_finish_kernel(const double* __restr
         mask[i] = in ? 1 : 0;
     }
 #pragma unroll
-    for (int k = 0; k < 4; ++k) votes[k] = block_all(votes[k], add, st.red);
+    for (int k = 0; k < 4; ++k) votes[k] = block_all(votes[k], add_ll, st.red);
     if (tid != 0) return;
 
     const bool nothing = usable < 8 || Hn == 0;
@@ -362,8 +233,8 @@ extern "C" int cpn_ransac_score(const double* E, const uint8_t* valid, const flo
                 "Hn %d)", B, N, Hn);
     CPN_REQUIRE(px_ok(inlier_px), CPN_E_ARG, "cpn_ransac_score: need a finite inlier_px >= 0 (got %g)", inlier_px);
     const dim3 grid(cpn_cdiv(Hn + 1, NT), cpn_cdiv(N, CH), B);
-    hipLaunchKernelGGL(ransac_score_kernel, grid, dim3(NT), 0, (hipStream_t)stream, E, valid, xy, count, intrinsics, rel_pose, N, Hn,
-                       inlier_px, partial);
+    hipLaunchKernelGGL(ransac_score_kernel<SampsonRule>, grid, dim3(SCORE_NT), 0, (hipStream_t)stream, E, valid, xy, count, intrinsics,
+                       rel_pose, N, Hn, inlier_px, partial);
     CPN_LAUNCH_CHECK("cpn_ransac_score");
     return 0;
 }

@@ -1,6 +1,6 @@
-// What ransac.hip and ransac5.hip share beside their arithmetic (epipolar_system.h, sampson.h): the sampler - the counter hash of
-// include/coponerf_hip.h, round 20 -, the count clamp (matches.hip's refinement takes it too), the fp32 finite test, and the
-// chunk and shape rule of the entry points.
+// What ransac.hip, ransac5.hip and ransac_h.hip share beside their arithmetic (epipolar_system.h, sampson.h): the sampler - the
+// counter hash of include/coponerf_hip.h, round 20 -, the count clamp (matches.hip's refinement takes it too), the fp32 finite
+// test, the chunk and shape rule of the entry points, and the finish kernels' block reduction, usable count and winner.
 #pragma once
 #include "common.h"
 
@@ -17,6 +17,48 @@ inline bool shape_ok(int B, int N, long long slots) {
            (long long)B * cpn_cdiv(N, CH) * (slots + 1) < (1LL << 31);
 }
 inline bool px_ok(double px) { return px >= 0.0 && px <= 1.79769313486231570815e308; }
+
+// ---- what the finish kernels of ransac.hip and ransac_h.hip share: one workgroup of 256 per pair
+// a value of every thread of the 256 combined by op, returned in every thread; red: 4 values in LDS
+template <class Op>
+__device__ __forceinline__ long long block_all(long long v, Op op, long long* red) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = op(v, __shfl_xor(v, o));
+    __syncthreads();                                       // red is free of its last use
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return op(op(red[0], red[1]), op(red[2], red[3]));
+}
+__device__ __forceinline__ long long add_ll(long long x, long long y) { return x + y; }
+__device__ __forceinline__ long long larger_ll(long long x, long long y) { return x > y ? x : y; }
+
+// the rows below n with four finite values, in every thread
+__device__ __forceinline__ long long usable_rows(const float* __restrict__ rows, int n, long long* red) {
+    long long mine = 0;
+    for (int i = threadIdx.x; i < n; i += 256) {
+        const float* const m = rows + (size_t)i * 4;
+        mine += (finite32(m[0]) && finite32(m[1]) && finite32(m[2]) && finite32(m[3])) ? 1 : 0;
+    }
+    return block_all(mine, add_ll, red);
+}
+// the winner among the pair's Hn hypotheses: most inliers - the sum of `used` partial counts, `width` apart -, the lower index on
+// ties: the largest of count << 32 | ~index over the valid ones, -1 where there is none or `score` is false; n_valid: the valid ones
+__device__ __forceinline__ long long best_hypothesis(const uint8_t* __restrict__ valid, const int* __restrict__ part, int Hn, int width,
+                                                     int used, bool score, long long* red, long long& n_valid) {
+    long long best = -1;
+    n_valid = 0;
+    for (int h = threadIdx.x; h < Hn; h += 256) {
+        if (!valid[h]) continue;
+        ++n_valid;
+        if (!score) continue;
+        long long sum = 0;
+        for (int c = 0; c < used; ++c) sum += part[(size_t)c * width + h];
+        best = larger_ll(best, (sum << 32) | (long long)(0x7FFFFFFF - h));
+    }
+    best = block_all(best, larger_ll, red);
+    n_valid = block_all(n_valid, add_ll, red);
+    return best;
+}
 
 }  // namespace
 

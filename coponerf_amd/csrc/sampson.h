@@ -1,4 +1,4 @@
-// The essential matrix, the Sampson residual and the inlier rule of matches.hip, ransac.hip and ransac5.hip, once:
+// The essential matrix, the Sampson residual and the inlier rule of matches.hip, ransac.hip, ransac5.hip and ransac_h.hip, once:
 // include/coponerf_hip.h (round 16) states the sequence, tests/matches_ref.py restates it.  float64 from the fp32 inputs, one
 // rounding per operation, sums left to right as the parentheses say; the units that include this are built with
 // -ffp-contract=off.  Cam is pinhole.h's.

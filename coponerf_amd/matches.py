@@ -12,7 +12,10 @@ round.  The reference uses them for the cycle loss and a warped panel only.  Her
   ransac_pose   the relative pose from the matches ALONE: 8-point RANSAC, cpn_ransac_hypotheses / _score / _finish, three
                 launches; with it the inlier count of rel_pose under the same rule and an inlier mask; solver="5pt" takes
                 minimal samples instead (cpn_ransac_hypotheses5, up to 10 solutions each)
-  from_pair     get_z once, then the three above (and ransac_pose with ransac={...})
+  homography_pose  the same RANSAC with a homography as its model, for walls, floors and pure rotations, where the essential
+                matrix is under-determined: cpn_ransac_homographies / _score_h / _finish_h, three launches; with it the twin
+                pose, the singular values of H and the statistics that say which regime a pair is in
+  from_pair     get_z once, then the three above (ransac_pose with ransac={...}, homography_pose with homography={...})
   photo_coords  host: matches of a prepare_pair dict in the coordinates of the original photos
 
 The conventions and the arithmetic are in include/coponerf_hip.h (round 16).  The selection defaults (cycle error up to 10
@@ -28,6 +31,14 @@ are as untried on a trained checkpoint; the linear 8-point solver is degenerate 
 solver="5pt" (round 21 of the header) is not degenerate on a plane - a wall, a floor -, where the 8-point solver returns a wrong
 pose with as many inliers as the true one; a purely planar scene keeps a two-fold ambiguity that only the vote on the depths
 breaks, and a pure rotation gives E = 0 for either solver.
+
+homography_pose (round 22 of the header) is the model of exactly those cases: one plane, or no baseline.  It returns a pose where
+the essential-matrix solvers cannot - on the wall with 64 samples, where the 5-point solver's winner is 10.3, 50.7 degrees off, its
+pose is 1.0, 3.2 degrees off and the wrong one is returned beside it as `twin` -, few inliers where the scene is not planar (39
+against the 8-point solver's 684 on the curved scene: the planarity verdict), and sigma_1 - sigma_3 of H, the baseline over the
+plane's distance, which says "no baseline".  Its transfer-error inlier rule, its visibility vote, its pick order and min_baseline
+with its default are this package's definitions and untried on a trained checkpoint; a fronto-parallel plane in a narrow field of
+view can leave the vote tied, and stats[4..7] then says so.
 """
 from __future__ import annotations
 
@@ -259,7 +270,71 @@ def ransac_pose(matches: Matches, intrinsics: torch.Tensor, rel_pose: Optional[t
     return {"pose": pose, "inlier": inlier, "stats": stats}
 
 
+@torch.no_grad()
+def homography_pose(matches: Matches, intrinsics: torch.Tensor, rel_pose: Optional[torch.Tensor] = None, hypotheses: int = 1024,
+                    inlier_px: float = 1.0, seed: int = 0, min_baseline: float = 0.0) -> Dict[str, torch.Tensor]:
+    """cpn_ransac_homographies, cpn_ransac_score_h, cpn_ransac_finish_h (round 22 of the header): the RANSAC of ransac_pose with
+    a homography a ~ H b as its model, for the pairs that one plane (a wall, a floor) or a pure rotation explains, where the
+    essential matrix is under-determined.  `hypotheses` samples of 4 matches - the first 4 of ransac_pose's sample of the same
+    index -, each H scored by the matches whose transfer error is within inlier_px in BOTH views, the best decomposed into its
+    four (R, T, N); the winner's inliers vote on the side of the plane (it must lie in front of the camera), and the Sampson
+    inliers of E = [T]x R under ransac_pose's own rule break a tie.  float64 inside, three launches for all pairs, nothing read on
+    the host -> `pose` (B, 4, 4) fp32 = [R | s T / |T|] with s as in ransac_pose; `twin` (B, 4, 4) fp32, the better-voted pose of
+    the other solution family - on a wall the pose the 8-point and the few-sample 5-point solver fall into -; `H` (B, 9)
+    float64, the winner with sigma_2 = 1 and det > 0; `inlier` (B, N) uint8; `stats` (B, 12) float64: [0] the winner's inliers,
+    [1] usable matches, [2] the winner's index, [3] valid hypotheses, [4], [5] the votes of the pose and of the twin, [6], [7]
+    the Sampson inliers of their essential matrices, [8] sigma_1 / sigma_2, [9] sigma_3 / sigma_2, [10] sigma_1 - sigma_3 = the
+    baseline over the plane's distance, [11] the status: 0 ok, 1 no valid hypothesis, 2 nothing to do (fewer than 4 usable matches
+    or hypotheses == 0; pose is rel_pose, or the identity without one), 3 rotation only ([10] <= min_baseline: pose = twin =
+    [R | 0] with R the rotation nearest to H).  [4] = [5] and [6] = [7] say that the ambiguity was not resolved - a fronto-parallel
+    plane in a narrow field of view can do that -; [0] against ransac_pose's stats[0] is the planarity verdict.
+    rel_pose is only measured against, never searched from.  The transfer-error rule, the vote, the pick order and min_baseline
+    are this package's definitions and untried on a trained checkpoint; min_baseline = 0.0 means "only an exactly rotation-only H
+    gets status 3", and where to set it for real data is unknown."""
+    xy, count = matches.xy, matches.count
+    named = [("matches.xy", xy, torch.float32, None), ("intrinsics", intrinsics, torch.float32, None)]
+    if rel_pose is not None:
+        named.append(("rel_pose", rel_pose, torch.float32, None))
+    device_tensors("homography_pose", tuple(named))
+    B, N = _matches_args("homography_pose", matches)
+    _cameras("homography_pose", intrinsics, rel_pose, B)
+    Hn, px, seed, base = int(hypotheses), float(inlier_px), int(seed), float(min_baseline)
+    chunks = -(-N // _hip.CONSTANTS["RANSAC_CHUNK"])
+    if not 0 <= Hn <= 2 ** 20 or not 1 <= B <= 32767 or N > 2 ** 24 or B * chunks * (Hn + 1) >= 2 ** 31:
+        raise ValueError(f"homography_pose: need 0 <= hypotheses <= 2^20, 1 <= B <= 32767, N <= 2^24 and B ceil(N / "
+                         f"{_hip.CONSTANTS['RANSAC_CHUNK']}) (hypotheses + 1) < 2^31, got hypotheses = {hypotheses}, B = {B}, N = {N}")
+    if not 0.0 <= px < float("inf"):
+        raise ValueError(f"homography_pose: need a finite inlier_px >= 0, got {inlier_px}")
+    if not 0.0 <= base < float("inf"):
+        raise ValueError(f"homography_pose: need a finite min_baseline >= 0, got {min_baseline}")
+    if not -2 ** 63 <= seed < 2 ** 63:
+        raise ValueError(f"homography_pose: seed must fit 64 bits, got {seed}")
+    dev = xy.device
+    Hm = torch.empty(B, max(Hn, 1), 9, dtype=torch.float64, device=dev)
+    sample = torch.empty(B, max(Hn, 1), 4, dtype=torch.int32, device=dev)
+    valid = torch.empty(B, max(Hn, 1), dtype=torch.uint8, device=dev)
+    partial = torch.empty(B, chunks, max(Hn, 1), dtype=torch.int32, device=dev)
+    pose = torch.empty(B, 4, 4, dtype=torch.float32, device=dev)
+    twin = torch.empty(B, 4, 4, dtype=torch.float32, device=dev)
+    Hout = torch.empty(B, 9, dtype=torch.float64, device=dev)
+    inlier = torch.empty(B, N, dtype=torch.uint8, device=dev)
+    stats = torch.empty(B, 12, dtype=torch.float64, device=dev)
+    rel = 0 if rel_pose is None else rel_pose.data_ptr()
+    with torch.cuda.device(dev):
+        s = _hip.stream_handle()
+        if Hn:
+            _hip.call("cpn_ransac_homographies", xy.data_ptr(), count.data_ptr(), intrinsics.data_ptr(), B, N, Hn, seed, Hm.data_ptr(),
+                      sample.data_ptr(), valid.data_ptr(), s)
+            _hip.call("cpn_ransac_score_h", Hm.data_ptr(), valid.data_ptr(), xy.data_ptr(), count.data_ptr(), intrinsics.data_ptr(), B, N,
+                      Hn, px, partial.data_ptr(), s)
+        _hip.call("cpn_ransac_finish_h", Hm.data_ptr(), valid.data_ptr(), partial.data_ptr(), xy.data_ptr(), count.data_ptr(),
+                  intrinsics.data_ptr(), rel, B, N, Hn, px, base, pose.data_ptr(), twin.data_ptr(), Hout.data_ptr(), inlier.data_ptr(),
+                  stats.data_ptr(), s)
+    return {"pose": pose, "twin": twin, "H": Hout, "inlier": inlier, "stats": stats}
+
+
 _STARTS = ("network", "ransac", "best")
+_H_STARTS = ("network", "homography")
 _SOLVERS = ("8pt", "5pt")
 
 
@@ -278,17 +353,40 @@ def _ransac_keywords(who: str, ransac: Dict) -> Tuple[Dict, str]:
     return kw, start
 
 
+def _homography_keywords(who: str, homography: Dict) -> Tuple[Dict, str]:
+    if not isinstance(homography, dict):
+        raise ValueError(f"{who}: homography must be None or a dict of homography_pose's keywords and `start`, got "
+                         f"{type(homography).__name__}")
+    kw = dict(homography)
+    start = kw.pop("start", "network")
+    if start not in _H_STARTS:
+        raise ValueError(f"{who}: homography['start'] must be one of {_H_STARTS}, got {start!r}")
+    unknown = set(kw) - {"hypotheses", "inlier_px", "seed", "min_baseline"}
+    if unknown:
+        raise ValueError(f"{who}: homography holds unknown keywords {sorted(unknown)}")
+    return kw, start
+
+
 @torch.no_grad()
 def from_flows(flow: Sequence[torch.Tensor], intrinsics: torch.Tensor, rel_pose: torch.Tensor, S: int = 256, refine: bool = True,
                max_cycle_px: float = 10.0, max_epi_px: Optional[float] = None, stride: int = 4, iters: int = 10,
-               scale_px: float = 2.0, ransac: Optional[Dict] = None) -> Dict:
+               scale_px: float = 2.0, ransac: Optional[Dict] = None, homography: Optional[Dict] = None) -> Dict:
     """from_pair's second half, for flows and a pose that get_z has already returned: four launches and the mask between them,
     no host read.  ransac: None, or a dict of ransac_pose's keywords (hypotheses, inlier_px, seed, solver) and `start`: three more
     launches, and the result gains the key `ransac` (ransac_pose's dict).  start="network" (the default) refines from rel_pose
     as without it, "ransac" from RANSAC's pose, "best" per pair from the one with more inliers under ransac_pose's rule (a tie
-    and a status other than 0 go to rel_pose; chosen by torch.where on the device)."""
+    and a status other than 0 go to rel_pose; chosen by torch.where on the device).
+    homography: None, or a dict of homography_pose's keywords (hypotheses, inlier_px, seed, min_baseline) and `start`: three more
+    launches, and the result gains the key `homography` (homography_pose's dict).  start="homography" refines from its pose where
+    its status is 0 and from rel_pose elsewhere (torch.where on the device); a start other than "network" in both dicts is a
+    ValueError.  Without the keyword nothing changes: no launch, no key."""
     if ransac is not None:
         ransac_kw, start = _ransac_keywords("from_flows", ransac)
+    if homography is not None:
+        homography_kw, h_start = _homography_keywords("from_flows", homography)
+        if h_start != "network" and ransac is not None and start != "network":
+            raise ValueError(f"from_flows: ransac['start'] = {start!r} and homography['start'] = {h_start!r} both name a start; "
+                             "one of them must be \"network\"")
     fields = match_fields(flow, intrinsics, rel_pose, S)
     matches = select(fields, max_cycle_px=max_cycle_px, max_epi_px=max_epi_px, stride=stride)
     result = {"matches": matches, "rel_pose": rel_pose, "pose": None, "stats": None, "fields": fields}
@@ -301,6 +399,10 @@ def from_flows(flow: Sequence[torch.Tensor], intrinsics: torch.Tensor, rel_pose:
         elif start == "best":
             better = (st[:, 7] == 0) & (st[:, 0] > st[:, 4])
             begin = torch.where(better[:, None, None], found["pose"], rel_pose)
+    if homography is not None:
+        plane = result["homography"] = homography_pose(matches, intrinsics, rel_pose, **homography_kw)
+        if h_start == "homography":
+            begin = torch.where((plane["stats"][:, 11] == 0)[:, None, None], plane["pose"], rel_pose)
     if refine:
         result.update(refine_pose(matches, intrinsics, begin, iters=iters, scale_px=scale_px))
     return result
@@ -311,7 +413,7 @@ def from_pair(model, model_input: Dict, S: int = 256, refine: bool = True, **sel
     """The matches of the pair(s) in model_input (prepare_pair's dict, or any dict get_z takes).  get_z runs once; its flows
     and its rel_pose - the ones novel_views.render_path hands on - go through match_fields, select and, with refine=True,
     refine_pose.  Keywords: select's max_cycle_px, max_epi_px, stride, refine_pose's iters, scale_px and from_flows' ransac
-    (with a dict the result gains the key `ransac`).  Returns `matches` (a
+    and homography (with a dict the result gains the key `ransac` or `homography`).  Returns `matches` (a
     Matches), `rel_pose` (B, 4, 4) as estimated, `pose` and `stats` as refine_pose returns them (None with refine=False) and
     `fields`, match_fields' dict.  Nothing is read on the host; Matches.numpy is the read."""
     _, rel_pose, flow = model.get_z(model_input)

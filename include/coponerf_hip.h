@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define CPN_ABI_VERSION 12   /* cpn_attend_units (round 7), cpn_ssim_warp* (round 8), cpn_image_metrics* (round 9), summaries.hip (round 10), lpips.hip (round 11), novel_views.hip (round 12), epipolar.hip (round 13), cpn_lpips_*_bwd (round 14), point_cloud.hip (round 15), matches.hip (round 16), splat.hip (round 17), mesh.hip (round 18), raster.hip (round 19), ransac.hip (round 20) and ransac5.hip (round 21) are additive - symbols added, none altered: the version stays */
+#define CPN_ABI_VERSION 12   /* cpn_attend_units (round 7), cpn_ssim_warp* (round 8), cpn_image_metrics* (round 9), summaries.hip (round 10), lpips.hip (round 11), novel_views.hip (round 12), epipolar.hip (round 13), cpn_lpips_*_bwd (round 14), point_cloud.hip (round 15), matches.hip (round 16), splat.hip (round 17), mesh.hip (round 18), raster.hip (round 19), ransac.hip (round 20), ransac5.hip (round 21) and ransac_h.hip (round 22) are additive - symbols added, none altered: the version stays */
 
 #define CPN_E_ARG   (-1)   /* bad argument (null pointer, size, alignment) */
 #define CPN_E_SHAPE (-2)   /* shape not supported by the compiled tiles    */
@@ -1197,6 +1197,69 @@ int cpn_ransac_finish(const double* E, const uint8_t* valid, const int* partial,
  *   element of the three outputs is written.  No atomics: bit-reproducible, and a pair's result does not depend on the batch. */
 int cpn_ransac_hypotheses5(const float* xy, const int* count, const float* intrinsics, int B, int N, int Hn, long long seed,
                            double* E, int* sample, uint8_t* valid, void* stream);
+
+/* ==== the homography model for round 20's RANSAC: walls and pure rotations (round 22) ======================================
+ * Where one plane or a pure rotation explains the matches the essential matrix is under-determined; the model of that case is
+ * a homography.  Three additive symbols: the ABI version stays.  The same three-launch shape as round 20, no atomics, nothing read
+ * on the host, bit-reproducible, and a pair's result does not depend on the batch.  Conventions, the draw, the elimination, the
+ * one-sided Jacobi method and the shape limits: round 20's (1 <= B <= 32767, 1 <= N <= 2^24, Hn <= 2^20 and
+ * B ceil(N / CPN_RANSAC_CHUNK) (Hn + 1) < 2^31, CPN_E_SHAPE otherwise; inlier_px and min_baseline finite and >= 0, CPN_E_ARG
+ * otherwise).  a ~ H b, with H = R + t n^T / d for the plane n . X1 = d in view 1's frame; H (.., 9) float64 row-major.  THE
+ * TRANSFER-ERROR INLIER RULE, THE VISIBILITY VOTE, THE PICK ORDER AND min_baseline ARE THIS LIBRARY'S definitions; none of them has
+ * been tried on a trained checkpoint.  All float64, one rounding per operation, only + - * / sqrt and comparisons.
+ * adj(M), the adjugate, row-major: (M4 M8 - M5 M7, M2 M7 - M1 M8, M1 M5 - M2 M4, M5 M6 - M3 M8, M0 M8 - M2 M6, M2 M3 - M0 M5,
+ *   M3 M7 - M4 M6, M1 M6 - M0 M7, M0 M4 - M1 M3); det M = (M0 adj0 + M1 adj3) + M2 adj6.  M p for a point p = (p0, p1, 1):
+ *   component i is (M_i0 p0 + M_i1 p1) + M_i2.
+ * THE INLIER RULE: with m = H b and w = adj(H) a, a match is an inlier of H iff m_2 > 0, m_2 is finite,
+ *   d0 = sqrt(dx dx + dy dy) with dx = fx0 (m_0 / m_2 - a0), dy = fy0 (m_1 / m_2 - a1) is finite and d0 <= inlier_px, and the
+ *   same holds for w against b in view 1's pixels (w_2 > 0 and finite, fx1 (w_0 / w_2 - b0), fy1 (w_1 / w_2 - b1)).
+ * cpn_ransac_homographies (Hn >= 1): ONE launch, one thread per (pair, hypothesis index h).
+ *   The draw is round 20's stopped at 4 distinct rows: for equal (seed, h, n) they are the first 4 of cpn_ransac_hypotheses' 8.
+ *   The hypothesis is invalid after 64 draws without 4 distinct indices (always so for n < 4) and where one of the four values
+ *   of a sampled row is not finite.  sample (B, Hn, 4) int32: the indices in the order drawn, -1 where none was.
+ *   The system: sampled match j gives rows 2 j = (b0, b1, 1, 0, 0, 0, -(a0 b0), -(a0 b1), -a0) and
+ *   2 j + 1 = (0, 0, 0, b0, b1, 1, -(a1 b0), -(a1 b1), -a1) of an 8 x 9 matrix.  Its null vector x: round 20's elimination with
+ *   complete pivoting, its RANK TEST |p_k| > 1e-9 |p_0| (three collinear points and repeated matches fail it) and its back
+ *   substitution.  H = x / sqrt((x_0^2 + x_1^2) + .. + x_8^2), negated where det H < 0.  The hypothesis is invalid also where
+ *   det H is not finite or not > 0, where a value of H is not finite, and where one of its own four matches has (H b)_2 <= 0 or
+ *   (adj(H) a)_2 <= 0: such a homography maps its own sample behind a camera.  H (B, Hn, 9) float64, all 0 where invalid; valid
+ *   (B, Hn) bytes 0 / 1.  Every element of the three outputs is written.
+ * cpn_ransac_score_h: ONE launch, cpn_ransac_score's grid and tiling over Hn slots (there is no slot for rel_pose: a pose has no
+ *   homography without a plane).  partial (B, ceil(N / CPN_RANSAC_CHUNK), Hn) int32: the inliers of hypothesis h among the
+ *   chunk's rows below n; 0 for an invalid hypothesis and for a chunk at or beyond n.  Every element is written.  Hn may be 0
+ *   (nothing is launched, H, valid and partial are not read).
+ * cpn_ransac_finish_h: ONE launch, one workgroup per pair.  usable and the WINNER as in cpn_ransac_finish.  Round 20's Jacobi
+ *   method on G = H with V = 1 and its ordering give the column norms sg_0 >= sg_1 >= sg_2; its frames give u_1, u_2, u_3 from G
+ *   and v_1, v_2, v_3 = v_1 x v_2 from V.  s1 = sg_0 / sg_1, s3 = sg_2 / sg_1, Hs = H / sg_1 entry by entry.
+ *   ROTATION ONLY where s1 s1 - s3 s3 is not > 0 or s1 - s3 <= min_baseline: the pose is [R_n | 0] with
+ *   R_n = (u_1 v_1^T + u_2 v_2^T) + u_3 v_3^T, the rotation nearest to H; twin = pose; status 3.  s1 - s3 is the baseline over
+ *   the plane's distance, |T| below; where to set min_baseline for real data is unknown, and 0 means "only an exact rotation".
+ *   Otherwise THE FOUR CANDIDATES (Ma, Soatto, Kosecka, Sastry, section 5.3): x1 = sqrt(max(1 - s3 s3, 0)),
+ *   x3 = sqrt(max(s1 s1 - 1, 0)), den = sqrt(s1 s1 - s3 s3); for k = 0, 1: u = (x1 v_1 + x3 v_3) / den (k = 0) or
+ *   (x1 v_1 - x3 v_3) / den (k = 1) component by component; N = v_2 x u; p = Hs v_2, q = Hs u (row sums
+ *   (Hs_i0 x_0 + Hs_i1 x_1) + Hs_i2 x_2), r = p x q; R_ij = (p_i v_2j + q_i u_j) + r_i N_j;
+ *   T_i = ((Hs_i0 - R_i0) N_0 + (Hs_i1 - R_i1) N_1) + (Hs_i2 - R_i2) N_2; Hs = R + T N^T.  Candidate 2 k is (R, T, N), candidate
+ *   2 k + 1 is (R, -T, -N).  E_k = [T]x R in round 16's expression.
+ *   THE VOTE: every inlier of the winner (under H as it was scored), with nb = (N_0 b0 + N_1 b1) + N_2, votes for candidate 2 k
+ *   where nb > 0 and for 2 k + 1 where nb < 0: the plane must lie in front of camera 1.  samp_k = the rows below n that are
+ *   inliers of E_k under cpn_ransac_score's rule with the same inlier_px.  THE PICK: the candidate with the most votes; on a tie
+ *   the one with the larger samp_k; on a tie the lower index.  THE TWIN: of the other k, the candidate with more votes, the even
+ *   one on a tie.  A fronto-parallel plane in a narrow field of view can leave the vote tied: stats [4] = [5] and [6] = [7] then
+ *   say that the ambiguity was not resolved.
+ *   pose, twin (B, 4, 4) fp32 = [R | s (+-T / |T|)], |T| = sqrt((T_0^2 + T_1^2) + T_2^2), s as in cpn_ransac_finish (rel_pose is
+ *   only measured against).  Hout (B, 9) float64 = Hs (sigma_2 = 1, det > 0).  inlier (B, N) bytes: the inliers of the winner,
+ *   0 elsewhere and at and beyond n; every byte is written.  stats (B, 12) float64: [0] the winner's inliers; [1] usable; [2] the
+ *   winner's index; [3] valid hypotheses; [4] votes of the pose; [5] votes of the twin; [6] samp of the pose; [7] samp of the
+ *   twin; [8] s1; [9] s3; [10] s1 - s3; [11] the status: 0 ok; 1 no valid hypothesis or a decomposition that is not finite: pose
+ *   and twin are rel_pose's 16 values, or the identity without one, Hout and inlier 0, [1] usable, the rest 0; 2 nothing to do
+ *   (usable < 4 or Hn == 0): as status 1 with [1] = 0; 3 rotation only: [0] .. [3] and [8] .. [10] as for status 0, [4] .. [7] 0. */
+int cpn_ransac_homographies(const float* xy, const int* count, const float* intrinsics, int B, int N, int Hn, long long seed,
+                            double* H, int* sample, uint8_t* valid, void* stream);
+int cpn_ransac_score_h(const double* H, const uint8_t* valid, const float* xy, const int* count, const float* intrinsics, int B,
+                       int N, int Hn, double inlier_px, int* partial, void* stream);
+int cpn_ransac_finish_h(const double* H, const uint8_t* valid, const int* partial, const float* xy, const int* count,
+                        const float* intrinsics, const float* rel_pose, int B, int N, int Hn, double inlier_px,
+                        double min_baseline, float* pose, float* twin, double* Hout, uint8_t* inlier, double* stats, void* stream);
 
 #ifdef __cplusplus
 }

@@ -22,9 +22,18 @@ refine_pose still converges from it: what it does with outliers is tests/test_ra
       and with every slot invalid (the launch's fixed part); ransac_pose(solver="5pt") at HN and at HN / 4 samples and
       from_flows with it, beside the 8-point figures of (a); and what came out.
 
+  (e) the homography model (csrc/ransac_h.hip) in the same process, written to --outh, on the curved pairs of
+      (a) and on two pairs of about 6 000 exact matches on a wall in buffers of the same N rows: its three kernels; the score
+      kernel once more with every slot declared valid (the 8-point score kernel of (a) has nearly every slot to count, the
+      homographies' own validity leaves about half: this is the like-for-like figure, and its ratio to (a)'s is recorded);
+      homography_pose as a whole beside ransac_pose 8-point and 5-point on the same Matches; the same rule from stock operators
+      (batched torch.linalg.svd null vectors of the kernel's own samples, an (Hn, n) float64 transfer-error matrix in both
+      views, argmax); and what came out of all three models.
+
 There is no pass / fail time: the numbers are recorded.
 
     python tools/ransac_time.py [--rounds 5] [--iters 20] [--out profiles/r20_ransac.json] [--out5 profiles/r21_ransac5.json]
+                                [--outh profiles/r22_homography.json]
 """
 import argparse
 import json
@@ -150,12 +159,123 @@ def five_point(m, flows, intr, pose, true, counts, sel, args, eight):
     return out
 
 
+def wall_matches(dev, N, n=6000):
+    """B pairs of about n exact matches on the plane (0.25, -0.1, 1) . X0 = 3 seen by curved_pairs' cameras, in N-row buffers
+    -> (Matches, true (B, 4, 4) float64 on the host)."""
+    gen = torch.Generator().manual_seed(22)
+    xy, counts, Pt = torch.zeros(B, N, 4, dtype=torch.float64), [], []
+    for b in range(B):
+        f = 210.0 + 15.0 * b
+        R, t = rodrigues((0.2, 1.0, 0.1), 7.0 + 2.0 * b), torch.tensor([0.45, 0.04, 0.1 + 0.05 * b], dtype=torch.float64)
+        p0 = torch.rand(n, 2, generator=gen, dtype=torch.float64) * S
+        ray = torch.cat(((p0 - S / 2) / f, torch.ones(n, 1, dtype=torch.float64)), 1)
+        depth = 3.0 / (ray @ torch.tensor([0.25, -0.1, 1.0], dtype=torch.float64))
+        X1 = (ray * depth[:, None] - t) @ R
+        p1 = f * X1[:, :2] / X1[:, 2:] + S / 2
+        keep = ((p1 >= 0) & (p1 <= S - 1)).all(1)
+        rows = torch.cat((p0, p1), 1)[keep]
+        xy[b, :len(rows)] = rows
+        counts.append(len(rows))
+        true = torch.eye(4, dtype=torch.float64)
+        true[:3, :3], true[:3, 3] = R, t
+        Pt.append(true)
+    return mt.Matches(xy.float().contiguous().to(dev), None, torch.tensor(counts, dtype=torch.int32, device=dev)), torch.stack(Pt), counts
+
+
+def stock_homography(xy, counts, intr, sample, px=PX):
+    """homography_pose's rule from stock operators, one pair after the other -> (winner index, winner count) per pair, on the
+    device: the 8 x 9 systems of the kernel's own samples, their null vectors by a batched torch.linalg.svd, an (Hn, n) float64
+    transfer-error matrix in both views, the counts and argmax.  (It does not drop the hypotheses that map their own sample
+    behind a camera: they count few inliers.)"""
+    out = []
+    for b, n in enumerate(counts):
+        rows = xy[b, :n].double()
+        k0, k1 = intr[b, 0].double(), intr[b, 1].double()
+        a = torch.stack(((rows[:, 0] - k0[0, 2]) / k0[0, 0], (rows[:, 1] - k0[1, 2]) / k0[1, 1], torch.ones_like(rows[:, 0])), -1)
+        bb = torch.stack(((rows[:, 2] - k1[0, 2]) / k1[0, 0], (rows[:, 3] - k1[1, 2]) / k1[1, 1], torch.ones_like(rows[:, 0])), -1)
+        f0, f1 = torch.stack((k0[0, 0], k0[1, 1])), torch.stack((k1[0, 0], k1[1, 1]))
+        idx = sample[b].long()
+        sa, sb = a[idx], bb[idx]                                    # (Hn, 4, 3)
+        zero = torch.zeros_like(sb)
+        A = torch.stack((torch.cat((sb, zero, -sa[..., 0:1] * sb), -1), torch.cat((zero, sb, -sa[..., 1:2] * sb), -1)), 2).reshape(-1, 8, 9)
+        Hm = torch.linalg.svd(A, full_matrices=True)[2][:, 8].reshape(-1, 3, 3)
+        Hm = Hm * torch.sign(torch.linalg.det(Hm))[:, None, None]
+        Hb, Ga = torch.einsum("hij,nj->hni", Hm, bb), torch.einsum("hij,nj->hni", torch.linalg.inv(Hm), a)
+        d0 = ((Hb[..., :2] / Hb[..., 2:] - a[None, :, :2]) * f0).norm(dim=-1)
+        d1 = ((Ga[..., :2] / Ga[..., 2:] - bb[None, :, :2]) * f1).norm(dim=-1)
+        cnt = ((Hb[..., 2] > 0) & (Ga[..., 2] > 0) & (d0 <= px) & (d1 <= px)).sum(1)
+        win = cnt.argmax()
+        out.append(torch.stack((win, cnt[win])))
+    return torch.stack(out)
+
+
+def homography(m, intr, pose, true, counts, args, other):
+    """(e) of the module's docstring -> the dict written to --outh; `other` holds the 8-point and 5-point figures of this process."""
+    dev, N = intr.device, int(m.xy.shape[1])
+    chunks = -(-N // _hip.CONSTANTS["RANSAC_CHUNK"])
+    wall, wall_true, wall_counts = wall_matches(dev, N)
+    s = _hip.stream_handle()
+    K, P = intr.data_ptr(), pose.data_ptr()
+    out = {"rows_per_pair_N": N, "matches_per_pair": {"curved": counts, "wall": wall_counts}, "kernels": {}, "calls": {}, "result": {}}
+
+    def off(Pm, truth):
+        return [[angle_deg(Pm[b, :3, :3].double().cpu(), truth[b, :3, :3].double().cpu()),
+                 dir_deg(Pm[b, :3, 3].double().cpu(), truth[b, :3, 3].double().cpu())] for b in range(B)]
+    for name, mm, truth, cnts in (("curved", m, true, counts), ("wall", wall, wall_true, wall_counts)):
+        Hm = torch.empty(B, HN, 9, dtype=torch.float64, device=dev)
+        sample = torch.empty(B, HN, 4, dtype=torch.int32, device=dev)
+        valid = torch.empty(B, HN, dtype=torch.uint8, device=dev)
+        partial = torch.empty(B, chunks, HN, dtype=torch.int32, device=dev)
+        po, tw = torch.empty(B, 4, 4, device=dev), torch.empty(B, 4, 4, device=dev)
+        Ho, st = torch.empty(B, 9, dtype=torch.float64, device=dev), torch.empty(B, 12, dtype=torch.float64, device=dev)
+        inl = torch.empty(B, N, dtype=torch.uint8, device=dev)
+        xy, cn = mm.xy.data_ptr(), mm.count.data_ptr()
+        kernels = {
+            "ransac_homographies_ms": lambda: _hip.call("cpn_ransac_homographies", xy, cn, K, B, N, HN, SEED, Hm.data_ptr(), sample.data_ptr(),
+                                                        valid.data_ptr(), s),
+            "ransac_score_h_ms": lambda: _hip.call("cpn_ransac_score_h", Hm.data_ptr(), valid.data_ptr(), xy, cn, K, B, N, HN, PX,
+                                                   partial.data_ptr(), s),
+            "ransac_finish_h_ms": lambda: _hip.call("cpn_ransac_finish_h", Hm.data_ptr(), valid.data_ptr(), partial.data_ptr(), xy, cn, K, P, B,
+                                                    N, HN, PX, 0.0, po.data_ptr(), tw.data_ptr(), Ho.data_ptr(), inl.data_ptr(), st.data_ptr(), s)}
+        out["kernels"][name] = {k: windows(fn, args.rounds, args.iters) for k, fn in kernels.items()}
+        # the slots with something to count decide the score kernel's time: the same kernel with every slot valid, the invalid
+        # ones filled with copies of the valid ones
+        order = torch.argsort(valid, dim=1, descending=True, stable=True)
+        nv = valid.sum(1, keepdim=True).clamp(min=1).long()
+        pick = torch.gather(order, 1, torch.arange(HN, device=dev)[None].expand(B, -1) % nv)
+        Hall, every = torch.gather(Hm, 1, pick[..., None].expand(-1, -1, 9)).contiguous(), torch.ones_like(valid)
+        out["kernels"][name]["ransac_score_h_every_slot_valid_ms"] = windows(
+            lambda: _hip.call("cpn_ransac_score_h", Hall.data_ptr(), every.data_ptr(), xy, cn, K, B, N, HN, PX, partial.data_ptr(), s),
+            args.rounds, args.iters)
+        forms = {"homography_pose_ms": lambda: mt.homography_pose(mm, intr, pose, HN, PX, SEED),
+                 "ransac_pose_8pt_ms": lambda: mt.ransac_pose(mm, intr, pose, HN, PX, SEED),
+                 "ransac_pose_5pt_ms": lambda: mt.ransac_pose(mm, intr, pose, HN, PX, SEED, solver="5pt"),
+                 "stock_homography_ms": lambda: stock_homography(mm.xy, cnts, intr, sample)}
+        out["calls"][name] = {k: windows(fn, args.rounds, args.iters if "stock" not in k else max(args.iters // 4, 2))
+                              for k, fn in forms.items()}
+        got = mt.homography_pose(mm, intr, pose, HN, PX, SEED)
+        eight, five = mt.ransac_pose(mm, intr, pose, HN, PX, SEED), mt.ransac_pose(mm, intr, pose, HN, PX, SEED, solver="5pt")
+        out["result"][name] = {"homography_stats": [[float(v) for v in row] for row in got["stats"].cpu()],
+                               "valid_hypotheses": [int(v) for v in valid.sum(1).cpu()],
+                               "stock_winner_and_count": stock_homography(mm.xy, cnts, intr, sample).cpu().tolist(),
+                               "inliers_8pt_5pt": [[float(eight["stats"][b, 0]), float(five["stats"][b, 0])] for b in range(B)],
+                               "degrees_from_truth": {"homography": off(got["pose"], truth), "twin": off(got["twin"], truth),
+                                                      "ransac_8pt": off(eight["pose"], truth), "ransac_5pt": off(five["pose"], truth)}}
+    # the score kernels on the same matches and the same number of slots with something to count: (nearly) all HN for the
+    # 8-point solver on the curved pairs, all HN here once every slot is declared valid
+    out["score_h_every_slot_over_score_8pt"] = round(out["kernels"]["curved"]["ransac_score_h_every_slot_valid_ms"]["median"] /
+                                                     other["eight_point"]["kernels"]["ransac_score_ms"]["median"], 3)
+    out["eight_and_five_point_same_process"] = other
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--out", default=None)
     ap.add_argument("--out5", default=None)
+    ap.add_argument("--outh", default=None)
     args = ap.parse_args()
     assert torch.cuda.is_available(), "ransac_time.py measures on a HIP device"
     dev = torch.device("cuda:0")
@@ -215,7 +335,13 @@ def main():
     res5 = dict({k: res[k] for k in ("device", "pairs", "side", "flow_side", "hypotheses", "inlier_px", "seed", "rounds", "iters", "ms")},
                 **five_point(m, (f0, f1), intr, pose, true, counts, sel, args, {"kernels": res["kernels"], "calls": res["calls"]}))
     print(json.dumps(res5, indent=1))
-    for path, what in ((args.out, res), (args.out5, res5)):
+    resh = dict({k: res[k] for k in ("device", "pairs", "side", "flow_side", "hypotheses", "inlier_px", "seed", "rounds", "iters", "ms")},
+                **homography(m, intr, pose, true, counts, args,
+                             {"eight_point": {"kernels": res["kernels"], "calls": res["calls"],
+                                              "valid_hypotheses": res["result"]["valid_hypotheses"]},
+                              "five_point": {"kernels": res5["kernels"], "calls": res5["calls"]}}))
+    print(json.dumps(resh, indent=1))
+    for path, what in ((args.out, res), (args.out5, res5), (args.outh, resh)):
         if path:
             with open(path, "w") as f:
                 json.dump(what, f, indent=1)
