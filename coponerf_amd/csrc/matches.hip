@@ -16,12 +16,15 @@
 // The residual is float64 from the fp32 inputs, one rounding per operation (-ffp-contract=off), sums left to right:
 // tests/matches_ref.py restates all three in numpy.  Cam and Pose are pinhole.h's; essential, sampson and residual_ok are sampson.h's,
 // the use of rel_pose and the pose written out pose_out.h's, the count clamp ransac_common.h's: ransac.hip shares all three.
+// cross_rows and the Rodrigues step are rotation_step.h's and the Cholesky solve cholesky_solve.h's: model_select.hip shares both.
+#include "cholesky_solve.h"
 #include "common.h"
 #include "compact.h"
 #include "flow_warp.h"
 #include "pinhole.h"
 #include "pose_out.h"
 #include "ransac_common.h"
+#include "rotation_step.h"
 #include "sampson.h"
 
 #include <math.h>
@@ -123,15 +126,6 @@ struct RefineState {
     int go;                         // another pass follows
 };
 
-// rows of [e_k]x R
-__device__ __forceinline__ void cross_rows(const double* R, int k, double* M) {
-    const int k1 = (k + 1) % 3, k2 = (k + 2) % 3;
-    for (int j = 0; j < 3; ++j) {
-        M[3 * k + j] = 0.0;
-        M[3 * k1 + j] = -R[3 * k2 + j];
-        M[3 * k2 + j] = R[3 * k1 + j];
-    }
-}
 __device__ void set_matrices(RefineState& st) {
     essential(st.R, st.t, st.E);
     for (int k = 0; k < 3; ++k) {
@@ -140,52 +134,10 @@ __device__ void set_matrices(RefineState& st) {
     }
 }
 
-// delta = -A^-1 g by Cholesky (A = L L^T, lower); false where a pivot is not positive or a value not finite
-__device__ bool solve6(double (&A)[6][6], const double (&g)[6], double (&x)[6]) {
-    for (int j = 0; j < 6; ++j) {
-        double s = A[j][j];
-        for (int k = 0; k < j; ++k) s -= A[j][k] * A[j][k];
-        if (!(s > 0.0) || !finite64(s)) return false;
-        const double l = sqrt(s);
-        A[j][j] = l;
-        for (int i = j + 1; i < 6; ++i) {
-            double v = A[i][j];
-            for (int k = 0; k < j; ++k) v -= A[i][k] * A[j][k];
-            A[i][j] = v / l;
-        }
-    }
-    double y[6];
-    for (int i = 0; i < 6; ++i) {
-        double v = -g[i];
-        for (int k = 0; k < i; ++k) v -= A[i][k] * y[k];
-        y[i] = v / A[i][i];
-    }
-    for (int i = 5; i >= 0; --i) {
-        double v = y[i];
-        for (int k = i + 1; k < 6; ++k) v -= A[k][i] * x[k];
-        x[i] = v / A[i][i];
-    }
-    for (int i = 0; i < 6; ++i)
-        if (!finite64(x[i])) return false;
-    return true;
-}
-
 // R <- exp([w]x) R (Rodrigues; the identity below 1e-12), t <- (t + dt) / |t + dt|; false (state untouched) where not finite
 __device__ bool apply_step(RefineState& st, const double (&x)[6]) {
-    const double th = sqrt((x[0] * x[0] + x[1] * x[1]) + x[2] * x[2]);
-    double Q[9] = {1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0};
-    if (th >= 1e-12) {
-        const double k0 = x[0] / th, k1 = x[1] / th, k2 = x[2] / th, s = sin(th), c = 1.0 - cos(th);
-        const double K[9] = {0.0, -k2, k1, k2, 0.0, -k0, -k1, k0, 0.0};
-        for (int i = 0; i < 3; ++i)
-            for (int j = 0; j < 3; ++j) {
-                const double kk = (K[3 * i] * K[j] + K[3 * i + 1] * K[3 + j]) + K[3 * i + 2] * K[6 + j];
-                Q[3 * i + j] = (Q[3 * i + j] + s * K[3 * i + j]) + c * kk;
-            }
-    }
     double Rn[9], tn[3];
-    for (int i = 0; i < 3; ++i)
-        for (int j = 0; j < 3; ++j) Rn[3 * i + j] = (Q[3 * i] * st.R[j] + Q[3 * i + 1] * st.R[3 + j]) + Q[3 * i + 2] * st.R[6 + j];
+    rotate_left(x, st.R, Rn);
     for (int i = 0; i < 3; ++i) tn[i] = st.t[i] + x[3 + i];
     const double len = sqrt((tn[0] * tn[0] + tn[1] * tn[1]) + tn[2] * tn[2]);
     if (!(len > 0.0) || !finite64(len)) return false;
@@ -275,7 +227,7 @@ __global__ __launch_bounds__(NT) void refine_pose_kernel(const float* __restrict
             if (pass == 0) cost0 = sum[27];
             bool more = pass < iters;
             if (more) {
-                double A[6][6], g[6], x[6];
+                double A[6][6], g[6], y[6], x[6];
                 int at = 0;
                 for (int j = 0; j < 6; ++j) {
                     for (int k = j; k < 6; ++k) A[j][k] = A[k][j] = sum[at++];
@@ -287,7 +239,7 @@ __global__ __launch_bounds__(NT) void refine_pose_kernel(const float* __restrict
                 const double pin = trace / 6.0;            // the gauge: the residual cannot see the length of t
                 for (int i = 0; i < 3; ++i)
                     for (int j = 0; j < 3; ++j) A[3 + i][3 + j] = A[3 + i][3 + j] + pin * (st.t[i] * st.t[j]);
-                more = solve6(A, g, x) && apply_step(st, x);
+                more = cholesky_solve<6>(A, g, y, x) && apply_step(st, x);
                 if (more) {
                     set_matrices(st);
                     ++done;

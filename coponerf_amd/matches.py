@@ -15,7 +15,12 @@ round.  The reference uses them for the cycle loss and a warped panel only.  Her
   homography_pose  the same RANSAC with a homography as its model, for walls, floors and pure rotations, where the essential
                 matrix is under-determined: cpn_ransac_homographies / _score_h / _finish_h, three launches; with it the twin
                 pose, the singular values of H and the statistics that say which regime a pair is in
-  from_pair     get_z once, then the three above (ransac_pose with ransac={...}, homography_pose with homography={...})
+  refine_homography  refine_pose's Gauss-Newton on the homography's own Sampson residual, for the plane (nine entries) or for the
+                rotation alone (three parameters): cpn_refine_homography, one launch
+  model_gric    Torr's GRIC of E, the plane and the rotation alone on the same matches: cpn_model_gric, one launch
+  select_pose   all of the above in a row and the picked model's pose: which estimator to believe, decided on the device
+  from_pair     get_z once, then the above (ransac_pose with ransac={...}, homography_pose with homography={...}, select_pose
+                with select={...})
   photo_coords  host: matches of a prepare_pair dict in the coordinates of the original photos
 
 The conventions and the arithmetic are in include/coponerf_hip.h (round 16).  The selection defaults (cycle error up to 10
@@ -39,6 +44,12 @@ against the 8-point solver's 684 on the curved scene: the planarity verdict), an
 plane's distance, which says "no baseline".  Its transfer-error inlier rule, its visibility vote, its pick order and min_baseline
 with its default are this package's definitions and untried on a trained checkpoint; a fronto-parallel plane in a narrow field of
 view can leave the vote tied, and stats[4..7] then says so.
+
+select_pose (round 23 of the header) is the verdict between them.  GRIC on the RANSAC winners as they are misreads the pure rotation;
+after refine_homography - ten robust Gauss-Newton passes on the homography's Sampson residual, from homography_pose's H and from the
+rotation nearest to it - the wall picks the plane, the curved scene E and the pure rotation the rotation alone.  The rotation-only
+model inside the criterion is what min_baseline was a stand-in for.  The residual, the weights, the gauge, sigma_px = 0.5 (half the
+default inlier_px), the tie rule and the (d, k) table are this package's definitions and untried on a trained checkpoint.
 """
 from __future__ import annotations
 
@@ -172,6 +183,9 @@ def select(fields: Dict[str, torch.Tensor], max_cycle_px: float = 10.0, max_epi_
     if stride > 1:
         keep &= _stride_mask(int(cycle.shape[-1]), stride, cycle.device)
     return compact(keep.to(torch.uint8), fields["q"], cycle, epi)
+
+
+_select_matches = select                  # from_flows has a keyword of this name
 
 
 def _matches_args(who: str, matches: Matches) -> Tuple[int, int]:
@@ -333,7 +347,159 @@ def homography_pose(matches: Matches, intrinsics: torch.Tensor, rel_pose: Option
     return {"pose": pose, "twin": twin, "H": Hout, "inlier": inlier, "stats": stats}
 
 
+_H_MODELS = ("plane", "rotation")
+
+
+@torch.no_grad()
+def refine_homography(matches: Matches, intrinsics: torch.Tensor, H: torch.Tensor, model: str = "plane", iters: int = 10,
+                      scale_px: float = 2.0) -> Dict[str, torch.Tensor]:
+    """cpn_refine_homography (round 23 of the header): refine_pose's robust Gauss-Newton on the homography's Sampson residual
+    e^2 - to first order the squared distance in pixels from a match to the matches that satisfy H, weighted
+    1 / (1 + e^2 / scale_px^2)^2 -, float64 inside, one launch for all pairs.  H (B, 9) float64 is the start (homography_pose's
+    `H`).  model="plane" refines the nine entries with |h| = 1 (the gauge pins the length); model="rotation" refines the rotation
+    nearest to H, three parameters -> `H` (B, 9) float64 (the unit h with det > 0, or the rotation), `pose` (B, 4, 4) fp32
+    ([R | 0] for "rotation", the identity for "plane": a plane's pose takes the decomposition of cpn_ransac_finish_h) and
+    `stats` (B, 8) float64: the cost at the start, the cost / sum of weights / rows that count at the end, how far the state
+    moved (Frobenius distance of the unit h, or degrees), sigma_1 - sigma_3 of the refined plane (0 for "rotation"), the updates
+    made, the status (0 ok, 1 a failed solve: the state before it is returned, 2 nothing to do: no matches, iters == 0, a zero
+    or non-finite H - H as it came, the identity, the rest 0)."""
+    if model not in _H_MODELS:
+        raise ValueError(f"refine_homography: model must be one of {_H_MODELS}, got {model!r}")
+    xy, count = matches.xy, matches.count
+    device_tensors("refine_homography", (("matches.xy", xy, torch.float32, None), ("intrinsics", intrinsics, torch.float32, None),
+                                         ("H", H, torch.float64, None)))
+    B, N = _matches_args("refine_homography", matches)
+    _cameras("refine_homography", intrinsics, None, B)
+    if tuple(H.shape) != (B, 9):
+        raise ValueError(f"refine_homography: H must be (B, 9) with B = {B}, got {tuple(H.shape)}")
+    if not 1 <= B <= 32767 or N > 2 ** 24:
+        raise ValueError(f"refine_homography: need 1 <= B <= 32767 and N <= 2^24, got B = {B}, N = {N}")
+    if int(iters) < 0 or not 0.0 < float(scale_px) < float("inf"):
+        raise ValueError(f"refine_homography: need iters >= 0 and a finite scale_px > 0, got {iters} and {scale_px}")
+    Hout = torch.empty(B, 9, dtype=torch.float64, device=xy.device)
+    pose = torch.empty(B, 4, 4, dtype=torch.float32, device=xy.device)
+    stats = torch.empty(B, 8, dtype=torch.float64, device=xy.device)
+    with torch.cuda.device(xy.device):
+        _hip.call("cpn_refine_homography", xy.data_ptr(), count.data_ptr(), intrinsics.data_ptr(), H.data_ptr(), B, N,
+                  _H_MODELS.index(model), int(iters), float(scale_px), Hout.data_ptr(), pose.data_ptr(), stats.data_ptr(),
+                  _hip.stream_handle())
+    return {"H": Hout, "pose": pose, "stats": stats}
+
+
+_LN4N: Dict = {}
+
+
+def ln4n_table(N: int) -> np.ndarray:
+    """(N + 1) float64: entry u is ln(4 u) as numpy computes it on the host, entry 0 is 0 - cpn_model_gric's table."""
+    t = np.zeros(N + 1)
+    t[1:] = np.log(4.0 * np.arange(1, N + 1, dtype=np.float64))
+    return t
+
+
+def _ln4n(N: int, dev) -> torch.Tensor:
+    """ln4n_table on the device; a constant, built and copied once per (N, device)."""
+    key = (N, str(dev))
+    t = _LN4N.get(key)
+    if t is None:
+        t = _LN4N[key] = torch.from_numpy(ln4n_table(N)).to(dev)
+    return t
+
+
+@torch.no_grad()
+def model_gric(matches: Matches, intrinsics: torch.Tensor, pose_e: torch.Tensor, H_plane: torch.Tensor, H_rot: torch.Tensor,
+               avail: torch.Tensor, sigma_px: float = 0.5) -> Dict[str, torch.Tensor]:
+    """cpn_model_gric (round 23 of the header): Torr's GRIC of three models of the same matches - E = [t]x R of pose_e (B, 4, 4)
+    fp32, the plane H_plane and the rotation H_rot (B, 9) float64 -, one launch, nothing read on the host.  Every usable match
+    pays min(e^2 / sigma_px^2, 2 (4 - d)) with e^2 the squared Sampson residual in pixels under the model; the model pays
+    ln 4 . d per match for its dimension d (3 for E, 2 for the other two) and ln(4 n) per parameter (5, 8, 3).  avail (B, 3) uint8
+    says which models take part; a model with a non-finite value is out as well -> `gric` (B, 3) float64 (+inf where out),
+    `label` (B, N) uint8 (bit m: the match lies below model m's cap) and `stats` (B, 7) float64: the pick (0 E, 1 plane, 2 rotation;
+    the smallest gric, a tie to the model with fewer parameters; -1 where none is in), the usable matches, the matches below the cap
+    per model, the runner-up's gric minus the winner's, the status (0 ok, 1 no model in, 2 no usable match).  sigma_px = 0.5 is
+    half the default inlier_px, this package's choice and untried on a trained checkpoint."""
+    xy, count = matches.xy, matches.count
+    device_tensors("model_gric", (("matches.xy", xy, torch.float32, None), ("intrinsics", intrinsics, torch.float32, None),
+                                  ("pose_e", pose_e, torch.float32, None), ("H_plane", H_plane, torch.float64, None),
+                                  ("H_rot", H_rot, torch.float64, None), ("avail", avail, torch.uint8, None)))
+    B, N = _matches_args("model_gric", matches)
+    _cameras("model_gric", intrinsics, pose_e, B)
+    for what, x, shape in (("H_plane", H_plane, (B, 9)), ("H_rot", H_rot, (B, 9)), ("avail", avail, (B, 3))):
+        if tuple(x.shape) != shape:
+            raise ValueError(f"model_gric: {what} must be {shape}, got {tuple(x.shape)}")
+    if not 1 <= B <= 32767 or N > 2 ** 24:
+        raise ValueError(f"model_gric: need 1 <= B <= 32767 and N <= 2^24, got B = {B}, N = {N}")
+    if not 0.0 < float(sigma_px) < float("inf"):
+        raise ValueError(f"model_gric: need a finite sigma_px > 0, got {sigma_px}")
+    dev = xy.device
+    table = _ln4n(N, dev)
+    gric = torch.empty(B, 3, dtype=torch.float64, device=dev)
+    label = torch.empty(B, N, dtype=torch.uint8, device=dev)
+    stats = torch.empty(B, 7, dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        _hip.call("cpn_model_gric", xy.data_ptr(), count.data_ptr(), intrinsics.data_ptr(), pose_e.data_ptr(), H_plane.data_ptr(),
+                  H_rot.data_ptr(), avail.data_ptr(), table.data_ptr(), B, N, float(sigma_px), gric.data_ptr(), label.data_ptr(),
+                  stats.data_ptr(), _hip.stream_handle())
+    return {"gric": gric, "label": label, "stats": stats}
+
+
+@torch.no_grad()
+def select_pose(matches: Matches, intrinsics: torch.Tensor, rel_pose: Optional[torch.Tensor] = None, hypotheses: int = 1024,
+                inlier_px: float = 1.0, seed: int = 0, solver: str = "8pt", sigma_px: float = 0.5, iters: int = 10,
+                scale_px: float = 2.0) -> Dict:
+    """The pose of two photos without knowing whether they show a room, a wall or a turn on a tripod: ransac_pose and refine_pose
+    from its pose (E); homography_pose with min_baseline 0 and refine_homography in both modes from its H (the plane, the rotation
+    alone); cpn_ransac_score_h and cpn_ransac_finish_h on ONE slot, the refined plane, for its decomposition, vote and twin;
+    model_gric; the picked model's pose by torch.where.  Twelve launches, nothing read on the host.  A model takes part where its
+    producers' statuses say it exists (built on the device): E where ransac_pose's is 0 and refine_pose's 0 or 1; the plane where
+    homography_pose's is 0 or 3, its refinement's 0 or 1 and the one-slot finish's 0; the rotation where homography_pose's is 0 or 3
+    and its refinement's 0 or 1 -> `pose` (B, 4, 4) fp32 (rel_pose, or the identity without one, where no model is in), `model`
+    (B) int32 (0 E, 1 plane, 2 rotation, -1 none), `gric`, `label`, `stats` (model_gric's), `avail` (B, 3) uint8, and the
+    producers' dicts: `ransac`, `refined`, `homography`, `plane` (the one-slot finish's dict - pose, twin, H with sigma_2 = 1,
+    inlier, stats - with `H_refined`, the unit h, and `refine_stats` beside it) and `rotation` (refine_homography's).
+    The verdict is only as good as the refinement: on the unrefined RANSAC winners GRIC misreads the pure rotation (README, round
+    23).  sigma_px is this package's choice and untried on a trained checkpoint."""
+    if solver not in _SOLVERS:
+        raise ValueError(f"select_pose: solver must be one of {_SOLVERS}, got {solver!r}")
+    if not 0.0 < float(sigma_px) < float("inf"):
+        raise ValueError(f"select_pose: need a finite sigma_px > 0, got {sigma_px}")
+    found = ransac_pose(matches, intrinsics, rel_pose, hypotheses=hypotheses, inlier_px=inlier_px, seed=seed, solver=solver)
+    refined = refine_pose(matches, intrinsics, found["pose"], iters=iters, scale_px=scale_px)
+    homog = homography_pose(matches, intrinsics, rel_pose, hypotheses=hypotheses, inlier_px=inlier_px, seed=seed, min_baseline=0.0)
+    flat = refine_homography(matches, intrinsics, homog["H"], model="plane", iters=iters, scale_px=scale_px)
+    turn = refine_homography(matches, intrinsics, homog["H"], model="rotation", iters=iters, scale_px=scale_px)
+    xy, count = matches.xy, matches.count
+    B, N = int(xy.shape[0]), int(xy.shape[1])
+    dev, px = xy.device, float(inlier_px)
+    chunks = -(-N // _hip.CONSTANTS["RANSAC_CHUNK"])
+    one = torch.ones(B, 1, dtype=torch.uint8, device=dev)
+    partial = torch.empty(B, chunks, 1, dtype=torch.int32, device=dev)
+    plane = {"pose": torch.empty(B, 4, 4, dtype=torch.float32, device=dev), "twin": torch.empty(B, 4, 4, dtype=torch.float32, device=dev),
+             "H": torch.empty(B, 9, dtype=torch.float64, device=dev), "inlier": torch.empty(B, N, dtype=torch.uint8, device=dev),
+             "stats": torch.empty(B, 12, dtype=torch.float64, device=dev)}
+    rel = 0 if rel_pose is None else rel_pose.data_ptr()
+    with torch.cuda.device(dev):
+        s = _hip.stream_handle()
+        _hip.call("cpn_ransac_score_h", flat["H"].data_ptr(), one.data_ptr(), xy.data_ptr(), count.data_ptr(), intrinsics.data_ptr(), B, N,
+                  1, px, partial.data_ptr(), s)
+        _hip.call("cpn_ransac_finish_h", flat["H"].data_ptr(), one.data_ptr(), partial.data_ptr(), xy.data_ptr(), count.data_ptr(),
+                  intrinsics.data_ptr(), rel, B, N, 1, px, 0.0, plane["pose"].data_ptr(), plane["twin"].data_ptr(), plane["H"].data_ptr(),
+                  plane["inlier"].data_ptr(), plane["stats"].data_ptr(), s)
+    plane["H_refined"], plane["refine_stats"] = flat["H"], flat["stats"]
+    h_ok = (homog["stats"][:, 11] == 0) | (homog["stats"][:, 11] == 3)
+    avail = torch.stack(((found["stats"][:, 7] == 0) & (refined["stats"][:, 7] <= 1),
+                         h_ok & (flat["stats"][:, 7] <= 1) & (plane["stats"][:, 11] == 0),
+                         h_ok & (turn["stats"][:, 7] <= 1)), dim=1).to(torch.uint8).contiguous()
+    verdict = model_gric(matches, intrinsics, refined["pose"], flat["H"], turn["H"], avail, sigma_px=sigma_px)
+    model = verdict["stats"][:, 0].to(torch.int32)
+    none = rel_pose if rel_pose is not None else torch.eye(4, dtype=torch.float32, device=dev).expand(B, 4, 4)
+    pick = model[:, None, None]
+    pose = torch.where(pick == 0, refined["pose"], torch.where(pick == 1, plane["pose"], torch.where(pick == 2, turn["pose"], none)))
+    return {"pose": pose.contiguous(), "model": model, "gric": verdict["gric"], "label": verdict["label"], "stats": verdict["stats"],
+            "avail": avail, "ransac": found, "refined": refined, "homography": homog, "plane": plane, "rotation": turn}
+
+
 _STARTS = ("network", "ransac", "best")
+_S_STARTS = ("network", "selected")
 _H_STARTS = ("network", "homography")
 _SOLVERS = ("8pt", "5pt")
 
@@ -367,10 +533,26 @@ def _homography_keywords(who: str, homography: Dict) -> Tuple[Dict, str]:
     return kw, start
 
 
+def _select_keywords(who: str, select_kw: Dict) -> Tuple[Dict, str]:
+    if not isinstance(select_kw, dict):
+        raise ValueError(f"{who}: select must be None or a dict of select_pose's keywords and `start`, got {type(select_kw).__name__}")
+    kw = dict(select_kw)
+    start = kw.pop("start", "network")
+    if start not in _S_STARTS:
+        raise ValueError(f"{who}: select['start'] must be one of {_S_STARTS}, got {start!r}")
+    unknown = set(kw) - {"hypotheses", "inlier_px", "seed", "solver", "sigma_px", "iters", "scale_px"}
+    if unknown:
+        raise ValueError(f"{who}: select holds unknown keywords {sorted(unknown)}")
+    if kw.get("solver", "8pt") not in _SOLVERS:
+        raise ValueError(f"{who}: select['solver'] must be one of {_SOLVERS}, got {kw['solver']!r}")
+    return kw, start
+
+
 @torch.no_grad()
 def from_flows(flow: Sequence[torch.Tensor], intrinsics: torch.Tensor, rel_pose: torch.Tensor, S: int = 256, refine: bool = True,
                max_cycle_px: float = 10.0, max_epi_px: Optional[float] = None, stride: int = 4, iters: int = 10,
-               scale_px: float = 2.0, ransac: Optional[Dict] = None, homography: Optional[Dict] = None) -> Dict:
+               scale_px: float = 2.0, ransac: Optional[Dict] = None, homography: Optional[Dict] = None,
+               select: Optional[Dict] = None) -> Dict:
     """from_pair's second half, for flows and a pose that get_z has already returned: four launches and the mask between them,
     no host read.  ransac: None, or a dict of ransac_pose's keywords (hypotheses, inlier_px, seed, solver) and `start`: three more
     launches, and the result gains the key `ransac` (ransac_pose's dict).  start="network" (the default) refines from rel_pose
@@ -379,7 +561,11 @@ def from_flows(flow: Sequence[torch.Tensor], intrinsics: torch.Tensor, rel_pose:
     homography: None, or a dict of homography_pose's keywords (hypotheses, inlier_px, seed, min_baseline) and `start`: three more
     launches, and the result gains the key `homography` (homography_pose's dict).  start="homography" refines from its pose where
     its status is 0 and from rel_pose elsewhere (torch.where on the device); a start other than "network" in both dicts is a
-    ValueError.  Without the keyword nothing changes: no launch, no key."""
+    ValueError.  Without the keyword nothing changes: no launch, no key.
+    select: None, or a dict of select_pose's keywords (hypotheses, inlier_px, seed, solver, sigma_px, iters, scale_px) and `start`:
+    select_pose's twelve launches, and the result gains the key `select` (select_pose's dict).  start="selected" refines from the
+    selected pose where model_gric's status is 0 and from rel_pose elsewhere; a second start other than "network" among ransac,
+    homography and select is the same ValueError.  Without the keyword nothing changes: no launch, no key."""
     if ransac is not None:
         ransac_kw, start = _ransac_keywords("from_flows", ransac)
     if homography is not None:
@@ -387,8 +573,15 @@ def from_flows(flow: Sequence[torch.Tensor], intrinsics: torch.Tensor, rel_pose:
         if h_start != "network" and ransac is not None and start != "network":
             raise ValueError(f"from_flows: ransac['start'] = {start!r} and homography['start'] = {h_start!r} both name a start; "
                              "one of them must be \"network\"")
+    if select is not None:
+        select_kw, s_start = _select_keywords("from_flows", select)
+        named = [f"{k}['start'] = {v!r}" for k, v in (("ransac", start if ransac is not None else "network"),
+                                                      ("homography", h_start if homography is not None else "network"),
+                                                      ("select", s_start)) if v != "network"]
+        if s_start != "network" and len(named) > 1:
+            raise ValueError(f"from_flows: {' and '.join(named)} all name a start; only one of them may differ from \"network\"")
     fields = match_fields(flow, intrinsics, rel_pose, S)
-    matches = select(fields, max_cycle_px=max_cycle_px, max_epi_px=max_epi_px, stride=stride)
+    matches = _select_matches(fields, max_cycle_px=max_cycle_px, max_epi_px=max_epi_px, stride=stride)
     result = {"matches": matches, "rel_pose": rel_pose, "pose": None, "stats": None, "fields": fields}
     begin = rel_pose
     if ransac is not None:
@@ -403,6 +596,10 @@ def from_flows(flow: Sequence[torch.Tensor], intrinsics: torch.Tensor, rel_pose:
         plane = result["homography"] = homography_pose(matches, intrinsics, rel_pose, **homography_kw)
         if h_start == "homography":
             begin = torch.where((plane["stats"][:, 11] == 0)[:, None, None], plane["pose"], rel_pose)
+    if select is not None:
+        chosen = result["select"] = select_pose(matches, intrinsics, rel_pose, **select_kw)
+        if s_start == "selected":
+            begin = torch.where((chosen["stats"][:, 6] == 0)[:, None, None], chosen["pose"], rel_pose)
     if refine:
         result.update(refine_pose(matches, intrinsics, begin, iters=iters, scale_px=scale_px))
     return result

@@ -1261,6 +1261,72 @@ int cpn_ransac_finish_h(const double* H, const uint8_t* valid, const int* partia
                         const float* intrinsics, const float* rel_pose, int B, int N, int Hn, double inlier_px,
                         double min_baseline, float* pose, float* twin, double* Hout, uint8_t* inlier, double* stats, void* stream);
 
+/* ==== which model explains a pair: the refined homography and GRIC (round 23) ==============================================
+ * Rounds 20 - 22 estimate an essential matrix and a homography; this round says which to believe - E, one plane, or a rotation
+ * alone - and refines the homography first, because on minimal 4-point winners the verdict is not reliable.  Two additive
+ * symbols: the ABI version stays.  One launch each, one workgroup of 256 threads per pair, no atomics, nothing read on the host,
+ * bit-reproducible, and a pair's result does not depend on the batch.  Conventions: rounds 16 and 22 (xy (B, N, 4) fp32 =
+ * (x0, y0, x1, y1), count (B) int32, n = min(max(count, 0), N), a and b the normalised points of views 0 and 1, a ~ H b,
+ * X0 = R X1 + t, intrinsics (B, 2, 4, 4) fp32 with fx, fy, cx, cy at entries 0, 5, 2, 6).  1 <= B <= 32767 and 1 <= N <= 2^24
+ * (CPN_E_SHAPE otherwise).  THE RESIDUAL, THE WEIGHTS, THE GAUGE, sigma_px AND ITS DEFAULT, THE TIE RULE AND THE (d, k) TABLE ARE
+ * THIS LIBRARY'S definitions; none of them has been tried on a trained checkpoint.  All float64 from the fp32 inputs, one rounding
+ * per operation, + - * / sqrt and comparisons (the rotation step alone takes a sine and a cosine, as cpn_refine_pose's does).
+ * THE HOMOGRAPHY'S SAMPSON RESIDUAL of a match under H (row-major): m = H b, component i (H_i0 b0 + H_i1 b1) + H_i2;
+ *   C0 = m0 - a0 m2, C1 = m1 - a1 m2; the Jacobian of C in the PIXELS (x0, y0, x1, y1): J00 = -m2 / fx0,
+ *   J02 = (H00 - a0 H20) / fx1, J03 = (H01 - a0 H21) / fy1, J11 = -m2 / fy0, J12 = (H10 - a1 H20) / fx1,
+ *   J13 = (H11 - a1 H21) / fy1, J01 = J10 = 0.  S = J J^T: A = (J00 J00 + J02 J02) + J03 J03, Bq = J02 J12 + J03 J13,
+ *   Cq = (J11 J11 + J12 J12) + J13 J13.  l00 = sqrt(A), l10 = Bq / l00, l11 = sqrt(Cq - l10 l10); y0 = C0 / l00,
+ *   y1 = (C1 - l10 y0) / l11; e^2 = y0 y0 + y1 y1: to first order the squared distance in pixels from the match to the matches
+ *   that satisfy H, the same kind of quantity as the squared round-16 residual r^2 under E.  The residual COUNTS iff A > 0,
+ *   Cq - l10 l10 > 0 and m, C, A, Bq, Cq, l, y and e^2 are all finite.
+ *   ALONG a direction dH: dm, dC and dJ are the expressions of m, C and J on dH (with a and b as they are);
+ *   dA = 2 ((J00 dJ00 + J02 dJ02) + J03 dJ03), dBq = ((dJ02 J12 + J02 dJ12) + dJ03 J13) + J03 dJ13,
+ *   dCq = 2 ((J11 dJ11 + J12 dJ12) + J13 dJ13); dl00 = dA / (2 l00), dl10 = (dBq - l10 dl00) / l00,
+ *   dl11 = (dCq - (2 l10) dl10) / (2 l11); dy0 = (dC0 - y0 dl00) / l00, dy1 = (((dC1 - dl10 y0) - l10 dy0) - y1 dl11) / l11: the
+ *   FULL derivative of y, the whitening differentiated with it.
+ * cpn_refine_homography: cpn_refine_pose's robust Gauss-Newton with that residual.  H0 (B, 9) float64; mode 0 the plane, 1 the
+ *   rotation alone; iters >= 0; scale_px finite and > 0 (CPN_E_ARG otherwise).
+ *   MODE 0: the state is h with |h|_F = 1: H0 / sqrt((H0_0^2 + H0_1^2) + .. + H0_8^2), negated where its determinant (round 22's
+ *   expression) is < 0; the sign is not looked at again.  The nine directions are the unit matrices, parameter k = entry k.
+ *   MODE 1: the state is the rotation nearest to H0, R_n = (u_1 v_1^T + u_2 v_2^T) + u_3 v_3^T from round 20's Jacobi method and
+ *   frames on G = H0, exactly as cpn_ransac_finish_h forms it for status 3; H = R; the three directions are [e_k]x R.
+ *   A PASS: thread t adds the rows t, t + 256, .. below n in ascending order, the 64 lanes of a wave by the xor butterfly
+ *   32 .. 1, the four waves as (0 + 1) + (2 + 3).  A row whose residual counts has u = 1 + e^2 / (scale_px scale_px),
+ *   w = 1 / (u u) and, with J0_k = dy0 and J1_k = dy1 along direction k, adds (w J0_j) J0_k + (w J1_j) J1_k to entry (j, k >= j)
+ *   of the normal matrix, (w J0_j) y0 + (w J1_j) y1 to entry j of the gradient, (e^2 / 2) / u to the cost, w to the weights and 1
+ *   to the rows.  THE STEP: A_jj += 1e-3 A_jj; in mode 0 then A += (tr / 9) h h^T with tr the trace before the damping, the
+ *   gauge (the residual cannot see the length of h: cpn_refine_pose's translation gauge at nine parameters); delta = -A^-1 g
+ *   by Cholesky as in cpn_refine_pose; mode 0: h <- (h + delta) / |h + delta|; mode 1: R <- exp([delta]x) R by cpn_refine_pose's
+ *   Rodrigues step.  A pivot that is not > 0 or a value that is not finite keeps the state, sets status 1 and ends the pair's
+ *   passes.  Pass `iters` only measures.
+ *   H (B, 9) float64: the unit h (mode 0) or the rotation (mode 1).  pose (B, 4, 4) fp32: [R | 0] above 0 0 0 1 in mode 1, the
+ *   identity in mode 0.  stats (B, 8) float64: [0] the cost of pass 0; [1], [2], [3] the cost, the sum of weights and the rows
+ *   that count at the returned state; [4] how far the state moved: |h - h_start|_F in mode 0, the angle in degrees in
+ *   cpn_refine_pose's formula in mode 1; [5] sigma_1 - sigma_3 of the returned H over sigma_2 (the column norms of round 20's
+ *   Jacobi method) in mode 0, 0 in mode 1; [6] the updates made; [7] the status: 0 ok; 1 a failed solve; 2 nothing to do (n == 0,
+ *   iters == 0, an H0 that is all zero or not finite, a start that is not finite): H is H0's nine values, pose the identity,
+ *   the other stats 0.  Every element of the three outputs is written.
+ * cpn_model_gric: Torr's GRIC with r = 4 and lambda = (ln 4, ln 4n, 2) over three models.  pose_e (B, 4, 4) fp32, its
+ *   E = [t]x R in round 16's expression; H_plane, H_rot (B, 9) float64; avail (B, 3) bytes: whether model m takes part;
+ *   sigma_px finite and > 0 (CPN_E_ARG otherwise); ln4n (N + 1) float64, entry u = ln(4 u) AS THE CALLER COMPUTED IT ON THE
+ *   HOST (entry 0 is not read): the kernel takes no logarithm, and ln 4 is the constant 1.3862943611198906.
+ *   USABLE rows: below n with four finite values; n_u their number.  Model m = 0, 1, 2 (E, plane, rotation) has
+ *   (d, k) = (3, 5), (2, 8), (2, 3) and cap_m = 2 (4 - d_m).  It is IN iff avail is not 0 and its nine values are finite.
+ *   x = e^2 / (sigma_px sigma_px) with e^2 = r r for E (r = n / sqrt(D), round 16) and the residual above for the other two.  A
+ *   usable row is BELOW THE CAP of a model that is in iff its residual counts and x < cap_m; rho = x there and cap_m otherwise.
+ *   gric_m = (sum rho + (ln 4 d_m) n_u) + ln4n[n_u] k_m, the sum in the order of a pass above; +inf where the model is out or
+ *   n_u = 0.  THE PICK: the smallest gric; a tie goes to the model with fewer parameters: rotation, then plane, then E.
+ *   gric (B, 3) float64.  label (B, N) bytes: bit m set iff the row is usable and below the cap of model m; 0 elsewhere and at
+ *   and beyond n; every byte is written.  stats (B, 7) float64: [0] the pick, -1 where no model is in; [1] n_u; [2], [3], [4]
+ *   the rows below the cap per model (0 for a model that is out); [5] the runner-up's gric minus the winner's, +inf with fewer
+ *   than two models in; [6] the status: 0 ok; 1 no model in; 2 n_u = 0.  sigma_px = 0.5, the wrapper's default, is half the
+ *   default inlier_px and as untried on a trained checkpoint as that is.                                                      */
+int cpn_refine_homography(const float* xy, const int* count, const float* intrinsics, const double* H0, int B, int N, int mode,
+                          int iters, double scale_px, double* H, float* pose, double* stats, void* stream);
+int cpn_model_gric(const float* xy, const int* count, const float* intrinsics, const float* pose_e, const double* H_plane,
+                   const double* H_rot, const uint8_t* avail, const double* ln4n, int B, int N, double sigma_px, double* gric,
+                   uint8_t* label, double* stats, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
