@@ -10,7 +10,8 @@ novel_views.hip for the one-rounding-per-operation sums of its resample and its 
 operation sequence of its fundamental matrices and line end points; point_cloud.hip for that of its points and votes; matches.hip
 for the flow warp's fp32 sequence and the float64 sequence of its residuals, Jacobians and sums; splat.hip for the float64
 sequence of its projection; ransac.hip for that of its 8-point systems, its residuals (sampson.h, shared with matches.hip, as
-is pose_out.h: rel_pose's use and the pose written out) and its split of the essential matrix; ransac5.hip for that of its 5-point
+is pose_out.h: rel_pose's use and the pose written out), its split of the essential matrix (essential_split.h) and its polish,
+which runs matches.hip's Gauss-Newton passes from pose_gauss_newton.h; ransac5.hip for that of its 5-point
 solver, which tests/ransac5_ref.py follows bit for bit (both take their sampler and shape rule from ransac_common.h and their
 system, elimination and null vectors from epipolar_system.h); ransac_h.hip for that of its homographies, their transfer errors
 and their decomposition, which tests/homography_ref.py follows bit for bit (it shares ransac_score.h's tiling, jacobi_svd.h's

@@ -6,25 +6,21 @@
 //                             in-image test and the signed Sampson residual of the pair under rel_pose in float64.
 //   matches_count_kernel /    cpn_compact_matches: compact.h's two launches over a pair's (direction, row, column) sequence; a
 //   matches_write_kernel      kept match writes (x0, y0, x1, y1) - view 0's point first - and (cycle, epi).
-//   refine_pose_kernel        cpn_refine_pose: ONE workgroup of 256 threads per pair, all Gauss-Newton iterations inside it.
-//                             Per pass thread t walks the matches t, t + 256, .. in ascending order and keeps 30 float64 sums
-//                             (21 of H, 6 of g, the cost, the weights, the finite matches) in registers; the butterfly of
-//                             wave_sum, then LDS and (w0 + w1) + (w2 + w3) in thread 0, which solves the damped 6 x 6 system by
-//                             Cholesky, updates R and t and leaves E and the six dE_k in LDS for the next pass.  Two barriers a
-//                             pass, no partials in HBM, no inter-workgroup synchronisation.  Pass `iters` only measures.
+//   refine_pose_kernel        cpn_refine_pose: ONE workgroup of 256 threads per pair, all Gauss-Newton iterations inside it:
+//                             pose_gauss_newton.h's passes (ransac.hip's polish shares them) from rel_pose.  No partials in HBM,
+//                             no inter-workgroup synchronisation.
 //
 // The residual is float64 from the fp32 inputs, one rounding per operation (-ffp-contract=off), sums left to right:
 // tests/matches_ref.py restates all three in numpy.  Cam and Pose are pinhole.h's; essential, sampson and residual_ok are sampson.h's,
 // the use of rel_pose and the pose written out pose_out.h's, the count clamp ransac_common.h's: ransac.hip shares all three.
 // cross_rows and the Rodrigues step are rotation_step.h's and the Cholesky solve cholesky_solve.h's: model_select.hip shares both.
-#include "cholesky_solve.h"
 #include "common.h"
 #include "compact.h"
 #include "flow_warp.h"
 #include "pinhole.h"
+#include "pose_gauss_newton.h"
 #include "pose_out.h"
 #include "ransac_common.h"
-#include "rotation_step.h"
 #include "sampson.h"
 
 #include <math.h>
@@ -33,7 +29,6 @@ namespace {
 
 constexpr int NT = 256;
 constexpr int PTW = 32, PTH = NT / PTW;                    // match fields: the tile of one workgroup
-constexpr int NSUM = 30;                                   // refinement: H (21), g (6), cost, sum of weights, finite matches
 
 __global__ __launch_bounds__(NT) void match_fields_kernel(const float* __restrict__ flow0, const float* __restrict__ flow1,
                                                           const float* __restrict__ intrinsics, const float* __restrict__ rel_pose,
@@ -117,52 +112,22 @@ __global__ __launch_bounds__(NT) void matches_write_kernel(const uint8_t* __rest
     if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) count[b] = at;
 }
 
-// ---- refinement
-// what thread 0 keeps for the pair between the passes, and what every thread reads in a pass
-struct RefineState {
-    double R[9], t[3];
-    double E[9], dE[6][9];          // E = [t]x R; dE_k = [t]x [e_k]x R (k < 3), [e_(k-3)]x R (k >= 3)
-    double red[NSUM][4];            // the four wave sums of a pass
-    int go;                         // another pass follows
-};
-
-__device__ void set_matrices(RefineState& st) {
-    essential(st.R, st.t, st.E);
-    for (int k = 0; k < 3; ++k) {
-        cross_rows(st.R, k, st.dE[3 + k]);
-        essential(st.dE[3 + k], st.t, st.dE[k]);
-    }
-}
-
-// R <- exp([w]x) R (Rodrigues; the identity below 1e-12), t <- (t + dt) / |t + dt|; false (state untouched) where not finite
-__device__ bool apply_step(RefineState& st, const double (&x)[6]) {
-    double Rn[9], tn[3];
-    rotate_left(x, st.R, Rn);
-    for (int i = 0; i < 3; ++i) tn[i] = st.t[i] + x[3 + i];
-    const double len = sqrt((tn[0] * tn[0] + tn[1] * tn[1]) + tn[2] * tn[2]);
-    if (!(len > 0.0) || !finite64(len)) return false;
-    for (int i = 0; i < 9; ++i)
-        if (!finite64(Rn[i])) return false;
-    for (int i = 0; i < 9; ++i) st.R[i] = Rn[i];
-    for (int i = 0; i < 3; ++i) st.t[i] = tn[i] / len;
-    return true;
-}
-
+// ---- refinement: pose_gauss_newton.h's passes from rel_pose
 __global__ __launch_bounds__(NT) void refine_pose_kernel(const float* __restrict__ xy, const int* __restrict__ count,
                                                          const float* __restrict__ intrinsics, const float* __restrict__ rel_pose,
                                                          int N, int iters, double scale_px, float* __restrict__ pose,
                                                          double* __restrict__ stats) {
     __shared__ RefineState st;
-    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int b = blockIdx.x, tid = threadIdx.x;
     const float* const P = rel_pose + (size_t)b * 16;
     const int n = clamp_count(count[b], N);
-    double len0 = 0.0, cost0 = 0.0;
+    double len0 = 0.0;
     if (tid == 0) {
         const RelStart start = rel_start(P);
         len0 = start.len0;
         st.go = (start.ok && n > 0 && iters > 0) ? 1 : 0;
         for (int r = 0; r < 3; ++r)                         // whether or not the pair goes on, as ever: the compiler's schedule
-            for (int c = 0; c < 3; ++c) st.R[3 * r + c] = start.rel.R[r][c];        // of the match loop below turns on it
+            for (int c = 0; c < 3; ++c) st.R[3 * r + c] = start.rel.R[r][c];        // of the match loop turns on it
         if (st.go) {
             for (int r = 0; r < 3; ++r) st.t[r] = start.rel.t[r] / len0;
             set_matrices(st);
@@ -175,97 +140,21 @@ __global__ __launch_bounds__(NT) void refine_pose_kernel(const float* __restrict
         return;
     }
     const Cam k0 = load_cam(intrinsics + ((size_t)b * 2 + 0) * 16), k1 = load_cam(intrinsics + ((size_t)b * 2 + 1) * 16);
-    const float* const rows = xy + (size_t)b * N * 4;
-    int done = 0, status = 0;
-
-    for (int pass = 0;; ++pass) {
-        double acc[NSUM];
-#pragma unroll
-        for (int k = 0; k < NSUM; ++k) acc[k] = 0.0;
-        for (int i = tid; i < n; i += NT) {
-            const float* const m = rows + (size_t)i * 4;
-            const Sampson s = sampson(st.E, k0, k1, (double)m[0], (double)m[1], (double)m[2], (double)m[3]);
-            const double sd = sqrt(s.D), r = s.n / sd;
-            if (!residual_ok(s, r)) continue;               // weight 0, not counted
-            double J[6];
-#pragma unroll
-            for (int k = 0; k < 6; ++k) {
-                const double* const dE = st.dE[k];
-                const double db0 = (dE[0] * s.b0 + dE[1] * s.b1) + dE[2];
-                const double db1 = (dE[3] * s.b0 + dE[4] * s.b1) + dE[5];
-                const double db2 = (dE[6] * s.b0 + dE[7] * s.b1) + dE[8];
-                const double da0 = (dE[0] * s.a0 + dE[3] * s.a1) + dE[6];
-                const double da1 = (dE[1] * s.a0 + dE[4] * s.a1) + dE[7];
-                const double dn = (s.a0 * db0 + s.a1 * db1) + db2;
-                const double dD = 2.0 * (((s.g[0] * (db0 / k0.fx) + s.g[1] * (db1 / k0.fy)) + s.g[2] * (da0 / k1.fx)) +
-                                         s.g[3] * (da1 / k1.fy));
-                J[k] = dn / sd - (s.n * dD) / ((2.0 * s.D) * sd);
-            }
-            const double z = r / scale_px, u = 1.0 + z * z, w = 1.0 / (u * u);
-            int at = 0;
-#pragma unroll
-            for (int j = 0; j < 6; ++j) {
-                const double wj = w * J[j];
-#pragma unroll
-                for (int k = j; k < 6; ++k) acc[at++] += wj * J[k];
-                acc[21 + j] += wj * r;
-            }
-            acc[27] += ((r * r) / 2.0) / u;
-            acc[28] += w;
-            acc[29] += 1.0;
-        }
-#pragma unroll
-        for (int k = 0; k < NSUM; ++k) acc[k] = wave_sum(acc[k]);
-        if (lane == 0) {
-#pragma unroll
-            for (int k = 0; k < NSUM; ++k) st.red[k][wave] = acc[k];
-        }
-        __syncthreads();
-        if (tid == 0) {
-            double sum[NSUM];
-            for (int k = 0; k < NSUM; ++k) sum[k] = (st.red[k][0] + st.red[k][1]) + (st.red[k][2] + st.red[k][3]);
-            if (pass == 0) cost0 = sum[27];
-            bool more = pass < iters;
-            if (more) {
-                double A[6][6], g[6], y[6], x[6];
-                int at = 0;
-                for (int j = 0; j < 6; ++j) {
-                    for (int k = j; k < 6; ++k) A[j][k] = A[k][j] = sum[at++];
-                    g[j] = sum[21 + j];
-                }
-                double trace = 0.0;
-                for (int j = 0; j < 6; ++j) trace += A[j][j];
-                for (int j = 0; j < 6; ++j) A[j][j] = A[j][j] + 1e-3 * A[j][j];
-                const double pin = trace / 6.0;            // the gauge: the residual cannot see the length of t
-                for (int i = 0; i < 3; ++i)
-                    for (int j = 0; j < 3; ++j) A[3 + i][3 + j] = A[3 + i][3 + j] + pin * (st.t[i] * st.t[j]);
-                more = cholesky_solve<6>(A, g, y, x) && apply_step(st, x);
-                if (more) {
-                    set_matrices(st);
-                    ++done;
-                } else {
-                    status = 1;                            // the pair keeps its state and stops
-                }
-            }
-            st.go = more ? 1 : 0;
-            if (!more) {
-                double deg_R, deg_t;
-                pose_angles(st.R, st.t, load_pose(P), len0, deg_R, deg_t);     // rel_pose read again: not held over the passes
-                store_pose(pose + (size_t)b * 16, st.R, st.t, len0);
-                double* const so = stats + (size_t)b * 8;
-                so[0] = cost0;
-                so[1] = sum[27];
-                so[2] = sum[28];
-                so[3] = sum[29];
-                so[4] = deg_R;
-                so[5] = deg_t;
-                so[6] = (double)done;
-                so[7] = (double)status;
-            }
-        }
-        __syncthreads();
-        if (!st.go) return;
-    }
+    pose_passes(st, xy + (size_t)b * N * 4, n, k0, k1, iters, scale_px,
+                [&](double cost0, const double (&sum)[POSE_NSUM], int done, int status) {
+                    double deg_R, deg_t;
+                    pose_angles(st.R, st.t, load_pose(P), len0, deg_R, deg_t);     // rel_pose read again: not held over the passes
+                    store_pose(pose + (size_t)b * 16, st.R, st.t, len0);
+                    double* const so = stats + (size_t)b * 8;
+                    so[0] = cost0;
+                    so[1] = sum[27];
+                    so[2] = sum[28];
+                    so[3] = sum[29];
+                    so[4] = deg_R;
+                    so[5] = deg_t;
+                    so[6] = (double)done;
+                    so[7] = (double)status;
+                });
 }
 
 bool grid_ok(int B, int S) { return B >= 1 && B <= 32767 && S >= 1 && S <= 16384 && 2LL * B * S * S < (1LL << 31); }

@@ -59,6 +59,75 @@ __device__ __forceinline__ long long best_hypothesis(const uint8_t* __restrict__
     n_valid = block_all(n_valid, add_ll, red);
     return best;
 }
+__device__ __forceinline__ long long smaller_ll(long long x, long long y) { return x < y ? x : y; }
+
+// best_hypothesis for scores that need all 64 bits (round 24: a graded sum reaches 2^44) and for the ranks beyond the first: the
+// order is (score descending, slot ascending) as a PAIR; slot -1 stands for "none" and ranks behind every slot.
+struct Ranked {
+    long long score;
+    int slot;
+};
+__device__ __forceinline__ bool ranks_before(long long sa, int ha, long long sb, int hb) {
+    return ha >= 0 && (hb < 0 || sa > sb || (sa == sb && ha < hb));
+}
+// the first in that order of one candidate per thread, in every thread: the largest score, then its lowest slot
+__device__ __forceinline__ Ranked first_ranked(long long score, int slot, long long* red) {
+    const long long best = block_all(slot >= 0 ? score : -1, larger_ll, red);
+    const long long at = block_all((slot >= 0 && score == best) ? slot : 0x7FFFFFFF, smaller_ll, red);
+    Ranked r;
+    r.score = best < 0 ? 0 : best;
+    r.slot = best < 0 ? -1 : (int)at;
+    return r;
+}
+
+// The first `want` + 1 <= DEPTH of the `slots` slots h with ok(h) in that order - their score the int64 sum of `used`
+// partials, `width` apart - in ONE sweep: thread t keeps the DEPTH best of its slots t, t + 256, .. in registers (a chain
+// of compare-and-swaps at fixed indices: no private array under a runtime index), sorted; then want + 1 times the workgroup
+// takes the first of the threads' heads and the thread that held it moves its chain up -> the one taken last (rank `want`),
+// slot -1 where there are no more than `want` such slots; in every thread.  (k + 1 sweeps of a winner search give the same
+// slot; on 10 240 slots and 24 chunks they took 1.69 ms of the polish kernel's 1.93.)  The finish asks for the winner alone:
+// DEPTH 1.
+template <int DEPTH, class Ok>
+__device__ __forceinline__ Ranked ranked_slot(Ok ok, const int* __restrict__ part, int slots, int width, int used, int want,
+                                              long long* red) {
+    long long top_score[DEPTH];
+    int top_slot[DEPTH];
+#pragma unroll
+    for (int j = 0; j < DEPTH; ++j) {
+        top_score[j] = 0;
+        top_slot[j] = -1;
+    }
+    for (int h = threadIdx.x; h < slots; h += 256) {
+        if (!ok(h)) continue;
+        long long s = 0;
+        for (int c = 0; c < used; ++c) s += part[(size_t)c * width + h];
+        int at = h;
+#pragma unroll
+        for (int j = 0; j < DEPTH; ++j)
+            if (ranks_before(s, at, top_score[j], top_slot[j])) {        // the better one stays, the other moves down the chain
+                const long long ts = top_score[j];
+                const int th = top_slot[j];
+                top_score[j] = s;
+                top_slot[j] = at;
+                s = ts;
+                at = th;
+            }
+    }
+    Ranked r = {0, -1};
+    for (int k = 0; k <= want; ++k) {
+        r = first_ranked(top_score[0], top_slot[0], red);
+        if (r.slot < 0) break;
+        if (top_slot[0] == r.slot) {
+#pragma unroll
+            for (int j = 0; j + 1 < DEPTH; ++j) {
+                top_score[j] = top_score[j + 1];
+                top_slot[j] = top_slot[j + 1];
+            }
+            top_slot[DEPTH - 1] = -1;
+        }
+    }
+    return r;
+}
 
 }  // namespace
 

@@ -315,7 +315,7 @@ extern "C" int cpn_ransac_score_h(const double* H, const uint8_t* valid, const f
     if (Hn == 0) return 0;                                 // no slot: partial holds nothing
     const dim3 grid(cpn_cdiv(Hn, SCORE_NT), cpn_cdiv(N, CH), B);
     hipLaunchKernelGGL(ransac_score_kernel<TransferRule>, grid, dim3(SCORE_NT), 0, (hipStream_t)stream, H, valid, xy, count, intrinsics,
-                       (const float*)nullptr, N, Hn, inlier_px, partial);
+                       (const float*)nullptr, N, Hn, 0, Hn, inlier_px, partial);
     CPN_LAUNCH_CHECK("cpn_ransac_score_h");
     return 0;
 }

@@ -3,6 +3,7 @@
 // rounding per operation, sums left to right as the parentheses say; the units that include this are built with
 // -ffp-contract=off.  Cam is pinhole.h's.
 #pragma once
+#include "common.h"
 #include "pinhole.h"
 
 #include <math.h>
@@ -59,6 +60,15 @@ __device__ __forceinline__ bool residual_ok(const Sampson& s, double r) {
 __device__ __forceinline__ bool within(const Sampson& s, double px) {
     const double r = s.n / sqrt(s.D);
     return residual_ok(s, r) && fabs(r) <= px;
+}
+// .. and weighs, in round 24's fixed-point MSAC, 0 where it is no inlier and otherwise floor(2^20 (1 - r^2 / px^2)) held to
+// [0, 2^20] (2^20 for px == 0; 0 where the quotient is not a number)
+__device__ __forceinline__ int msac_weight(const Sampson& s, double px) {
+    const double r = s.n / sqrt(s.D);
+    if (!(residual_ok(s, r) && fabs(r) <= px)) return 0;
+    if (!(px > 0.0)) return CPN_MSAC_ONE;
+    const double v = floor((double)CPN_MSAC_ONE * (1.0 - (r * r) / (px * px)));
+    return v >= (double)CPN_MSAC_ONE ? CPN_MSAC_ONE : (v > 0.0 ? (int)v : 0);
 }
 
 }  // namespace

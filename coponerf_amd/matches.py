@@ -11,7 +11,9 @@ round.  The reference uses them for the cycle loss and a warped panel only.  Her
   refine_pose   robust Gauss-Newton of the relative pose on the Sampson residuals of the matches: cpn_refine_pose, one launch
   ransac_pose   the relative pose from the matches ALONE: 8-point RANSAC, cpn_ransac_hypotheses / _score / _finish, three
                 launches; with it the inlier count of rel_pose under the same rule and an inlier mask; solver="5pt" takes
-                minimal samples instead (cpn_ransac_hypotheses5, up to 10 solutions each)
+                minimal samples instead (cpn_ransac_hypotheses5, up to 10 solutions each); score="msac" and lo=K (round 24,
+                opt-in) grade the inliers and polish the K best hypotheses inside the loop (cpn_ransac_score_slots /
+                _polish / _finish_lo)
   homography_pose  the same RANSAC with a homography as its model, for walls, floors and pure rotations, where the essential
                 matrix is under-determined: cpn_ransac_homographies / _score_h / _finish_h, three launches; with it the twin
                 pose, the singular values of H and the statistics that say which regime a pair is in
@@ -225,7 +227,8 @@ def refine_pose(matches: Matches, intrinsics: torch.Tensor, rel_pose: torch.Tens
 
 @torch.no_grad()
 def ransac_pose(matches: Matches, intrinsics: torch.Tensor, rel_pose: Optional[torch.Tensor] = None, hypotheses: int = 1024,
-                inlier_px: float = 1.0, seed: int = 0, solver: str = "8pt") -> Dict[str, torch.Tensor]:
+                inlier_px: float = 1.0, seed: int = 0, solver: str = "8pt", score: str = "inliers", lo: int = 0, lo_iters: int = 4,
+                lo_scale_px: Optional[float] = None) -> Dict[str, torch.Tensor]:
     """cpn_ransac_hypotheses, cpn_ransac_score, cpn_ransac_finish: `hypotheses` linear 8-point solutions from samples drawn by
     a counter hash of (seed, hypothesis, draw) - the same for every pair -, each scored by its matches within inlier_px of
     Sampson residual, the best split into the pose that puts its inliers in front of both cameras.  float64 inside, three
@@ -241,9 +244,31 @@ def ransac_pose(matches: Matches, intrinsics: torch.Tensor, rel_pose: Optional[t
     SLOT (its sample is stats[2] // 10) and stats[3] the number of valid slots.  Unlike the 8-point solver it is not degenerate
     where the matches lie on one plane (a wall, a floor); a purely planar scene keeps a two-fold ambiguity that only the vote
     on the depths breaks, and a pure rotation gives E = 0 for either solver.  Status 2 stays "fewer than 8 usable matches".
-    Three launches as well, with 10 times the slots to score."""
+    Three launches as well, with 10 times the slots to score.
+    LO-MSAC (round 24 of the header), opt-in: score="msac" grades an inlier by floor(2^20 (1 - r^2 / inlier_px^2)) instead of
+    counting it, an integer still; lo=K (0 .. 16) polishes the K best-scoring slots by lo_iters passes of refine_pose's
+    Gauss-Newton on all matches (weights of scale lo_scale_px, None: inlier_px) inside the loop, scores them as slots
+    `slots` .. `slots` + K - 1 and lets the finish choose among all: a polished slot wins only where it scores strictly higher.
+    With score="inliers" and lo=0 the call is the three launches above; otherwise hypotheses, cpn_ransac_score_slots,
+    cpn_ransac_finish_lo are three launches too, and lo > 0 adds cpn_ransac_polish and a second cpn_ransac_score_slots on the K
+    new slots alone: five.  Nothing is read on the host.  stats keep their meaning: [0] is the winner's inlier COUNT under either
+    score, [2] the winning slot - at or beyond `slots` a polished one - and [3] counts the valid slots among all slots + K.  With
+    either keyword off its default the result gains `score` (B,) int64, the winner's score (in units of 2^-20 inlier for "msac", the count otherwise), and `lo`
+    (B, 4) float64: whether a polished slot won, the slot it was polished from and that slot's rank (-1 where none won), and the
+    passes made."""
     if solver not in _SOLVERS:
         raise ValueError(f"ransac_pose: solver must be one of {_SOLVERS}, got {solver!r}")
+    if score not in _SCORES:
+        raise ValueError(f"ransac_pose: score must be one of {_SCORES}, got {score!r}")
+    if isinstance(lo, bool) or not isinstance(lo, int) or not 0 <= lo <= _hip.CONSTANTS["RANSAC_LO_MAX"]:
+        raise ValueError(f"ransac_pose: lo must be an integer in 0 .. {_hip.CONSTANTS['RANSAC_LO_MAX']}, got {lo!r}")
+    if isinstance(lo_iters, bool) or not isinstance(lo_iters, int) or lo_iters < 0:
+        raise ValueError(f"ransac_pose: lo_iters must be an integer >= 0, got {lo_iters!r}")
+    if lo_scale_px is not None and not 0.0 < float(lo_scale_px) < float("inf"):
+        raise ValueError(f"ransac_pose: lo_scale_px must be None or finite and > 0, got {lo_scale_px!r}")
+    if lo and lo_scale_px is None and not float(inlier_px) > 0.0:
+        raise ValueError(f"ransac_pose: lo > 0 with lo_scale_px None takes inlier_px as the scale, which must be > 0; got lo = {lo}, "
+                         f"inlier_px = {inlier_px}")
     per = 10 if solver == "5pt" else 1                              # hypothesis slots per sample
     xy, count = matches.xy, matches.count
     named = [("matches.xy", xy, torch.float32, None), ("intrinsics", intrinsics, torch.float32, None)]
@@ -255,10 +280,12 @@ def ransac_pose(matches: Matches, intrinsics: torch.Tensor, rel_pose: Optional[t
     Hn, px, seed = int(hypotheses), float(inlier_px), int(seed)
     chunks = -(-N // _hip.CONSTANTS["RANSAC_CHUNK"])
     slots = per * Hn
-    if not 0 <= slots <= 2 ** 20 or not 1 <= B <= 32767 or N > 2 ** 24 or B * chunks * (slots + 1) >= 2 ** 31:
+    if not 0 <= slots <= 2 ** 20 - lo or not 1 <= B <= 32767 or N > 2 ** 24 or B * chunks * (slots + lo + 1) >= 2 ** 31:
         what = "hypotheses" if per == 1 else f"{per} hypotheses"
+        what = what if lo == 0 else f"{what} + lo"
         raise ValueError(f"ransac_pose: need 0 <= {what} <= 2^20, 1 <= B <= 32767, N <= 2^24 and B ceil(N / "
-                         f"{_hip.CONSTANTS['RANSAC_CHUNK']}) ({what} + 1) < 2^31, got hypotheses = {hypotheses}, B = {B}, N = {N}")
+                         f"{_hip.CONSTANTS['RANSAC_CHUNK']}) ({what} + 1) < 2^31, got hypotheses = {hypotheses}, lo = {lo}, B = {B}, "
+                         f"N = {N}")
     if not 0.0 <= px < float("inf"):
         raise ValueError(f"ransac_pose: need a finite inlier_px >= 0, got {inlier_px}")
     if not -2 ** 63 <= seed < 2 ** 63:
@@ -267,21 +294,40 @@ def ransac_pose(matches: Matches, intrinsics: torch.Tensor, rel_pose: Optional[t
     E = torch.empty(B, max(slots, 1), 9, dtype=torch.float64, device=dev)
     sample = torch.empty(B, max(Hn, 1), 5 if per == 10 else 8, dtype=torch.int32, device=dev)
     valid = torch.empty(B, max(slots, 1), dtype=torch.uint8, device=dev)
-    partial = torch.empty(B, chunks, slots + 1, dtype=torch.int32, device=dev)
+    partial = torch.empty(B, chunks, slots + lo + 1, dtype=torch.int32, device=dev)
     pose = torch.empty(B, 4, 4, dtype=torch.float32, device=dev)
     inlier = torch.empty(B, N, dtype=torch.uint8, device=dev)
     stats = torch.empty(B, 8, dtype=torch.float64, device=dev)
     rel = 0 if rel_pose is None else rel_pose.data_ptr()
+    graded = 1 if score == "msac" else 0
     with torch.cuda.device(dev):
         s = _hip.stream_handle()
         if Hn:
             _hip.call("cpn_ransac_hypotheses5" if per == 10 else "cpn_ransac_hypotheses", xy.data_ptr(), count.data_ptr(),
                       intrinsics.data_ptr(), B, N, Hn, seed, E.data_ptr(), sample.data_ptr(), valid.data_ptr(), s)
-        _hip.call("cpn_ransac_score", E.data_ptr(), valid.data_ptr(), xy.data_ptr(), count.data_ptr(), intrinsics.data_ptr(), rel, B, N,
-                  slots, px, partial.data_ptr(), s)
-        _hip.call("cpn_ransac_finish", E.data_ptr(), valid.data_ptr(), partial.data_ptr(), xy.data_ptr(), count.data_ptr(),
-                  intrinsics.data_ptr(), rel, B, N, slots, px, pose.data_ptr(), inlier.data_ptr(), stats.data_ptr(), s)
-    return {"pose": pose, "inlier": inlier, "stats": stats}
+        if not graded and lo == 0:                                  # round 20's path, as it was
+            _hip.call("cpn_ransac_score", E.data_ptr(), valid.data_ptr(), xy.data_ptr(), count.data_ptr(), intrinsics.data_ptr(), rel, B,
+                      N, slots, px, partial.data_ptr(), s)
+            _hip.call("cpn_ransac_finish", E.data_ptr(), valid.data_ptr(), partial.data_ptr(), xy.data_ptr(), count.data_ptr(),
+                      intrinsics.data_ptr(), rel, B, N, slots, px, pose.data_ptr(), inlier.data_ptr(), stats.data_ptr(), s)
+            return {"pose": pose, "inlier": inlier, "stats": stats}
+        E_lo = torch.empty(B, max(lo, 1), 9, dtype=torch.float64, device=dev)
+        valid_lo = torch.empty(B, max(lo, 1), dtype=torch.uint8, device=dev)
+        info = torch.empty(B, max(lo, 1), 8, dtype=torch.float64, device=dev)
+        won = torch.empty(B, dtype=torch.int64, device=dev)
+        lo_out = torch.empty(B, 4, dtype=torch.float64, device=dev)
+        _hip.call("cpn_ransac_score_slots", E.data_ptr(), valid.data_ptr(), xy.data_ptr(), count.data_ptr(), intrinsics.data_ptr(), rel, B,
+                  N, slots, 0, slots + lo, graded, px, partial.data_ptr(), s)
+        if lo:
+            _hip.call("cpn_ransac_polish", E.data_ptr(), valid.data_ptr(), partial.data_ptr(), xy.data_ptr(), count.data_ptr(),
+                      intrinsics.data_ptr(), B, N, slots, lo, lo_iters, px, float(px if lo_scale_px is None else lo_scale_px),
+                      E_lo.data_ptr(), valid_lo.data_ptr(), info.data_ptr(), s)
+            _hip.call("cpn_ransac_score_slots", E_lo.data_ptr(), valid_lo.data_ptr(), xy.data_ptr(), count.data_ptr(),
+                      intrinsics.data_ptr(), rel, B, N, lo, slots, slots + lo, graded, px, partial.data_ptr(), s)
+        _hip.call("cpn_ransac_finish_lo", E.data_ptr(), valid.data_ptr(), E_lo.data_ptr(), valid_lo.data_ptr(), info.data_ptr(),
+                  partial.data_ptr(), xy.data_ptr(), count.data_ptr(), intrinsics.data_ptr(), rel, B, N, slots, lo, graded, px,
+                  pose.data_ptr(), inlier.data_ptr(), stats.data_ptr(), won.data_ptr(), lo_out.data_ptr(), s)
+    return {"pose": pose, "inlier": inlier, "stats": stats, "score": won, "lo": lo_out}
 
 
 @torch.no_grad()
@@ -445,7 +491,7 @@ def model_gric(matches: Matches, intrinsics: torch.Tensor, pose_e: torch.Tensor,
 @torch.no_grad()
 def select_pose(matches: Matches, intrinsics: torch.Tensor, rel_pose: Optional[torch.Tensor] = None, hypotheses: int = 1024,
                 inlier_px: float = 1.0, seed: int = 0, solver: str = "8pt", sigma_px: float = 0.5, iters: int = 10,
-                scale_px: float = 2.0) -> Dict:
+                scale_px: float = 2.0, **lo_msac) -> Dict:
     """The pose of two photos without knowing whether they show a room, a wall or a turn on a tripod: ransac_pose and refine_pose
     from its pose (E); homography_pose with min_baseline 0 and refine_homography in both modes from its H (the plane, the rotation
     alone); cpn_ransac_score_h and cpn_ransac_finish_h on ONE slot, the refined plane, for its decomposition, vote and twin;
@@ -457,12 +503,15 @@ def select_pose(matches: Matches, intrinsics: torch.Tensor, rel_pose: Optional[t
     producers' dicts: `ransac`, `refined`, `homography`, `plane` (the one-slot finish's dict - pose, twin, H with sigma_2 = 1,
     inlier, stats - with `H_refined`, the unit h, and `refine_stats` beside it) and `rotation` (refine_homography's).
     The verdict is only as good as the refinement: on the unrefined RANSAC winners GRIC misreads the pure rotation (README, round
-    23).  sigma_px is this package's choice and untried on a trained checkpoint."""
+    23).  sigma_px is this package's choice and untried on a trained checkpoint.  ransac_pose's score, lo, lo_iters and lo_scale_px
+    (round 24) are handed on to it: two more launches with lo > 0, and `ransac` gains its keys `score` and `lo`."""
     if solver not in _SOLVERS:
         raise ValueError(f"select_pose: solver must be one of {_SOLVERS}, got {solver!r}")
+    if set(lo_msac) - _LO_KEYWORDS:
+        raise ValueError(f"select_pose: unknown keywords {sorted(set(lo_msac) - _LO_KEYWORDS)}")
     if not 0.0 < float(sigma_px) < float("inf"):
         raise ValueError(f"select_pose: need a finite sigma_px > 0, got {sigma_px}")
-    found = ransac_pose(matches, intrinsics, rel_pose, hypotheses=hypotheses, inlier_px=inlier_px, seed=seed, solver=solver)
+    found = ransac_pose(matches, intrinsics, rel_pose, hypotheses=hypotheses, inlier_px=inlier_px, seed=seed, solver=solver, **lo_msac)
     refined = refine_pose(matches, intrinsics, found["pose"], iters=iters, scale_px=scale_px)
     homog = homography_pose(matches, intrinsics, rel_pose, hypotheses=hypotheses, inlier_px=inlier_px, seed=seed, min_baseline=0.0)
     flat = refine_homography(matches, intrinsics, homog["H"], model="plane", iters=iters, scale_px=scale_px)
@@ -502,6 +551,8 @@ _STARTS = ("network", "ransac", "best")
 _S_STARTS = ("network", "selected")
 _H_STARTS = ("network", "homography")
 _SOLVERS = ("8pt", "5pt")
+_SCORES = ("inliers", "msac")
+_LO_KEYWORDS = {"score", "lo", "lo_iters", "lo_scale_px"}
 
 
 def _ransac_keywords(who: str, ransac: Dict) -> Tuple[Dict, str]:
@@ -511,7 +562,7 @@ def _ransac_keywords(who: str, ransac: Dict) -> Tuple[Dict, str]:
     start = kw.pop("start", "network")
     if start not in _STARTS:
         raise ValueError(f"{who}: ransac['start'] must be one of {_STARTS}, got {start!r}")
-    unknown = set(kw) - {"hypotheses", "inlier_px", "seed", "solver"}
+    unknown = set(kw) - {"hypotheses", "inlier_px", "seed", "solver"} - _LO_KEYWORDS
     if unknown:
         raise ValueError(f"{who}: ransac holds unknown keywords {sorted(unknown)}")
     if kw.get("solver", "8pt") not in _SOLVERS:
@@ -540,7 +591,7 @@ def _select_keywords(who: str, select_kw: Dict) -> Tuple[Dict, str]:
     start = kw.pop("start", "network")
     if start not in _S_STARTS:
         raise ValueError(f"{who}: select['start'] must be one of {_S_STARTS}, got {start!r}")
-    unknown = set(kw) - {"hypotheses", "inlier_px", "seed", "solver", "sigma_px", "iters", "scale_px"}
+    unknown = set(kw) - {"hypotheses", "inlier_px", "seed", "solver", "sigma_px", "iters", "scale_px"} - _LO_KEYWORDS
     if unknown:
         raise ValueError(f"{who}: select holds unknown keywords {sorted(unknown)}")
     if kw.get("solver", "8pt") not in _SOLVERS:
@@ -554,7 +605,8 @@ def from_flows(flow: Sequence[torch.Tensor], intrinsics: torch.Tensor, rel_pose:
                scale_px: float = 2.0, ransac: Optional[Dict] = None, homography: Optional[Dict] = None,
                select: Optional[Dict] = None) -> Dict:
     """from_pair's second half, for flows and a pose that get_z has already returned: four launches and the mask between them,
-    no host read.  ransac: None, or a dict of ransac_pose's keywords (hypotheses, inlier_px, seed, solver) and `start`: three more
+    no host read.  ransac: None, or a dict of ransac_pose's keywords (hypotheses, inlier_px, seed, solver, and round 24's score, lo,
+    lo_iters, lo_scale_px: two more launches with lo > 0) and `start`: three more
     launches, and the result gains the key `ransac` (ransac_pose's dict).  start="network" (the default) refines from rel_pose
     as without it, "ransac" from RANSAC's pose, "best" per pair from the one with more inliers under ransac_pose's rule (a tie
     and a status other than 0 go to rel_pose; chosen by torch.where on the device).

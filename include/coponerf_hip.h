@@ -1083,7 +1083,7 @@ int cpn_raster_resolve(const unsigned long long* zbuf, const float* xyz, const u
  * inlier count of rel_pose under the same rule, and an inlier mask.  The symbols are additive: the ABI version stays.  The
  * sampler, the solver, the threshold, the scoring and the choice among the four poses are THIS LIBRARY'S definitions.  There is
  * no local optimisation inside the loop (cpn_refine_pose afterwards is that step), no adaptive stopping, no MSAC / MAGSAC
- * scoring; the linear 8-point solver is degenerate for a planar scene and for a pure rotation (round 21 adds the 5-point solver).
+ * scoring (round 24 adds a graded score and the local optimisation, both opt-in); the linear 8-point solver is degenerate for a planar scene and for a pure rotation (round 21 adds the 5-point solver).
  * Conventions: round 16's.  xy (B, N, 4) fp32 = (x0, y0, x1, y1) with count (B) int32 on the device, n = min(max(count, 0), N);
  *   rows at and beyond n are never read.  a = ((x0 - cx0) / fx0, (y0 - cy0) / fy0, 1), b likewise of view 1, float64 from the
  *   fp32 inputs.  X0 = R X1 + t, E = [t]x R, a^T E b = 0; E (.., 9) float64 row-major.  One rounding per operation, sums left to
@@ -1326,6 +1326,59 @@ int cpn_refine_homography(const float* xy, const int* count, const float* intrin
 int cpn_model_gric(const float* xy, const int* count, const float* intrinsics, const float* pose_e, const double* H_plane,
                    const double* H_rot, const uint8_t* avail, const double* ln4n, int B, int N, double sigma_px, double* gric,
                    uint8_t* label, double* stats, void* stream);
+
+/* ==== LO-MSAC for round 20's RANSAC: a graded integer score and local optimisation inside the loop (round 24) ==============
+ * Round 20's loop scores a hypothesis by a bare inlier count and refines only the one that wins.  Three additive symbols - the ABI
+ * version stays - give it a graded score and let the K best-scoring hypotheses be polished BEFORE the winner is chosen, on the
+ * device: a fixed number of launches, no atomics, nothing read on the host, bit-reproducible, a pair's result independent of the
+ * batch.  Both parts are opt-in: cpn_ransac_score and cpn_ransac_finish are what they were.  Both solvers (rounds 20 and 21) fill
+ * the hypothesis buffers; Hn below is the number of SLOTS (10 per sample for the 5-point solver).  Conventions, the residual, the
+ * inlier rule, the split, the vote, the norm and sign of E: round 20's.  THE 2^20 FIXED POINT, K, THE NUMBER OF PASSES, THE
+ * SCALE OF THE WEIGHTS AND THE RANK AND TIE RULES ARE THIS LIBRARY'S definitions; none of them has been tried on a trained
+ * checkpoint.  Shapes: 1 <= B <= 32767, 1 <= N <= 2^24, 0 <= K <= CPN_RANSAC_LO_MAX, Hn + K <= 2^20 and
+ * B ceil(N / CPN_RANSAC_CHUNK) (Hn + K + 1) < 2^31 (CPN_E_SHAPE otherwise); inlier_px finite and >= 0, graded 0 or 1, iters >= 0,
+ * scale_px finite and > 0 (CPN_E_ARG otherwise).
+ * THE GRADED SCORE: the WEIGHT of a match under a slot's E is 0 where the match is no inlier of the slot (round 20's rule) and
+ *   otherwise floor(CPN_MSAC_ONE (1 - (r r) / (inlier_px inlier_px))) in float64, held to [0, CPN_MSAC_ONE], with r the round-16
+ *   residual; CPN_MSAC_ONE where inlier_px == 0; 0 where the quotient is not a number.  A slot's score is the sum of its weights:
+ *   an integer in units of 2^-20 inlier, at most 2^28 over a chunk (an int32 partial) and 2^44 over a pair (summed in int64).
+ * cpn_ransac_score_slots: cpn_ransac_score's launch on a RANGE of a wider row.  E (B, Hn, 9) and valid (B, Hn) are scored into
+ *   columns first .. first + Hn - 1 of partial (B, ceil(N / CPN_RANSAC_CHUNK), total + 1) int32, first + Hn <= total; the call
+ *   with first + Hn == total also scores rel_pose's own E into column `total` (0 there without rel_pose).  graded 0: the inlier
+ *   counts of cpn_ransac_score; 1: the sums of weights.  The other columns are not touched; a call with nothing to score launches
+ *   nothing.
+ * cpn_ransac_polish (K >= 1): ONE launch, grid (K, B), one workgroup per (rank k, pair).  partial (B, chunks, Hn + K + 1) holds
+ *   the scores of the Hn hypotheses in its first Hn columns.  THE RANK: the order of the valid hypotheses is (score descending,
+ *   slot ascending) with the score the int64 sum of the slot's partials below n; rank k is the k-th of that order from 0.
+ *   Where usable < 8 (round 20's count) or there are no more than k valid hypotheses, polished slot k is INVALID: E_lo 0,
+ *   valid_lo 0, info (-1, -1, 0, 0, 0, 0, 0, 2).  Otherwise the slot's E is split and its inliers under inlier_px vote exactly as
+ *   in cpn_ransac_finish (a split that is not finite: invalid with info [7] = 3 and [0], [1] = -1); the picked candidate (R, +-t)
+ *   is the start of cpn_refine_pose's passes - the same sums in the same order, the same damping, gauge, Cholesky solve and
+ *   Rodrigues step - over ALL rows below n with weights 1 / (1 + (r / scale_px)^2)^2: `iters` updates, ended early by a failed
+ *   solve, which keeps the state before it.  E_lo (B, K, 9) float64 = [t]x R of the final state in round 16's expression,
+ *   normalised and signed as cpn_ransac_hypotheses' E; valid_lo (B, K) bytes; info (B, K, 8) float64: [0] the slot polished,
+ *   [1] its rank k, [2] the updates made, [3 - 6] the four vote counts, [7] 0 ok, 1 a failed solve (the slot is valid all the
+ *   same), 2, 3 as above (3 also where E_lo is not finite).  Every element of the three outputs is written.
+ * cpn_ransac_finish_lo: cpn_ransac_finish over Hn + K slots, slot Hn + k the polished slot k, partial (B, chunks, Hn + K + 1)
+ *   with rel_pose's column last.  The winner is the valid slot with the largest int64 sum, the LOWER slot on ties: a polished
+ *   slot wins only where it scores strictly higher, so the winning score never falls below that of the hypotheses alone.  graded
+ *   says which score partial holds.  pose, inlier and stats as cpn_ransac_finish's: [0] stays the winner's INLIERS and [4] those
+ *   of rel_pose - with graded 1 both are counted in the pass that writes `inlier` -, [2] is the winning slot (>= Hn: a polished
+ *   one), [3] counts the valid ones among all Hn + K.  score (B) int64: the winner's score, 0 where the status is not 0.  lo
+ *   (B, 4) float64: [0] 1 where a polished slot won, else 0; [1] the slot it was polished from, [2] that slot's rank (both -1
+ *   where none won); [3] the updates made (0 where none won).  K may be 0 (E_lo, valid_lo and info are then not read).      */
+#define CPN_MSAC_ONE 1048576
+#define CPN_RANSAC_LO_MAX 16
+int cpn_ransac_score_slots(const double* E, const uint8_t* valid, const float* xy, const int* count, const float* intrinsics,
+                           const float* rel_pose, int B, int N, int Hn, int first, int total, int graded, double inlier_px,
+                           int* partial, void* stream);
+int cpn_ransac_polish(const double* E, const uint8_t* valid, const int* partial, const float* xy, const int* count,
+                      const float* intrinsics, int B, int N, int Hn, int K, int iters, double inlier_px, double scale_px,
+                      double* E_lo, uint8_t* valid_lo, double* info, void* stream);
+int cpn_ransac_finish_lo(const double* E, const uint8_t* valid, const double* E_lo, const uint8_t* valid_lo, const double* info,
+                         const int* partial, const float* xy, const int* count, const float* intrinsics, const float* rel_pose,
+                         int B, int N, int Hn, int K, int graded, double inlier_px, float* pose, uint8_t* inlier, double* stats,
+                         long long* score, double* lo, void* stream);
 
 #ifdef __cplusplus
 }
