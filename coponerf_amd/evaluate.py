@@ -13,6 +13,10 @@ pair.  Here
 `pipeline.render_images` without stalling it.  LPIPS (test.py:149, 258-263) is `coponerf_amd.lpips.LPIPS`, on
 the user's own weight files (none are part of this package): `Evaluator(extra={"lpips": LPIPS.from_files(...).to(dev)})` adds
 its column, and `extra` takes any other callable `fn(pred, target) -> (N,)` the same way.
+
+`Evaluator(geometry={...})` (round 25) also scores every pose `matches.from_flows` returns - the refined, RANSAC's,
+the homography's, the selected one - against the ground truth in float64 (csrc/pose_eval.hip: cpn_pose_errors), measures the matches'
+residuals under the true pose (cpn_residual_stats) and summarises each source by `pose_auc`.  Without the keyword nothing changes.
 """
 from __future__ import annotations
 
@@ -26,6 +30,14 @@ from . import _hip
 
 COLUMNS = ("mse", "psnr", "ssim", "rot", "trans", "angle_trans", "overlap", "call")
 BUCKETS = ("small", "medium", "large")
+# Evaluator(geometry=...): the poses from_flows can return, in the order of their columns; what is measured of the matches; the
+# labels of select_pose's `model` (0, 1, 2; -1 is "none"); the thresholds of the AUC in degrees
+SOURCES = ("network", "refined", "ransac", "homography", "select")
+QUALITY = ("matches", "usable_gt", "med_gt", "in_gt", "sigma_gt", "med_network", "in_network")
+MODELS = ("E", "plane", "rotation")
+AUC_AT = (5, 10, 20)
+_GEOMETRY_KEYS = ("S", "refine", "max_cycle_px", "max_epi_px", "stride", "iters", "scale_px", "ransac", "homography", "select",
+                  "inlier_px")
 WIN = 11                                                  # structural_similarity(win_size=11): the smallest image side
 
 
@@ -112,6 +124,39 @@ def _mean(values: Sequence[float]) -> float:
     return math.fsum(values) / len(values)                 # np.mean of Python floats, without its rounding
 
 
+def _stats64(values: Sequence[float]) -> Dict[str, float]:
+    """_stats of float64 values, kept in float64: the rot64 / angle64 columns resolve what fp32 would round away."""
+    t = torch.tensor(list(values), dtype=torch.float64)
+    return {"mean": float(t.mean()), "median": float(t.median()), "std": float(t.std()) if t.numel() > 1 else float("nan")}
+
+
+def _nanmean(values: Sequence[float]) -> float:
+    """The mean of the values that are numbers; NaN where none is."""
+    kept = [v for v in values if v == v]
+    return _mean(kept) if kept else float("nan")
+
+
+def pose_auc(errors: Sequence[float], thresholds: Sequence[float] = AUC_AT) -> List[float]:
+    """The area under the recall curve of `errors` up to each threshold, normalised by the threshold: the pose literature's
+    exact trapezoid over the sorted errors - the curve runs through (0, 0) and (e_i, i / n) for the i-th smallest error and is
+    cut at the threshold with the recall of the last error below it.  A NaN error is a miss: it counts in n and is never
+    recalled.  Host, float64."""
+    errs = sorted(float("inf") if e != e else float(e) for e in errors)
+    n = len(errs)
+    out = []
+    for t in thresholds:
+        xs, ys = [0.0], [0.0]
+        for i, e in enumerate(errs):
+            if not e < t:
+                break
+            xs.append(e)
+            ys.append((i + 1) / n)
+        xs.append(float(t))
+        ys.append(ys[-1])
+        out.append(math.fsum((xs[i + 1] - xs[i]) * (ys[i + 1] + ys[i]) / 2.0 for i in range(len(xs) - 1)) / t if n else float("nan"))
+    return out
+
+
 def _to_device(obj, dev):
     if torch.is_tensor(obj):
         return obj if obj.device == dev else obj.to(dev, non_blocking=True)
@@ -131,14 +176,47 @@ class Evaluator:
 
     A row per image: COLUMNS, then one column per entry of `extra`.  The table is float64 (fp32 metrics, overlaps and call
     indices are all exact in it), preallocated at `capacity` rows and doubled when it fills.  `host_reads` counts the device
-    -> host reads made here: `add` and `run` make none, `summary`, `format_summary` and `rows(host=True)` one each."""
+    -> host reads made here: `add` and `run` make none, `summary`, `format_summary` and `rows(host=True)` one each.
 
-    def __init__(self, extra: Optional[Dict[str, Callable]] = None, capacity: int = 256, device=None):
+    geometry: None, or a dict of matches.from_flows' own keywords (S, refine, max_cycle_px, max_epi_px, stride, iters, scale_px,
+    ransac, homography, select) and `inlier_px` (1.0).  `add` then needs `intrinsics`, runs from_flows on the batch's flows and
+    pose and scores EVERY pose it returns against the ground truth - `self.sources`, of SOURCES: network, refined (unless
+    refine=False), ransac, homography, select - in float64: per source s the columns `rot64_s`, `trans64_s`, `angle64_s`
+    (matches.pose_errors: radians and scene units, as the built-in ones), then QUALITY: `matches` (the pair's count), and of the
+    matches' Sampson residuals under the GROUND-TRUTH pose `usable_gt`, `med_gt` (the median |r| in pixels), `in_gt` (the share
+    within inlier_px), `sigma_gt` (matches.residual_stats' sigma[1]), under the network's pose `med_network`, `in_network`; with
+    select `model`, select_pose's label.  Two more launches beside from_flows' own and still no host read.  Without the keyword
+    nothing changes: no launch, no column, no key."""
+
+    def __init__(self, extra: Optional[Dict[str, Callable]] = None, capacity: int = 256, device=None,
+                 geometry: Optional[Dict] = None):
         self.extra: Dict[str, Callable] = dict(extra or {})
         for name in self.extra:
             if name in COLUMNS:
                 raise ValueError(f"Evaluator: extra metric {name!r} collides with a built-in column")
         self.columns: Tuple[str, ...] = COLUMNS + tuple(self.extra)
+        self.geometry: Optional[Dict] = None
+        self.sources: Tuple[str, ...] = ()
+        if geometry is not None:
+            if not isinstance(geometry, dict):
+                raise ValueError(f"Evaluator: geometry must be None or a dict of from_flows' keywords and inlier_px, got "
+                                 f"{type(geometry).__name__}")
+            unknown = set(geometry) - set(_GEOMETRY_KEYS)
+            if unknown:
+                raise ValueError(f"Evaluator: geometry holds unknown keywords {sorted(unknown)}; it takes {_GEOMETRY_KEYS}")
+            self.geometry = dict(geometry)
+            self._inlier_px = float(self.geometry.pop("inlier_px", 1.0))
+            if not 0.0 <= self._inlier_px < float("inf"):
+                raise ValueError(f"Evaluator: geometry['inlier_px'] must be finite and >= 0, got {geometry['inlier_px']}")
+            on = {"network": True, "refined": bool(self.geometry.get("refine", True))}
+            on.update({k: self.geometry.get(k) is not None for k in ("ransac", "homography", "select")})
+            self.sources = tuple(s for s in SOURCES if on[s])
+            names = tuple(f"{c}_{s}" for s in self.sources for c in ("rot64", "trans64", "angle64")) + QUALITY
+            names += ("model",) if on["select"] else ()
+            clash = set(names) & set(self.columns)
+            if clash:
+                raise ValueError(f"Evaluator: extra metrics {sorted(clash)} collide with the geometry columns")
+            self.columns += names
         self._capacity = max(1, int(capacity))
         self._device = torch.device(device) if device is not None else None
         self._table: Optional[torch.Tensor] = None
@@ -181,11 +259,15 @@ class Evaluator:
         return ov
 
     @torch.no_grad()
-    def add(self, model_output: Dict, gt_rgb, overlap=None, image_shape: Optional[Sequence[int]] = None) -> None:
+    def add(self, model_output: Dict, gt_rgb, overlap=None, image_shape: Optional[Sequence[int]] = None,
+            intrinsics: Optional[torch.Tensor] = None) -> None:
         """One rendered batch (test.py:222-296): `model_output` is the joined dict of `forward(val=True)` / `render_images`
         ('rgb', 'rel_pose', 'gt_rel_pose'), `gt_rgb` the ground truth (gt['rgb'], or the gt dict itself), `overlap` one value
         per image (host sequence, tensor, or None: then the images join no bucket).  image_shape=(H, W); None takes a 4-D
-        (B, H, W, 3) shape as it is and a (B, 1, R, 3) one as square.  Enqueues device work only."""
+        (B, H, W, 3) shape as it is and a (B, 1, R, 3) one as square.  With `geometry`, model_output['flow'] and intrinsics
+        (B, 2, 4, 4), `context.intrinsics`, are needed as well.  Enqueues device work only."""
+        if self.geometry is not None and intrinsics is None:
+            raise ValueError("Evaluator.add: geometry needs intrinsics=model_input['context']['intrinsics']")
         rgb = model_output["rgb"].contiguous()              # as forward() and the chunk join return it: no copy
         gt = (gt_rgb["rgb"] if isinstance(gt_rgb, dict) else gt_rgb).contiguous()
         rel, gt_rel = model_output["rel_pose"], model_output["gt_rel_pose"]
@@ -215,8 +297,32 @@ class Evaluator:
             t = gt.view(B, H, W, 3).permute(0, 3, 1, 2)
             for j, fn in enumerate(self.extra.values()):
                 rows[:, len(COLUMNS) + j] = torch.as_tensor(fn(p, t), device=dev).reshape(B)
+        if self.geometry is not None:
+            self._add_geometry(rows, model_output["flow"], rel, gt_rel, intrinsics)
         self._n += B
         self._calls += 1
+
+    def _add_geometry(self, rows: torch.Tensor, flow, rel: torch.Tensor, gt_rel: torch.Tensor, intrinsics: torch.Tensor) -> None:
+        """The geometry columns of a batch: from_flows, ONE cpn_pose_errors on the stack of its poses, ONE cpn_residual_stats on
+        (ground truth, network)."""
+        from . import matches as mt
+        flows = (flow[0].float().contiguous(), flow[1].float().contiguous())
+        K, rel, gt_rel = intrinsics.float().contiguous(), rel.float().contiguous(), gt_rel.float().contiguous()
+        found = mt.from_flows(flows, K, rel, **self.geometry)
+        pose = {"network": rel, "refined": found["pose"]}
+        pose.update({k: found[k]["pose"] for k in ("ransac", "homography", "select") if k in found})
+        errs = mt.pose_errors(torch.stack([pose[s] for s in self.sources], dim=1).contiguous(), gt_rel)
+        at = len(COLUMNS) + len(self.extra)
+        rows[:, at:at + 3 * len(self.sources)] = errs.reshape(errs.shape[0], -1)
+        at += 3 * len(self.sources)
+        st = mt.residual_stats(found["matches"], K, torch.stack((gt_rel, rel), dim=1).contiguous(), q=(0.5,),
+                               thresholds=(self._inlier_px,))
+        share = st["within"][:, :, 0].to(torch.float64) / st["usable"].to(torch.float64)          # 0 / 0: NaN
+        for j, col in enumerate((found["matches"].count, st["usable"][:, 0], st["quant"][:, 0, 0], share[:, 0], st["sigma"][:, 0, 1],
+                                 st["quant"][:, 1, 0], share[:, 1])):
+            rows[:, at + j] = col
+        if "select" in found:
+            rows[:, at + len(QUALITY)] = found["select"]["model"]
 
     @torch.no_grad()
     def run(self, model, loader: Iterable, nchunks: Optional[int] = None, image_shape: Optional[Sequence[int]] = None,
@@ -239,7 +345,8 @@ class Evaluator:
             gt, overlap = pending.popleft()
             if summary_log is not None:
                 summary_log.add(model_input, out, self._calls, image_shape=image_shape)
-            self.add(out, gt, overlap, image_shape=image_shape)
+            self.add(out, gt, overlap, image_shape=image_shape,
+                     intrinsics=model_input["context"]["intrinsics"] if self.geometry is not None else None)
         return self
 
     # ------------------------------------------------------------------------------------------------- reading it back
@@ -260,7 +367,11 @@ class Evaluator:
         Every group has `n`, mean `psnr` / `ssim` / `mse`, `{rot,trans,angle_trans}_{mean,median,std}` and a mean per extra.
         A bucket (test.py:271-272 by the image's overlap) holds per-image values.  "all" follows test.py:246-280 per `add`
         call: the MSE pooled over the call's images, the PSNR of that pooled MSE, the call's mean SSIM, translation angle and
-        extras, and `rot` / `trans` per image.  Groups without entries are omitted."""
+        extras, and `rot` / `trans` per image.  Groups without entries are omitted.
+        With `geometry` every group gains, from its images one by one (in "all" too), per source s
+        `{rot64,angle64}_s_{mean,median,std}` in float64 and `auc5_s`, `auc10_s`, `auc20_s` - pose_auc of max(rot64_s, angle64_s)
+        in degrees -, the mean of every QUALITY column over the images where it is a number, and with select `model_E`,
+        `model_plane`, `model_rotation`, `model_none`: the share of each label."""
         table = self.rows(host=True).tolist()
         c = {name: i for i, name in enumerate(self.columns)}
         groups: Dict[str, Dict[str, List[float]]] = {}
@@ -283,7 +394,8 @@ class Evaluator:
             push("all", mse=mse, psnr=psnr, ssim=_mean([r[c["ssim"]] for r in rs]),
                  rot=[r[c["rot"]] for r in rs], trans=[r[c["trans"]] for r in rs],
                  angle_trans=_mean([r[c["angle_trans"]] for r in rs]),
-                 **{name: _mean([r[c[name]] for r in rs]) for name in self.extra})
+                 **{name: _mean([r[c[name]] for r in rs]) for name in self.extra},
+                 **{name: [r[c[name]] for r in rs] for name in self.columns[len(COLUMNS) + len(self.extra):]})
         out: Dict[str, Dict[str, float]] = {}
         for key in ("all",) + BUCKETS:
             g = groups.get(key)
@@ -297,6 +409,20 @@ class Evaluator:
                     s[f"{name}_{stat}"] = v
             for name in self.extra:
                 s[name] = _mean(g[name])
+            for src in self.sources:
+                for name in ("rot64", "angle64"):
+                    for stat, v in _stats64(g[f"{name}_{src}"]).items():
+                        s[f"{name}_{src}_{stat}"] = v
+                worst = [math.degrees(max(a, b)) if a == a and b == b else float("nan")
+                         for a, b in zip(g[f"rot64_{src}"], g[f"angle64_{src}"])]
+                for t, v in zip(AUC_AT, pose_auc(worst, AUC_AT)):
+                    s[f"auc{t}_{src}"] = v
+            if self.geometry is not None:
+                for name in QUALITY:
+                    s[name] = _nanmean(g[name])
+                if "select" in self.sources:
+                    for label, name in enumerate(MODELS + ("none",)):
+                        s[f"model_{name}"] = sum(1 for v in g["model"] if int(v) == (label if label < len(MODELS) else -1)) / len(g["model"])
             out[key] = s
         return out
 
@@ -314,4 +440,10 @@ class Evaluator:
             parts += [f"Avg_Trans_angle: {s['angle_trans_mean']:.4f}", f"Med_Trans_angle: {s['angle_trans_median']:.4f}",
                       f"std_Trans_angle: {s['angle_trans_std']:.4f}"]
             lines.append(f"{key}: " + ", ".join(parts))
+            for src in self.sources:                        # one more line per group and scored pose, in degrees
+                if f"rot64_{src}_mean" not in s:
+                    continue
+                lines.append(f"{key}/{src}: " + ", ".join(
+                    [f"{label}_{stat}: {math.degrees(s[f'{name}_{src}_{stat}']):.6f}" for label, name in (("Rot64_deg", "rot64"), ("Angle64_deg", "angle64"))
+                     for stat in ("mean", "median", "std")] + [f"AUC@{t}: {s[f'auc{t}_{src}']:.4f}" for t in AUC_AT]))
         return "\n".join(lines)

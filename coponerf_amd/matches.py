@@ -21,6 +21,9 @@ round.  The reference uses them for the cycle loss and a warped panel only.  Her
                 rotation alone (three parameters): cpn_refine_homography, one launch
   model_gric    Torr's GRIC of E, the plane and the rotation alone on the same matches: cpn_model_gric, one launch
   select_pose   all of the above in a row and the picked model's pose: which estimator to believe, decided on the device
+  pose_errors   up to 8 poses per pair against a ground truth in float64, both angles by atan2: cpn_pose_errors, one launch
+  residual_stats  exact quantiles, inlier counts and a robust sigma of the matches' residuals under given poses - under the true
+                pose the evidence the thresholds above should be set by: cpn_residual_stats, one launch
   from_pair     get_z once, then the above (ransac_pose with ransac={...}, homography_pose with homography={...}, select_pose
                 with select={...})
   photo_coords  host: matches of a prepare_pair dict in the coordinates of the original photos
@@ -55,6 +58,7 @@ default inlier_px), the tie rule and the (d, k) table are this package's definit
 """
 from __future__ import annotations
 
+import ctypes
 from typing import Dict, Optional, Sequence, Tuple
 
 import numpy as np
@@ -486,6 +490,90 @@ def model_gric(matches: Matches, intrinsics: torch.Tensor, pose_e: torch.Tensor,
                   H_rot.data_ptr(), avail.data_ptr(), table.data_ptr(), B, N, float(sigma_px), gric.data_ptr(), label.data_ptr(),
                   stats.data_ptr(), _hip.stream_handle())
     return {"gric": gric, "label": label, "stats": stats}
+
+
+def _pose_stack(who: str, poses: torch.Tensor, B: Optional[int] = None) -> Tuple[torch.Tensor, bool]:
+    """poses (B, P, 4, 4), or (B, 4, 4) for P = 1 -> ((B, P, 4, 4), whether the outputs drop the pose axis)."""
+    if not torch.is_tensor(poses) or poses.dim() not in (3, 4) or tuple(poses.shape[-2:]) != (4, 4) or \
+            (B is not None and int(poses.shape[0]) != B):
+        raise ValueError(f"{who}: poses must be (B, P, 4, 4) or (B, 4, 4){'' if B is None else f' with B = {B}'}, got "
+                         f"{tuple(poses.shape) if torch.is_tensor(poses) else type(poses).__name__}")
+    single = poses.dim() == 3
+    poses = poses[:, None] if single else poses
+    top = _hip.CONSTANTS["POSE_EVAL_MAX"]
+    if not 1 <= int(poses.shape[0]) <= 32767 or not 1 <= int(poses.shape[1]) <= top:
+        raise ValueError(f"{who}: need 1 <= B <= 32767 pairs of 1 <= P <= {top} poses, got {tuple(poses.shape)}")
+    return poses, single
+
+
+@torch.no_grad()
+def pose_errors(poses: torch.Tensor, gt: torch.Tensor) -> torch.Tensor:
+    """cpn_pose_errors (round 25 of the header): poses (B, P, 4, 4) fp32 - or (B, 4, 4): P is 1 and the output drops that axis -
+    against gt (B, 4, 4) fp32 -> (B, P, 3) float64: the rotation angle in radians, atan2 of the sine from the antisymmetric part of
+    R R_gt^T and the cosine from its trace; the translation distance in scene units; the angle between the two translation
+    directions in radians, atan2(|t x t_gt|, t . t_gt), NaN for a zero translation.  A pose with a value that is not finite has
+    three NaNs.  One launch, one thread per (pair, pose), float64 inside.  evaluate.pose_metrics is the reference's fp32 acos, whose
+    angle comes in steps of 0.02 degrees near 0; this one resolves 1e-6 degrees and 179.9999."""
+    poses, single = _pose_stack("pose_errors", poses)
+    B, P = int(poses.shape[0]), int(poses.shape[1])
+    device_tensors("pose_errors", (("poses", poses, torch.float32, None), ("gt", gt, torch.float32, (B, 4, 4))))
+    out = torch.empty(B, P, 3, dtype=torch.float64, device=poses.device)
+    with torch.cuda.device(poses.device):
+        _hip.call("cpn_pose_errors", poses.data_ptr(), gt.data_ptr(), B, P, out.data_ptr(), _hip.stream_handle())
+    return out[:, 0] if single else out
+
+
+_LEVELS: Dict = {}
+
+
+def _levels(who: str, what: str, values: Sequence[float], top: float):
+    """The quantiles or thresholds of residual_stats as the C array cpn_residual_stats takes; checked and built once per values."""
+    key = (what, tuple(float(v) for v in values))
+    arr = _LEVELS.get(key)
+    if arr is None:
+        n = _hip.CONSTANTS["POSE_EVAL_MAX"]
+        if not 1 <= len(key[1]) <= n or not all(0.0 <= v <= top for v in key[1]):
+            raise ValueError(f"{who}: {what} must hold 1 .. {n} values in [0, {top}], got {tuple(values)}")
+        arr = _LEVELS[key] = (ctypes.c_double * len(key[1]))(*key[1])
+    return arr
+
+
+@torch.no_grad()
+def residual_stats(matches: Matches, intrinsics: torch.Tensor, poses: torch.Tensor, q: Sequence[float] = (0.5,),
+                   thresholds: Sequence[float] = (1.0,)) -> Dict[str, torch.Tensor]:
+    """cpn_residual_stats (round 25 of the header): the distribution of the matches' Sampson residuals |r| in pixels under each of
+    `poses` (B, P, 4, 4) fp32 - or (B, 4, 4): P is 1 and the outputs drop that axis -, E = [t]x R of the pose; with the ground-truth
+    pose it is the evidence inlier_px, sigma_px and scale_px should be set by.  One launch, one workgroup per (pose, pair), float64
+    inside, nothing read on the host -> `usable` (B, P) int32, the matches whose residual counts; `quant` (B, P, Q) float64, for
+    each of `q` (1 .. 8 values in [0, 1]) the usable |r| of rank floor(q (usable - 1)) in ascending order - one of the residuals in
+    its bits, never an interpolation; 0.5 is torch.median's lower middle -, NaN without a usable match; `within` (B, P, T) int32,
+    the usable matches with |r| <= each of `thresholds` (1 .. 8 finite values >= 0); `sigma` (B, P, 2) float64: [0] Rousseeuw's
+    LMedS scale 1.4826 (1 + 5 / (usable - 5)) median (NaN up to 5 usable matches), [1] sqrt(sum r^2 / (n_in - 5)) over the n_in
+    usable matches within 2.5 [0] (NaN up to 5 of them); `status` (B, P) int32: 0 ok, 1 no usable match, 2 a pose that is not
+    finite or has no translation.  The order statistics are exact: a radix descent on the bit pattern of |r| with the residual
+    recomputed in every pass, no sort, no boolean indexing.  sigma is reported, not fed back: ransac_pose and model_gric take one
+    threshold by value for all pairs.  The rank rule, the LMedS factor with p = 5 and the 2.5 sigma cut are this package's
+    definitions and untried on a trained checkpoint."""
+    xy, count = matches.xy, matches.count
+    B, N = _matches_args("residual_stats", matches)
+    poses, single = _pose_stack("residual_stats", poses, B)
+    device_tensors("residual_stats", (("matches.xy", xy, torch.float32, None), ("intrinsics", intrinsics, torch.float32, None),
+                                      ("poses", poses, torch.float32, None)))
+    _cameras("residual_stats", intrinsics, None, B)
+    if N > 2 ** 24:
+        raise ValueError(f"residual_stats: need N <= 2^24, got N = {N}")
+    qs, ts = _levels("residual_stats", "q", q, 1.0), _levels("residual_stats", "thresholds", thresholds, float(np.finfo(np.float64).max))
+    P, Q, T, dev = int(poses.shape[1]), len(qs), len(ts), xy.device
+    usable = torch.empty(B, P, dtype=torch.int32, device=dev)
+    quant = torch.empty(B, P, Q, dtype=torch.float64, device=dev)
+    within = torch.empty(B, P, T, dtype=torch.int32, device=dev)
+    sigma = torch.empty(B, P, 2, dtype=torch.float64, device=dev)
+    status = torch.empty(B, P, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        _hip.call("cpn_residual_stats", xy.data_ptr(), count.data_ptr(), intrinsics.data_ptr(), poses.data_ptr(), qs, ts, B, N, P, Q, T,
+                  usable.data_ptr(), quant.data_ptr(), within.data_ptr(), sigma.data_ptr(), status.data_ptr(), _hip.stream_handle())
+    out = {"usable": usable, "quant": quant, "within": within, "sigma": sigma, "status": status}
+    return {k: v[:, 0] for k, v in out.items()} if single else out
 
 
 @torch.no_grad()

@@ -1380,6 +1380,47 @@ int cpn_ransac_finish_lo(const double* E, const uint8_t* valid, const double* E_
                          int B, int N, int Hn, int K, int graded, double inlier_px, float* pose, uint8_t* inlier, double* stats,
                          long long* score, double* lo, void* stream);
 
+/* ==== how good is a pose, and how good are the matches under it: float64 pose errors and exact residual quantiles (round 25) ===
+ * Rounds 16 and 20 - 24 estimate poses; this round measures them against a ground truth, on the device, for Evaluator's table.  Two
+ * additive symbols: the ABI version stays.  One launch each, no atomics in global memory, no device value read on the host,
+ * bit-reproducible, and a (pair, pose)'s result does not depend on the batch.  Conventions: round 16's (xy (B, N, 4) fp32 =
+ * (x0, y0, x1, y1), count (B) int32, n = min(max(count, 0), N), rows at and beyond n are never read, intrinsics (B, 2, 4, 4) fp32
+ * with fx, fy, cx, cy at entries 0, 5, 2, 6, a pose row-major [R | t] with X0 = R X1 + t).  1 <= B <= 32767, 1 <= N <= 2^24 and
+ * 1 <= P, Q, T <= CPN_POSE_EVAL_MAX (CPN_E_SHAPE otherwise).  THE RANK RULE, THE LMedS FACTOR WITH p = 5, THE 2.5 SIGMA CUT AND THE
+ * ANGLE FORMULA ARE THIS LIBRARY'S definitions; none of them has been tried on a trained checkpoint.  All float64 from the fp32
+ * inputs, one rounding per operation, sums left to right as the parentheses say; |v| of three values is
+ * sqrt((v_0 v_0 + v_1 v_1) + v_2 v_2).
+ * cpn_pose_errors: one thread per (pair, pose).  poses (B, P, 4, 4) fp32, gt (B, 4, 4) fp32, out (B, P, 3) float64, in the
+ *   reference's units (radians and scene units).  M = R R_gt^T, M_ij = (R_i0 G_j0 + R_i1 G_j1) + R_i2 G_j2.
+ *   [0] the rotation angle atan2(0.5 |(M21 - M12, M02 - M20, M10 - M01)|, (((M00 + M11) + M22) - 1) / 2): the sine from the
+ *   antisymmetric part and the cosine from the trace, so that the angle is well conditioned at 0 and at pi, where acos of the
+ *   cosine alone is not;  [1] the translation distance |t - t_gt|;  [2] the direction angle atan2(|t x t_gt|, t . t_gt) with
+ *   t x g = (t_1 g_2 - t_2 g_1, t_2 g_0 - t_0 g_2, t_0 g_1 - t_1 g_0) and t . g = (t_0 g_0 + t_1 g_1) + t_2 g_2; NaN where t or
+ *   t_gt is (0, 0, 0).  Where one of the twelve values of the pose or of gt is not finite all three are NaN, in that entry alone.
+ *   atan2 is the device library's; the other operations are exact to the last bit.
+ * cpn_residual_stats: grid (P, B), one workgroup of 256 threads per (pose, pair), cpn_refine_pose's shape.  poses (B, P, 4, 4)
+ *   fp32; q (Q) float64, each in [0, 1], and thr (T) float64, each finite and >= 0 (CPN_E_ARG otherwise): HOST arrays, checked
+ *   here and handed to the kernel as arguments - 16 doubles, no copy, and a bad value is a status code.  The residual of a row is
+ *   round 16's r = n / sqrt(D) under E = [t]x R of the pose as it comes (t is not normalised); the row is USABLE iff the
+ *   residual counts (round 16's rule); its key is |r|, so -0 and +0 are one value.
+ *   usable (B, P) int32 = n_u.  quant (B, P, Q) float64 = the element of rank floor(q (n_u - 1)) - the product in float64 - of
+ *   the usable |r| in ascending order: no interpolation, every value is one of the residuals in its bits, and q = 0.5 is the
+ *   lower middle.  within (B, P, T) int32 = the usable rows with |r| <= thr.  sigma (B, P, 2) float64: with med the element of
+ *   rank (n_u - 1) / 2 rounded down, [0] = (1.4826 (1 + 5 / (n_u - 5))) med, Rousseeuw's LMedS scale for p = 5 parameters, NaN for
+ *   n_u <= 5; [1] = sqrt(S / (n_in - 5)) with n_in the usable rows with |r| <= 2.5 [0] and S the sum of their r r in the order of
+ *   a pass of cpn_refine_pose (thread t adds the rows t, t + 256, .. in ascending order from 0, the 64 lanes of a wave by the xor
+ *   butterfly 32 .. 1, the four waves as (0 + 1) + (2 + 3)), NaN for n_in <= 5.  status (B, P) int32: 0 ok; 1 no usable row; 2 a
+ *   pose with a value that is not finite or with t = (0, 0, 0); for 1 and 2 usable and within are 0 and quant and sigma NaN.
+ *   Every element of the five outputs is written.
+ *   THE SELECTION is a radix descent on the 64-bit pattern of |r| (non-negative doubles order as their patterns), 8 bits a pass
+ *   from the top, with the residual recomputed in every pass from the same inputs and the digit counts kept in LDS as integers:
+ *   ten passes over the rows below n, no sort, no scratch in global memory.  N = 131 072 rows and more work.                     */
+#define CPN_POSE_EVAL_MAX 8
+int cpn_pose_errors(const float* poses, const float* gt, int B, int P, double* out, void* stream);
+int cpn_residual_stats(const float* xy, const int* count, const float* intrinsics, const float* poses, const double* q,
+                       const double* thr, int B, int N, int P, int Q, int T, int* usable, double* quant, int* within, double* sigma,
+                       int* status, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
