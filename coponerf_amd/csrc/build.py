@@ -17,7 +17,9 @@ system, elimination and null vectors from epipolar_system.h); ransac_h.hip for t
 and their decomposition, which tests/homography_ref.py follows bit for bit (it shares ransac_score.h's tiling, jacobi_svd.h's
 sweeps and ransac_common.h's winner with ransac.hip); model_select.hip for that of the homography's Sampson residual (sampson_h.h),
 its Jacobians, sums and GRIC scores, which tests/model_select_ref.py follows (rotation_step.h and cholesky_solve.h are shared with matches.hip);
-pose_eval.hip for that of its pose errors and of sampson.h's residual, whose bits its order statistics return; mesh.hip for that of its signed distances and vertices; raster.hip for that of its projection,
+pose_eval.hip for that of its pose errors and of sampson.h's residual, whose bits its order statistics return (radix_select.h's
+descent, shared with triangulate.hip); triangulate.hip for that of its pixel correction, its points and the depth ratios it ranks,
+which tests/triangulate_ref.py follows bit for bit; mesh.hip for that of its signed distances and vertices; raster.hip for that of its projection,
 depths and colours.  The last five share pinhole.h (the float64 camera; its bodies also switch contraction off by pragma) and
 splat and raster zbuffer.h (the key, its atomic minimum, the resolve stores, the clear and the image checks).
 """
@@ -72,6 +74,7 @@ UNITS = [
     ("ransac_h.hip", ["-ffp-contract=off"]),               # the float64 sequence of the homography model, bit for bit
     ("model_select.hip", ["-ffp-contract=off"]),           # the float64 sequence of the homography's Sampson residual and GRIC
     ("pose_eval.hip", ["-ffp-contract=off"]),              # the float64 sequence of the pose errors and of sampson.h's residual
+    ("triangulate.hip", ["-ffp-contract=off"]),            # the float64 sequence of the correction, the point and the ratios
     ("splat.hip", ["-ffp-contract=off"]),                  # one rounding per float64 operation of the projection
     ("mesh.hip", ["-ffp-contract=off"]),                   # one rounding per float64 operation of the TSDF and the vertices
     ("raster.hip", ["-ffp-contract=off"]),                 # one rounding per float64 operation of the projection and the depth

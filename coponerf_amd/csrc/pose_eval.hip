@@ -16,9 +16,10 @@
 //
 // float64 from the fp32 inputs, one rounding per operation (-ffp-contract=off), sums left to right: tests/pose_eval_ref.py restates
 // both kernels in numpy.  Cam and Pose are pinhole.h's; essential, sampson, residual_ok and finite64 sampson.h's; the count clamp
-// ransac_common.h's.
+// ransac_common.h's; the descent radix_select.h's, which cpn_depth_scale (triangulate.hip) ranks with as well.
 #include "common.h"
 #include "pinhole.h"
+#include "radix_select.h"
 #include "ransac_common.h"
 #include "sampson.h"
 
@@ -28,7 +29,6 @@ namespace {
 
 constexpr int NT = 256;
 constexpr int SLOTS = CPN_POSE_EVAL_MAX + 1;               // the wanted ranks: Q quantiles and the median of the sigmas
-constexpr int DIGITS = 8, BINS = 256;                      // 8 passes of 8 bits
 
 // the quantiles and thresholds travel as kernel arguments: the entry point has checked them on the host
 struct StatArgs {
@@ -72,23 +72,8 @@ __device__ __forceinline__ double abs_residual(const double (&E)[9], const Cam& 
     return fabs(r);                                        // -0 and +0 are one key
 }
 
-// the digit that holds rank k of a histogram - the first whose rows reach beyond k -; k becomes the rank among that digit's rows
-__device__ __forceinline__ int descend(const int* hist, long long& k) {
-    long long below = 0;
-    int d = 0;
-    for (; d < BINS - 1; ++d) {                            // the last digit takes what is left
-        const int c = hist[d];
-        if (k < below + c) break;
-        below += c;
-    }
-    k -= below;
-    return d;
-}
-
 struct StatShared {
-    int hist[SLOTS][BINS];
-    unsigned long long prefix[SLOTS];                      // the digits found so far, in place
-    long long rank[SLOTS];                                 // the wanted rank among the rows that carry the prefix
+    radix::Select<SLOTS> sel;                              // radix_select.h: the histograms, the prefixes and the ranks
     int within[CPN_POSE_EVAL_MAX];
     double red[4];
     int n_in[4];
@@ -110,38 +95,22 @@ __global__ __launch_bounds__(NT) void residual_stats_kernel(const float* __restr
     const Cam k0 = load_cam(intrinsics + ((size_t)b * 2 + 0) * 16), k1 = load_cam(intrinsics + ((size_t)b * 2 + 1) * 16);
     double E[9];
     essential(&pose.R[0][0], pose.t, E);
+    // the value being ranked: |r| of the row, recomputed wherever it is asked for
+    const auto value = [&](int i, double& r) {
+        bool ok;
+        r = abs_residual(E, k0, k1, rows + (size_t)i * 4, ok);
+        return ok;
+    };
 
     // ---- pass 0: the top digit of every usable row (their sum is n_u) and the rows within the thresholds
-    for (int i = tid; i < BINS; i += NT) sh.hist[0][i] = 0;
     if (tid < CPN_POSE_EVAL_MAX) sh.within[tid] = 0;
-    __syncthreads();
-    if (pose_ok) {
-        int in[CPN_POSE_EVAL_MAX];
+    int in[CPN_POSE_EVAL_MAX];
 #pragma unroll
-        for (int t = 0; t < CPN_POSE_EVAL_MAX; ++t) in[t] = 0;
-        int last = -1, run = 0;                            // equal digits in a row - the rule, at the top - make one add
-        for (int i = tid; i < n; i += NT) {
-            bool ok;
-            const double r = abs_residual(E, k0, k1, rows + (size_t)i * 4, ok);
-            if (!ok) continue;
-            const int d = (int)((unsigned long long)__double_as_longlong(r) >> 56);
-            if (d != last) {
-                if (run) atomicAdd(&sh.hist[0][last], run);
-                last = d;
-                run = 0;
-            }
-            ++run;
+    for (int t = 0; t < CPN_POSE_EVAL_MAX; ++t) in[t] = 0;
+    const int n_u = radix::top_digits<NT>(sh.sel, pose_ok ? n : 0, value, [&](double r) {
 #pragma unroll
-            for (int t = 0; t < CPN_POSE_EVAL_MAX; ++t) in[t] += (t < T && r <= args.thr[t]) ? 1 : 0;
-        }
-        if (run) atomicAdd(&sh.hist[0][last], run);
-#pragma unroll
-        for (int t = 0; t < CPN_POSE_EVAL_MAX; ++t)
-            if (t < T && in[t]) atomicAdd(&sh.within[t], in[t]);
-    }
-    __syncthreads();
-    int n_u = 0;
-    for (int d = 0; d < BINS; ++d) n_u += sh.hist[0][d];   // every thread, the same integers
+        for (int t = 0; t < CPN_POSE_EVAL_MAX; ++t) in[t] += (t < T && r <= args.thr[t]) ? 1 : 0;
+    });
     if (n_u == 0) {                                        // nothing to rank: every element of the five outputs all the same
         if (tid == 0) {
             usable[item] = 0;
@@ -152,44 +121,18 @@ __global__ __launch_bounds__(NT) void residual_stats_kernel(const float* __restr
         if (tid < T) within[item * T + tid] = 0;
         return;
     }
+#pragma unroll
+    for (int t = 0; t < CPN_POSE_EVAL_MAX; ++t)
+        if (t < T && in[t]) atomicAdd(&sh.within[t], in[t]);  // read behind the descent's barriers
 
     // ---- the wanted ranks, and the descent: slot j < Q is quantile j, slot Q the median
-    if (tid < slots) {
-        long long k = tid < Q ? (long long)floor(args.q[tid] * (double)(n_u - 1)) : (long long)((n_u - 1) >> 1);
-        k = k < 0 ? 0 : (k > n_u - 1 ? n_u - 1 : k);
-        sh.prefix[tid] = (unsigned long long)descend(sh.hist[0], k) << 56;
-        sh.rank[tid] = k;
-    }
-    __syncthreads();
-    for (int pass = 1; pass < DIGITS; ++pass) {
-        const int shift = 56 - 8 * pass;
-        for (int i = tid; i < slots * BINS; i += NT) (&sh.hist[0][0])[i] = 0;
-        unsigned long long want[SLOTS];
-#pragma unroll
-        for (int j = 0; j < SLOTS; ++j) want[j] = j < slots ? sh.prefix[j] >> (shift + 8) : ~0ull;      // no key has all 56 bits set
-        __syncthreads();
-        for (int i = tid; i < n; i += NT) {
-            bool ok;
-            const double r = abs_residual(E, k0, k1, rows + (size_t)i * 4, ok);
-            if (!ok) continue;
-            const unsigned long long key = (unsigned long long)__double_as_longlong(r);
-            const unsigned long long head = key >> (shift + 8);
-            const int d = (int)(key >> shift) & (BINS - 1);
-#pragma unroll
-            for (int j = 0; j < SLOTS; ++j)
-                if (head == want[j]) atomicAdd(&sh.hist[j][d], 1);
-        }
-        __syncthreads();
-        if (tid < slots) {
-            long long k = sh.rank[tid];
-            sh.prefix[tid] |= (unsigned long long)descend(sh.hist[tid], k) << shift;
-            sh.rank[tid] = k;
-        }
-        __syncthreads();
-    }
+    radix::select<NT>(sh.sel, slots, n, value, [&](int j) {
+        const long long k = j < Q ? (long long)floor(args.q[j] * (double)(n_u - 1)) : (long long)((n_u - 1) >> 1);
+        return k < 0 ? 0 : (k > n_u - 1 ? (long long)(n_u - 1) : k);
+    });
 
     // ---- the sigmas: Rousseeuw's LMedS scale with p = 5 from the median, then the rows within 2.5 of it
-    const double med = __longlong_as_double((long long)sh.prefix[Q]);
+    const double med = __longlong_as_double((long long)sh.sel.prefix[Q]);
     const double s0 = n_u > 5 ? (1.4826 * (1.0 + 5.0 / (double)(n_u - 5))) * med : nan64();
     const double cut = 2.5 * s0;
     double acc = 0.0;
@@ -217,7 +160,7 @@ __global__ __launch_bounds__(NT) void residual_stats_kernel(const float* __restr
         sigma[item * 2 + 0] = s0;
         sigma[item * 2 + 1] = n_in > 5 ? sqrt(sum / (double)(n_in - 5)) : nan64();
     }
-    if (tid < Q) quant[item * Q + tid] = __longlong_as_double((long long)sh.prefix[tid]);
+    if (tid < Q) quant[item * Q + tid] = __longlong_as_double((long long)sh.sel.prefix[tid]);
     if (tid < T) within[item * T + tid] = sh.within[tid];
 }
 

@@ -25,14 +25,14 @@ round.  The reference uses them for the cycle loss and a warped panel only.  Her
   residual_stats  exact quantiles, inlier counts and a robust sigma of the matches' residuals under given poses - under the true
                 pose the evidence the thresholds above should be set by: cpn_residual_stats, one launch
   from_pair     get_z once, then the above (ransac_pose with ransac={...}, homography_pose with homography={...}, select_pose
-                with select={...})
+                with select={...}; triangulate={...} adds the matches' 3-D points, coponerf_amd.triangulate.points)
   photo_coords  host: matches of a prepare_pair dict in the coordinates of the original photos
 
 The conventions and the arithmetic are in include/coponerf_hip.h (round 16).  The selection defaults (cycle error up to 10
 pixels - the reference's own mask -, one match per native flow cell) and scale_px are this package's choices and have not been
 tried on a trained checkpoint, because none is available offline; whether the refined pose is closer to the truth than the
 network's on real data is unknown.  The epipolar residual cannot see the translation's length: the refined pose keeps the
-network's.
+network's (coponerf_amd.triangulate.depth_scale, round 26, measures it against the model's own rendered depth).
 
 refine_pose is a local method: from a rel_pose 30 degrees off it does not move.  ransac_pose (round 20 of the header) does not
 look at rel_pose to find its pose, so the pose head cannot spoil it; `ransac={..., "start": "ransac" | "best"}` lets from_flows
@@ -687,11 +687,26 @@ def _select_keywords(who: str, select_kw: Dict) -> Tuple[Dict, str]:
     return kw, start
 
 
+def _triangulate_keywords(who: str, triangulate: Dict, refine: bool, ransac: Optional[Dict], select_kw: Optional[Dict]):
+    if not isinstance(triangulate, dict):
+        raise ValueError(f"{who}: triangulate must be None or a dict of `pose` and `images`, got {type(triangulate).__name__}")
+    unknown = set(triangulate) - {"pose", "images"}
+    if unknown:
+        raise ValueError(f"{who}: triangulate holds unknown keywords {sorted(unknown)}")
+    pose = triangulate.get("pose", "network")
+    asked = {"network": True, "refined": bool(refine), "ransac": ransac is not None, "selected": select_kw is not None}
+    if pose not in asked:
+        raise ValueError(f"{who}: triangulate['pose'] must be one of {tuple(asked)}, got {pose!r}")
+    if not asked[pose]:
+        raise ValueError(f"{who}: triangulate['pose'] = {pose!r} needs that estimator to run (refine=True, ransac={{..}} or select={{..}})")
+    return pose, triangulate.get("images")
+
+
 @torch.no_grad()
 def from_flows(flow: Sequence[torch.Tensor], intrinsics: torch.Tensor, rel_pose: torch.Tensor, S: int = 256, refine: bool = True,
                max_cycle_px: float = 10.0, max_epi_px: Optional[float] = None, stride: int = 4, iters: int = 10,
                scale_px: float = 2.0, ransac: Optional[Dict] = None, homography: Optional[Dict] = None,
-               select: Optional[Dict] = None) -> Dict:
+               select: Optional[Dict] = None, triangulate: Optional[Dict] = None) -> Dict:
     """from_pair's second half, for flows and a pose that get_z has already returned: four launches and the mask between them,
     no host read.  ransac: None, or a dict of ransac_pose's keywords (hypotheses, inlier_px, seed, solver, and round 24's score, lo,
     lo_iters, lo_scale_px: two more launches with lo > 0) and `start`: three more
@@ -705,7 +720,13 @@ def from_flows(flow: Sequence[torch.Tensor], intrinsics: torch.Tensor, rel_pose:
     select: None, or a dict of select_pose's keywords (hypotheses, inlier_px, seed, solver, sigma_px, iters, scale_px) and `start`:
     select_pose's twelve launches, and the result gains the key `select` (select_pose's dict).  start="selected" refines from the
     selected pose where model_gric's status is 0 and from rel_pose elsewhere; a second start other than "network" among ransac,
-    homography and select is the same ValueError.  Without the keyword nothing changes: no launch, no key."""
+    homography and select is the same ValueError.  Without the keyword nothing changes: no launch, no key.
+    triangulate: None, or a dict of `pose` ("network", the default, "refined", "ransac" or "selected": rel_pose, refine_pose's,
+    ransac_pose's or select_pose's pose, each of which must have been asked for) and `images` (None, or the pair's photos
+    (B, 2, S, S, 3) fp32): one more launch, and the result gains the key `points`, coponerf_amd.triangulate.points' dict of the
+    matches under that pose (round 26 of the header).  Without the keyword nothing changes: no launch, no key."""
+    if triangulate is not None:
+        tri_pose, tri_images = _triangulate_keywords("from_flows", triangulate, refine, ransac, select)
     if ransac is not None:
         ransac_kw, start = _ransac_keywords("from_flows", ransac)
     if homography is not None:
@@ -742,6 +763,11 @@ def from_flows(flow: Sequence[torch.Tensor], intrinsics: torch.Tensor, rel_pose:
             begin = torch.where((chosen["stats"][:, 6] == 0)[:, None, None], chosen["pose"], rel_pose)
     if refine:
         result.update(refine_pose(matches, intrinsics, begin, iters=iters, scale_px=scale_px))
+    if triangulate is not None:
+        from . import triangulate as _triangulate                   # it imports this module
+        under = {"network": rel_pose, "refined": result["pose"], "ransac": result["ransac"]["pose"] if ransac is not None else None,
+                 "selected": result["select"]["pose"] if select is not None else None}[tri_pose]
+        result["points"] = _triangulate.points(matches, intrinsics, under.contiguous(), tri_images)
     return result
 
 
@@ -749,8 +775,8 @@ def from_flows(flow: Sequence[torch.Tensor], intrinsics: torch.Tensor, rel_pose:
 def from_pair(model, model_input: Dict, S: int = 256, refine: bool = True, **select_and_refine_keywords) -> Dict:
     """The matches of the pair(s) in model_input (prepare_pair's dict, or any dict get_z takes).  get_z runs once; its flows
     and its rel_pose - the ones novel_views.render_path hands on - go through match_fields, select and, with refine=True,
-    refine_pose.  Keywords: select's max_cycle_px, max_epi_px, stride, refine_pose's iters, scale_px and from_flows' ransac
-    and homography (with a dict the result gains the key `ransac` or `homography`).  Returns `matches` (a
+    refine_pose.  Keywords: select's max_cycle_px, max_epi_px, stride, refine_pose's iters, scale_px and from_flows' ransac,
+    homography, select and triangulate (with a dict the result gains the key `ransac`, `homography`, `select` or `points`).  Returns `matches` (a
     Matches), `rel_pose` (B, 4, 4) as estimated, `pose` and `stats` as refine_pose returns them (None with refine=False) and
     `fields`, match_fields' dict.  Nothing is read on the host; Matches.numpy is the read."""
     _, rel_pose, flow = model.get_z(model_input)

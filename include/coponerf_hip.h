@@ -1421,6 +1421,64 @@ int cpn_residual_stats(const float* xy, const int* count, const float* intrinsic
                        const double* thr, int B, int N, int P, int Q, int T, int* usable, double* quant, int* within, double* sigma,
                        int* status, void* stream);
 
+/* ==== the matches as geometry: optimal two-view triangulation and the length of the baseline (round 26) ========================
+ * Rounds 16 and 20 - 25 stop at the pose.  This round turns the matches into 3-D points under a pose and, against a depth map of
+ * view 0, into the one number the epipolar residual cannot see: the translation's length.  Two additive symbols: the ABI version
+ * stays.  One launch each, no atomics in global memory, no device value read on the host, bit-reproducible, and a row's (a
+ * pair's) result does not depend on the batch.  Conventions: round 16's (xy (B, N, 4) fp32 = (x0, y0, x1, y1) = (x, x'), count (B)
+ * int32, n = min(max(count, 0), N), intrinsics (B, 2, 4, 4) fp32 with fx, fy, cx, cy at entries 0, 5, 2, 6, a pose row-major
+ * [R | t] with X0 = R X1 + t, a of view 0, b of view 1, a^T E b = 0).  1 <= B <= 32767, 1 <= N <= 2^24 (CPN_E_SHAPE otherwise).
+ * THE PASS COUNT, THE FLAG RULES, THE KEEP RULE AND ITS DEFAULTS, THE NEAREST-PIXEL READ AND THE MEDIAN RULE ARE THIS LIBRARY'S
+ * definitions; none of them has been tried on a trained checkpoint.  All float64 from the fp32 inputs, one rounding per operation,
+ * sums left to right as the parentheses say; |v| of three values is sqrt((v_0 v_0 + v_1 v_1) + v_2 v_2), u x v =
+ * (u_1 v_2 - u_2 v_1, u_2 v_0 - u_0 v_2, u_0 v_1 - u_1 v_0), u . v = (u_0 v_0 + u_1 v_1) + u_2 v_2.
+ * cpn_triangulate_matches: one thread per (pair, row).  pose (B, 4, 4) fp32; images NULL, or (B, 2, S, S, 3) fp32 in [-1, 1] (the
+ *   pair's two photos, `context.rgb`), 1 <= S <= 16384; rgb may be NULL iff images is.  Outputs xyz (B, N, 3) fp32, geom (B, N, 4)
+ *   fp32, flag (B, N) uint8, rgb (B, N, 3) fp32; every element is written.  Rows at and beyond n: NaN and flag 255.  A row with a
+ *   value that is not finite, and every row of a pair whose pose or intrinsics hold a value that is not finite or whose t is
+ *   (0, 0, 0): NaN and flag CPN_TRI_INPUT alone.  Every other row:
+ *   THE CORRECTION (Lindstrom's rule in the iterated form; only + - x / sqrt, CPN_TRIANGULATE_PASSES passes).  th = t / |t|,
+ *   E = [th]x R (round 16's entries), a = ((x0 - cx0) / fx0, (y0 - cy0) / fy0, 1), b likewise from (x1, y1) and camera 1,
+ *   c = a^T E b = round 16's n, n0 = ((E b)_0 / fx0, (E b)_1 / fy0), n0' = ((E^T a)_0 / fx1, (E^T a)_1 / fy1) - round 16's g: with
+ *   F = K0^-T E K1^-1 they are x^T F x', (F x')_12 and (F^T x)_12 -, and Ft_ij = (E_ij / f0_i) / f1_j for i, j < 2 with
+ *   f0 = (fx0, fy0), f1 = (fx1, fy1): the upper-left 2 x 2 of F.  From n = n0, n' = n0', every pass:
+ *     A = n_0 (Ft_00 n'_0 + Ft_01 n'_1) + n_1 (Ft_10 n'_0 + Ft_11 n'_1);   Bq = 0.5 ((n_0 n0_0 + n_1 n0_1) + (n'_0 n0'_0 + n'_1 n0'_1));
+ *     disc = Bq Bq - A c;   d = sqrt(disc);   den = Bq + d;   lambda = c / den;   D = lambda n;   D' = lambda n';
+ *     n_i = n0_i - (Ft_i0 D'_0 + Ft_i1 D'_1);   n'_j = n0'_j - (Ft_0j D_0 + Ft_1j D_1).
+ *   A pass in which disc >= 0 or den != 0 does not hold sets CPN_TRI_CORRECTION (a match on both epipoles does: everything is 0).
+ *   The corrected match is xh = x - D, xh' = x' - D' with the last pass's D, D'.  c - 2 Bq lambda + A lambda^2 = 0 in every pass,
+ *   so (xh, xh') lies on the constraint after any number of passes; further passes slide it towards the closest such pair.
+ *   THE POINT.  ah, bh the normalised xh, xh' (as a, b above); cr_j = (R_j0 bh_0 + R_j1 bh_1) + R_j2;  w = ah x cr;  ww = w . w;
+ *   z0 = ((t x cr) . w) / ww;  z1 = ((t x ah) . w) / ww - round 20's two cheirality numerators over ww, with t AS GIVEN: the caller
+ *   decides the length -;  X = (z0 ah_0, z0 ah_1, z0), in view 0's frame.  CPN_TRI_PARALLAX unless ww > 0, CPN_TRI_BEHIND0 unless
+ *   z0 > 0, CPN_TRI_BEHIND1 unless z1 > 0 (a NaN sets them).
+ *   xyz = X; geom = (z0, z1, sqrt(((D_0 D_0 + D_1 D_1) + D'_0 D'_0) + D'_1 D'_1) - the reprojection error in pixels -,
+ *   atan2(sqrt(ww), ah . cr) 57.29577951308232 - the parallax in degrees; atan2 is the device library's, every other operation is
+ *   exact to the last bit), each rounded to fp32 once.
+ *   rgb, per channel: 0.5 (s0 + s1) with s_v the bilinear sample of image v at the match AS GIVEN: u = min(max(x, 0), S - 1),
+ *   i = min(floor(u), S - 2) (0 for S = 1), l = u - i, likewise along y, s = (1 - ly) ((1 - lx) p00 + lx p01) + ly ((1 - lx) p10 +
+ *   lx p11) with the taps clamped to the image.
+ * cpn_depth_scale: grid B, one workgroup of 256 threads per pair.  geom and flag as cpn_triangulate_matches wrote them for a pose
+ *   with |t| = 1; depth (B, S S) fp32, a z-depth map of view 0 on the S x S grid; rel_pose NULL or (B, 4, 4) fp32; max_reproj_px
+ *   and min_parallax_deg finite and >= 0, min_rows >= 1 (CPN_E_ARG otherwise).  Row i < n is USED iff flag = 0, geom_2 <=
+ *   max_reproj_px, geom_3 >= min_parallax_deg, the NEAREST pixel (floor(x0 + 0.5), floor(y0 + 0.5)) lies in the grid, the depth d
+ *   read there counts by round 14's rule (finite, 0 < d < 10), and q = d / geom_0 (both converted to float64) is finite and > 0.
+ *   scale (B) float64 = the element of rank (n_u - 1) / 2 rounded down of the used q in ascending order - round 25's rank rule:
+ *   the LOWER median, one of the q in its bits.  stats (B, 4) float64: [0] n_u; [1] the element of the same rank of
+ *   |q / scale - 1|; [2] |t| of rel_pose / scale, NaN without one; [3] 0 ok, 1 n_u < min_rows: scale, [1] and [2] are NaN.
+ *   The selection is round 25's radix descent (radix_select.h), twice: sixteen passes over the rows below n.                       */
+#define CPN_TRIANGULATE_PASSES 3
+#define CPN_TRI_INPUT 1
+#define CPN_TRI_CORRECTION 2
+#define CPN_TRI_PARALLAX 4
+#define CPN_TRI_BEHIND0 8
+#define CPN_TRI_BEHIND1 16
+int cpn_triangulate_matches(const float* xy, const int* count, const float* intrinsics, const float* pose, const float* images,
+                            int B, int N, int S, float* xyz, float* geom, uint8_t* flag, float* rgb, void* stream);
+int cpn_depth_scale(const float* geom, const uint8_t* flag, const float* xy, const int* count, const float* depth,
+                    const float* rel_pose, int B, int N, int S, double max_reproj_px, double min_parallax_deg, int min_rows,
+                    double* scale, double* stats, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
