@@ -19,8 +19,9 @@ sweeps and ransac_common.h's winner with ransac.hip); model_select.hip for that 
 its Jacobians, sums and GRIC scores, which tests/model_select_ref.py follows (rotation_step.h and cholesky_solve.h are shared with matches.hip);
 pose_eval.hip for that of its pose errors and of sampson.h's residual, whose bits its order statistics return (radix_select.h's
 descent, shared with triangulate.hip); triangulate.hip for that of its pixel correction, its points and the depth ratios it ranks,
-which tests/triangulate_ref.py follows bit for bit; mesh.hip for that of its signed distances and vertices; raster.hip for that of its projection,
-depths and colours.  The last five share pinhole.h (the float64 camera; its bodies also switch contraction off by pragma) and
+which tests/triangulate_ref.py follows bit for bit; bundle.hip for that of its residuals, Jacobians, Schur sums and covariances,
+which tests/bundle_ref.py follows (it shares pose_gauss_newton.h's reduction and step with matches.hip and ransac.hip); mesh.hip
+for that of its signed distances and vertices; raster.hip for that of its projection, depths and colours.  The last six share pinhole.h (the float64 camera; its bodies also switch contraction off by pragma) and
 splat and raster zbuffer.h (the key, its atomic minimum, the resolve stores, the clear and the image checks).
 """
 import os
@@ -75,6 +76,7 @@ UNITS = [
     ("model_select.hip", ["-ffp-contract=off"]),           # the float64 sequence of the homography's Sampson residual and GRIC
     ("pose_eval.hip", ["-ffp-contract=off"]),              # the float64 sequence of the pose errors and of sampson.h's residual
     ("triangulate.hip", ["-ffp-contract=off"]),            # the float64 sequence of the correction, the point and the ratios
+    ("bundle.hip", ["-ffp-contract=off"]),                 # the float64 sequence of the residuals, the Schur sums and the covariances
     ("splat.hip", ["-ffp-contract=off"]),                  # one rounding per float64 operation of the projection
     ("mesh.hip", ["-ffp-contract=off"]),                   # one rounding per float64 operation of the TSDF and the vertices
     ("raster.hip", ["-ffp-contract=off"]),                 # one rounding per float64 operation of the projection and the depth

@@ -35,6 +35,22 @@ __device__ void set_matrices(RefineState& st) {
     }
 }
 
+// The sums of a pass, 256 threads: the butterfly of wave_sum on each of the first V values of acc, lane 0 of wave w parks them in
+// red[.][w]; behind the caller's barrier four_waves(red[k]) is sum k.  bundle.hip (round 27) reduces its sweeps with the same two.
+template <int V, int NV>
+__device__ __forceinline__ void park_wave_sums(double (&acc)[NV], double (*red)[4]) {
+    static_assert(V <= NV, "more sums than values");
+#pragma unroll
+    for (int k = 0; k < V; ++k) acc[k] = wave_sum(acc[k]);
+    if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+        for (int k = 0; k < V; ++k) red[k][threadIdx.x >> 6] = acc[k];
+    }
+}
+template <int NV>
+__device__ __forceinline__ void park_wave_sums(double (&acc)[NV], double (*red)[4]) { park_wave_sums<NV, NV>(acc, red); }
+__device__ __forceinline__ double four_waves(const double (&r)[4]) { return (r[0] + r[1]) + (r[2] + r[3]); }
+
 // R <- exp([w]x) R (Rodrigues; the identity below 1e-12), t <- (t + dt) / |t + dt|; false (state untouched) where not finite
 __device__ bool apply_step(RefineState& st, const double (&x)[6]) {
     double Rn[9], tn[3];
@@ -56,7 +72,7 @@ template <class Done>
 __device__ __forceinline__ void pose_passes(RefineState& st, const float* __restrict__ rows, int n, const Cam& k0, const Cam& k1,
                                             int iters, double scale_px, Done done_fn) {
     constexpr int NT = 256, NSUM = POSE_NSUM;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x;
     double cost0 = 0.0;
     int done = 0, status = 0;
 
@@ -96,16 +112,11 @@ __device__ __forceinline__ void pose_passes(RefineState& st, const float* __rest
             acc[28] += w;
             acc[29] += 1.0;
         }
-#pragma unroll
-        for (int k = 0; k < NSUM; ++k) acc[k] = wave_sum(acc[k]);
-        if (lane == 0) {
-#pragma unroll
-            for (int k = 0; k < NSUM; ++k) st.red[k][wave] = acc[k];
-        }
+        park_wave_sums(acc, st.red);
         __syncthreads();
         if (tid == 0) {
             double sum[NSUM];
-            for (int k = 0; k < NSUM; ++k) sum[k] = (st.red[k][0] + st.red[k][1]) + (st.red[k][2] + st.red[k][3]);
+            for (int k = 0; k < NSUM; ++k) sum[k] = four_waves(st.red[k]);
             if (pass == 0) cost0 = sum[27];
             bool more = pass < iters;
             if (more) {

@@ -32,12 +32,12 @@ COLUMNS = ("mse", "psnr", "ssim", "rot", "trans", "angle_trans", "overlap", "cal
 BUCKETS = ("small", "medium", "large")
 # Evaluator(geometry=...): the poses from_flows can return, in the order of their columns; what is measured of the matches; the
 # labels of select_pose's `model` (0, 1, 2; -1 is "none"); the thresholds of the AUC in degrees
-SOURCES = ("network", "refined", "ransac", "homography", "select")
+SOURCES = ("network", "refined", "ransac", "homography", "select", "adjusted")
 QUALITY = ("matches", "usable_gt", "med_gt", "in_gt", "sigma_gt", "med_network", "in_network")
 MODELS = ("E", "plane", "rotation")
 AUC_AT = (5, 10, 20)
 _GEOMETRY_KEYS = ("S", "refine", "max_cycle_px", "max_epi_px", "stride", "iters", "scale_px", "ransac", "homography", "select",
-                  "inlier_px")
+                  "triangulate", "inlier_px")
 WIN = 11                                                  # structural_similarity(win_size=11): the smallest image side
 
 
@@ -179,9 +179,10 @@ class Evaluator:
     -> host reads made here: `add` and `run` make none, `summary`, `format_summary` and `rows(host=True)` one each.
 
     geometry: None, or a dict of matches.from_flows' own keywords (S, refine, max_cycle_px, max_epi_px, stride, iters, scale_px,
-    ransac, homography, select) and `inlier_px` (1.0).  `add` then needs `intrinsics`, runs from_flows on the batch's flows and
+    ransac, homography, select, triangulate) and `inlier_px` (1.0).  `add` then needs `intrinsics`, runs from_flows on the batch's flows and
     pose and scores EVERY pose it returns against the ground truth - `self.sources`, of SOURCES: network, refined (unless
-    refine=False), ransac, homography, select - in float64: per source s the columns `rot64_s`, `trans64_s`, `angle64_s`
+    refine=False), ransac, homography, select, and adjusted: with `triangulate` = a dict of `pose` and `adjust` (from_flows' own),
+    bundle adjustment's pose from that pose (round 27) - in float64: per source s the columns `rot64_s`, `trans64_s`, `angle64_s`
     (matches.pose_errors: radians and scene units, as the built-in ones), then QUALITY: `matches` (the pair's count), and of the
     matches' Sampson residuals under the GROUND-TRUTH pose `usable_gt`, `med_gt` (the median |r| in pixels), `in_gt` (the share
     within inlier_px), `sigma_gt` (matches.residual_stats' sigma[1]), under the network's pose `med_network`, `in_network`; with
@@ -210,6 +211,10 @@ class Evaluator:
                 raise ValueError(f"Evaluator: geometry['inlier_px'] must be finite and >= 0, got {geometry['inlier_px']}")
             on = {"network": True, "refined": bool(self.geometry.get("refine", True))}
             on.update({k: self.geometry.get(k) is not None for k in ("ransac", "homography", "select")})
+            tri = self.geometry.get("triangulate")
+            if tri is not None and not (isinstance(tri, dict) and tri.get("adjust") is not None):
+                raise ValueError("Evaluator: geometry['triangulate'] is taken for its `adjust` alone: a dict of `pose` and `adjust`")
+            on["adjusted"] = tri is not None
             self.sources = tuple(s for s in SOURCES if on[s])
             names = tuple(f"{c}_{s}" for s in self.sources for c in ("rot64", "trans64", "angle64")) + QUALITY
             names += ("model",) if on["select"] else ()
@@ -311,6 +316,8 @@ class Evaluator:
         found = mt.from_flows(flows, K, rel, **self.geometry)
         pose = {"network": rel, "refined": found["pose"]}
         pose.update({k: found[k]["pose"] for k in ("ransac", "homography", "select") if k in found})
+        if "adjust" in found:
+            pose["adjusted"] = found["adjust"]["pose"]
         errs = mt.pose_errors(torch.stack([pose[s] for s in self.sources], dim=1).contiguous(), gt_rel)
         at = len(COLUMNS) + len(self.extra)
         rows[:, at:at + 3 * len(self.sources)] = errs.reshape(errs.shape[0], -1)

@@ -689,8 +689,8 @@ def _select_keywords(who: str, select_kw: Dict) -> Tuple[Dict, str]:
 
 def _triangulate_keywords(who: str, triangulate: Dict, refine: bool, ransac: Optional[Dict], select_kw: Optional[Dict]):
     if not isinstance(triangulate, dict):
-        raise ValueError(f"{who}: triangulate must be None or a dict of `pose` and `images`, got {type(triangulate).__name__}")
-    unknown = set(triangulate) - {"pose", "images"}
+        raise ValueError(f"{who}: triangulate must be None or a dict of `pose`, `images` and `adjust`, got {type(triangulate).__name__}")
+    unknown = set(triangulate) - {"pose", "images", "adjust"}
     if unknown:
         raise ValueError(f"{who}: triangulate holds unknown keywords {sorted(unknown)}")
     pose = triangulate.get("pose", "network")
@@ -699,7 +699,16 @@ def _triangulate_keywords(who: str, triangulate: Dict, refine: bool, ransac: Opt
         raise ValueError(f"{who}: triangulate['pose'] must be one of {tuple(asked)}, got {pose!r}")
     if not asked[pose]:
         raise ValueError(f"{who}: triangulate['pose'] = {pose!r} needs that estimator to run (refine=True, ransac={{..}} or select={{..}})")
-    return pose, triangulate.get("images")
+    adjust = triangulate.get("adjust")
+    if adjust is not None:
+        if not isinstance(adjust, dict):
+            raise ValueError(f"{who}: triangulate['adjust'] must be None or a dict of bundle_adjust's keywords, got {type(adjust).__name__}")
+        unknown = set(adjust) - {"iters", "scale_px", "ftol", "min_rows", "inliers_only"}
+        if unknown:
+            raise ValueError(f"{who}: triangulate['adjust'] holds unknown keywords {sorted(unknown)}")
+        if adjust.get("inliers_only") and pose not in ("ransac", "selected"):
+            raise ValueError(f"{who}: triangulate['adjust']['inliers_only'] needs triangulate['pose'] \"ransac\" or \"selected\", got {pose!r}")
+    return pose, triangulate.get("images"), adjust
 
 
 @torch.no_grad()
@@ -724,9 +733,12 @@ def from_flows(flow: Sequence[torch.Tensor], intrinsics: torch.Tensor, rel_pose:
     triangulate: None, or a dict of `pose` ("network", the default, "refined", "ransac" or "selected": rel_pose, refine_pose's,
     ransac_pose's or select_pose's pose, each of which must have been asked for) and `images` (None, or the pair's photos
     (B, 2, S, S, 3) fp32): one more launch, and the result gains the key `points`, coponerf_amd.triangulate.points' dict of the
-    matches under that pose (round 26 of the header).  Without the keyword nothing changes: no launch, no key."""
+    matches under that pose (round 26 of the header), and `adjust` (None, or a dict of coponerf_amd.triangulate.bundle_adjust's
+    keywords iters, scale_px, ftol, min_rows and `inliers_only`, which hands it ransac_pose's mask): one launch more, and the
+    result gains the key `adjust`, bundle_adjust's dict from those points and that pose (round 27).  Without the keyword nothing
+    changes: no launch, no key."""
     if triangulate is not None:
-        tri_pose, tri_images = _triangulate_keywords("from_flows", triangulate, refine, ransac, select)
+        tri_pose, tri_images, tri_adjust = _triangulate_keywords("from_flows", triangulate, refine, ransac, select)
     if ransac is not None:
         ransac_kw, start = _ransac_keywords("from_flows", ransac)
     if homography is not None:
@@ -767,7 +779,14 @@ def from_flows(flow: Sequence[torch.Tensor], intrinsics: torch.Tensor, rel_pose:
         from . import triangulate as _triangulate                   # it imports this module
         under = {"network": rel_pose, "refined": result["pose"], "ransac": result["ransac"]["pose"] if ransac is not None else None,
                  "selected": result["select"]["pose"] if select is not None else None}[tri_pose]
-        result["points"] = _triangulate.points(matches, intrinsics, under.contiguous(), tri_images)
+        under = under.contiguous()
+        result["points"] = _triangulate.points(matches, intrinsics, under, tri_images)
+        if tri_adjust is not None:
+            kw = dict(tri_adjust)
+            mask = None
+            if kw.pop("inliers_only", False):
+                mask = (result["ransac"] if tri_pose == "ransac" else result["select"]["ransac"])["inlier"]
+            result["adjust"] = _triangulate.bundle_adjust(result["points"], matches, intrinsics, under, inlier=mask, **kw)
     return result
 
 

@@ -9,6 +9,9 @@
   depth_scale   the translation's length, which the epipolar residual cannot see: the exact median of (the model's own rendered
                 depth of view 0) / (the triangulated depth under |t| = 1), its spread, and the pose head's |t| over it - a verdict
                 on the network's translation norm that needs no ground truth: cpn_depth_scale, one launch
+  bundle_adjust the pose and one point per match that minimise the reprojection error of both views together, Levenberg-Marquardt
+                on the Schur complement of the points, with the Gauss-Newton covariance of the pose and of every point and a
+                noise estimate sigma: cpn_bundle_adjust, one launch (round 27)
   rescale       [R | scale t / |t|] by torch.where
   cloud         the kept points as a point_cloud.PointCloud (save, points(b), frames and splat.draw work on it unchanged)
   from_pair     matches.from_pair, points under the chosen pose and, with scale="depth", one render of view 0's depth, depth_scale,
@@ -21,8 +24,14 @@ parallax >= min_parallax_deg = 1 degree) and its defaults, the nearest-pixel rea
 middle, round 25's rank rule) are this package's definitions.  None of it has been tried on a trained checkpoint, because none is
 available offline; on the synthetic weights the flows carry no geometry, and the cloud is empty or tiny.
 
-Left out: two-view bundle adjustment over points and pose, per-point covariances, feeding the cloud to mesh.integrate, feeding the
-scale back into Evaluator's columns, and tracks over more than two views.
+bundle_adjust (round 27): the gauge (|t| = 1, pinned by (tr S / 6) t t^T), sigma = sqrt(2 cost / (rows - 5)), the LM constants (lambda
+from 1e-3, / 3 on an accepted step, x 4 on a rejected one, within [1e-12, 1e8]), the stop rule (iters solves, a gain of at most ftol x
+cost, lambda > 1e8, a failed solve) and the used-row rule are this package's definitions.  The covariance is the Gauss-Newton one: it
+ignores the weights' derivative and the outliers.  On the synthetic scenes its pose is NOT nearer the truth than refine_pose's (the
+two costs agree to first order); none of it has been tried on a trained checkpoint.
+
+Left out: feeding the cloud to mesh.integrate, feeding the scale back into Evaluator's columns, a robust (sandwich) covariance, more
+workgroups per pair for stride-1 pairs, and tracks over more than two views.
 """
 from __future__ import annotations
 
@@ -117,6 +126,54 @@ def depth_scale(tri: Dict[str, torch.Tensor], matches: "_matches.Matches", depth
 
 
 @torch.no_grad()
+def bundle_adjust(tri: Dict[str, torch.Tensor], matches: "_matches.Matches", intrinsics: torch.Tensor, pose: torch.Tensor,
+                  inlier: Optional[torch.Tensor] = None, iters: int = 10, scale_px: float = 1.0, ftol: float = 1e-12,
+                  min_rows: int = 8) -> Dict[str, torch.Tensor]:
+    """cpn_bundle_adjust: tri = points(matches, intrinsics, pose), the same pose (B, 4, 4) fp32, inlier None or (B, N) uint8 ->
+    the pose and one point per used row that minimise the robust reprojection error of both views together (refine_pose's cost and
+    weight with scale_px, on the 4 pixel residuals of a row), by Levenberg-Marquardt on the Schur complement of the points, at most
+    `iters` solves, and their Gauss-Newton covariances.  A row is used iff it is below the count, finite, has flag 0, a non-zero
+    inlier byte where given, and starts in front of both cameras.  A dict of `pose` (B, 4, 4) fp32 = [R | |t| of the input times the
+    new direction], `xyz` (B, N, 3) fp32, `geom` (B, N, 4) fp32 = (z0, z1, the row's error in pixels, its weight), `cov_x`
+    (B, N, 6) fp32, the upper triangle of the point's covariance for unit pixel variance (times sigma^2 for the estimated one),
+    `cov` (B, 6, 6) float64, the pose's covariance in (rotation vector, dt) order in the gauge |t| = 1, px^-2 units, and `stats`
+    (B, 12) float64: the cost at the start and at the end, the sum of weights, the rows used, steps accepted, rejected, the last
+    lambda, sigma = sqrt(2 cost / (rows - 5)), sigma sqrt(tr C_rot) and sigma sqrt(tr C_t) in degrees, the rotation moved in
+    degrees, the status (0 ok, 1 a solve failed, 2 not usable: the pose is the input's, everything else NaN).  Rows that are not
+    used are NaN.  One launch, one workgroup per pair, float64 inside, nothing read on the host; the workspace (B, 2, N, 3) float64
+    is allocated here.  The covariance ignores the weights' derivative and the outliers."""
+    named = [("tri['xyz']", tri["xyz"], torch.float32, None), ("tri['flag']", tri["flag"], torch.uint8, None),
+             ("matches.xy", matches.xy, torch.float32, None), ("intrinsics", intrinsics, torch.float32, None), ("pose", pose, torch.float32, None)]
+    if inlier is not None:
+        named.append(("inlier", inlier, torch.uint8, None))
+    device_tensors("bundle_adjust", tuple(named))
+    B, N = _matches._matches_args("bundle_adjust", matches)
+    _matches._cameras("bundle_adjust", intrinsics, pose, B)
+    if tuple(tri["xyz"].shape) != (B, N, 3) or tuple(tri["flag"].shape) != (B, N):
+        raise ValueError(f"bundle_adjust: tri must be points() of these matches: xyz {(B, N, 3)} and flag {(B, N)}, got "
+                         f"{tuple(tri['xyz'].shape)} and {tuple(tri['flag'].shape)}")
+    if inlier is not None and tuple(inlier.shape) != (B, N):
+        raise ValueError(f"bundle_adjust: inlier must be (B, N) = {(B, N)}, got {tuple(inlier.shape)}")
+    if int(iters) < 0 or not 0.0 < float(scale_px) < float("inf") or not 0.0 <= float(ftol) < float("inf") or int(min_rows) < 1:
+        raise ValueError(f"bundle_adjust: need iters >= 0, a finite scale_px > 0, a finite ftol >= 0 and min_rows >= 1, got {iters}, "
+                         f"{scale_px}, {ftol}, {min_rows}")
+    if not 1 <= B <= 32767 or N > 2 ** 24:
+        raise ValueError(f"bundle_adjust: need 1 <= B <= 32767 and N <= 2^24, got B = {B}, N = {N}")
+    dev = matches.xy.device
+    work = torch.empty(B, 2, N, 3, dtype=torch.float64, device=dev)
+    out = {"pose": torch.empty(B, 4, 4, dtype=torch.float32, device=dev), "xyz": torch.empty(B, N, 3, dtype=torch.float32, device=dev),
+           "geom": torch.empty(B, N, 4, dtype=torch.float32, device=dev), "cov_x": torch.empty(B, N, 6, dtype=torch.float32, device=dev),
+           "cov": torch.empty(B, 6, 6, dtype=torch.float64, device=dev),
+           "stats": torch.empty(B, _hip.CONSTANTS["BUNDLE_STATS"], dtype=torch.float64, device=dev)}
+    with torch.cuda.device(dev):
+        _hip.call("cpn_bundle_adjust", matches.xy.data_ptr(), matches.count.data_ptr(), intrinsics.data_ptr(), pose.data_ptr(),
+                  tri["xyz"].data_ptr(), tri["flag"].data_ptr(), inlier.data_ptr() if inlier is not None else None, B, N, int(iters),
+                  float(scale_px), float(ftol), int(min_rows), work.data_ptr(), out["pose"].data_ptr(), out["xyz"].data_ptr(),
+                  out["geom"].data_ptr(), out["cov_x"].data_ptr(), out["cov"].data_ptr(), out["stats"].data_ptr(), _hip.stream_handle())
+    return out
+
+
+@torch.no_grad()
 def rescale(pose: torch.Tensor, scale: torch.Tensor) -> torch.Tensor:
     """[R | scale t / |t|] of pose (B, 4, 4) fp32 and scale (B) - the direction and the product in float64, rounded to fp32 once -
     by torch.where: a pair whose scale or whose new translation is not finite (depth_scale's status 1, t = 0) keeps its pose."""
@@ -130,11 +187,14 @@ def rescale(pose: torch.Tensor, scale: torch.Tensor) -> torch.Tensor:
 
 @torch.no_grad()
 def cloud(tri: Dict[str, torch.Tensor], max_reproj_px: float = 1.0, min_parallax_deg: float = 1.0,
-          inlier: Optional[torch.Tensor] = None) -> "point_cloud.PointCloud":
+          inlier: Optional[torch.Tensor] = None, max_rel_sigma_z: Optional[float] = None, cov_x: Optional[torch.Tensor] = None,
+          sigma: Optional[torch.Tensor] = None) -> "point_cloud.PointCloud":
     """The PointCloud of points()' dict: a row is kept iff its flag is 0, its reprojection error is at most max_reproj_px, its
     parallax at least min_parallax_deg and, with inlier (B, N) (ransac_pose's mask), inlier is not zero.  Stock ops form the mask,
     point_cloud.compact (K = 1, h = 1, w = N) compacts it: the kept rows in the matches' order, no new kernel, nothing read on
-    the host.  Without colours in tri the points are grey."""
+    the host.  Without colours in tri the points are grey.  max_rel_sigma_z: with bundle_adjust's `cov_x` (B, N, 6) and a `sigma`
+    (B) - its stats[:, 7] - a row is also dropped unless sigma sqrt(cov_zz) / z0 <= max_rel_sigma_z (a NaN drops it); without the
+    keyword the mask and the bytes are as before."""
     xyz, geom, flag = tri["xyz"], tri["geom"], tri["flag"]
     B, N = int(flag.shape[0]), int(flag.shape[1])
     keep = (flag == 0) & (geom[..., 2] <= float(max_reproj_px)) & (geom[..., 3] >= float(min_parallax_deg))
@@ -142,20 +202,29 @@ def cloud(tri: Dict[str, torch.Tensor], max_reproj_px: float = 1.0, min_parallax
         if tuple(inlier.shape) != (B, N) or inlier.device != flag.device:
             raise ValueError(f"cloud: inlier must be (B, N) = {(B, N)} on tri's device, got {tuple(inlier.shape)}")
         keep &= inlier != 0
+    if max_rel_sigma_z is not None:
+        if cov_x is None or sigma is None or tuple(cov_x.shape) != (B, N, 6) or tuple(sigma.shape) != (B,):
+            raise ValueError(f"cloud: max_rel_sigma_z needs cov_x (B, N, 6) and sigma (B) with (B, N) = {(B, N)}")
+        keep &= sigma.double()[:, None] * cov_x[..., 5].double().sqrt() / geom[..., 0].double() <= float(max_rel_sigma_z)
     rgb = tri["rgb"] if "rgb" in tri else torch.zeros_like(xyz)
     return point_cloud.compact(keep.to(torch.uint8)[None].contiguous(), xyz[None], rgb[None], 1, N)
 
 
 @torch.no_grad()
 def from_pair(model, model_input: Dict, pose: str = "selected", scale: str = "given", max_reproj_px: float = 1.0,
-              min_parallax_deg: float = 1.0, min_rows: int = 8, inliers_only: bool = False, **matches_keywords) -> Dict:
+              min_parallax_deg: float = 1.0, min_rows: int = 8, inliers_only: bool = False, adjust: Optional[Dict] = None,
+              **matches_keywords) -> Dict:
     """The triangulated cloud of the pair(s) in model_input (prepare_pair's dict).  matches.from_pair runs (get_z once; its
     keywords - S, stride, max_cycle_px, ransac, select, .. - are handed on); the matches are triangulated under `pose`: "network"
     (get_z's rel_pose), "refined" (refine_pose's), "ransac" (ransac_pose's; ransac={} is added where the keyword is missing) or
     "selected" (select_pose's, likewise).  scale="given" takes the pose's translation as it is - the network's length, whatever the
     estimator -; scale="depth" triangulates under |t| = 1, renders view 0's depth ONCE (render_path at t = 0, which runs get_z
     again), takes depth_scale against it, rescales the pose and triangulates again: two more launches and the render.
-    inliers_only=True keeps ransac_pose's inliers alone (pose "ransac" or "selected").
+    inliers_only=True keeps ransac_pose's inliers alone (pose "ransac" or "selected").  adjust: None, or a dict of bundle_adjust's
+    keywords (iters, scale_px, ftol, min_rows) and cloud's max_rel_sigma_z: bundle_adjust runs after the last points call (on the
+    inliers alone with inliers_only), the cloud is formed from the adjusted points - with the error and the flags of the adjusted
+    rows: a row that bundle_adjust did not use is dropped - and the result gains the key `adjust`, its dict; `pose` stays the pose
+    the triangulation used.  Without the keyword nothing is launched.
     -> `cloud` (a PointCloud, coloured from the two photos), `pose` (B, 4, 4) the pose the points were formed under, `scale` (B)
     float64 and `stats` (B, 4) float64 (depth_scale's; None with scale="given"), `points` (points()' dict) and `matches`
     (matches.from_pair's dict).  Nothing is read on the host; PointCloud.points is the read.  On the synthetic weights the flows
@@ -166,6 +235,11 @@ def from_pair(model, model_input: Dict, pose: str = "selected", scale: str = "gi
         raise ValueError(f"from_pair: scale must be one of {_SCALES}, got {scale!r}")
     if inliers_only and pose not in ("ransac", "selected"):
         raise ValueError(f"from_pair: inliers_only needs pose \"ransac\" or \"selected\", got {pose!r}")
+    if adjust is not None:
+        if not isinstance(adjust, dict) or set(adjust) - {"iters", "scale_px", "ftol", "min_rows", "max_rel_sigma_z"}:
+            raise ValueError(f"from_pair: adjust must be None or a dict of iters, scale_px, ftol, min_rows and max_rel_sigma_z, got {adjust!r}")
+        adjust_kw = dict(adjust)
+        max_rel_sigma_z = adjust_kw.pop("max_rel_sigma_z", None)
     kw = dict(matches_keywords)
     if pose == "ransac":
         kw.setdefault("ransac", {})
@@ -197,5 +271,16 @@ def from_pair(model, model_input: Dict, pose: str = "selected", scale: str = "gi
                          min_parallax_deg=min_parallax_deg, min_rows=min_rows)
         chosen = rescale(chosen, ds["scale"])
     tri = points(m, intrinsics, chosen, images)
-    return {"cloud": cloud(tri, max_reproj_px=max_reproj_px, min_parallax_deg=min_parallax_deg, inlier=inlier), "pose": chosen,
-            "scale": None if ds is None else ds["scale"], "stats": None if ds is None else ds["stats"], "points": tri, "matches": found}
+    result = {"pose": chosen, "scale": None if ds is None else ds["scale"], "stats": None if ds is None else ds["stats"], "points": tri,
+              "matches": found}
+    if adjust is None:
+        result["cloud"] = cloud(tri, max_reproj_px=max_reproj_px, min_parallax_deg=min_parallax_deg, inlier=inlier)
+        return result
+    ba = result["adjust"] = bundle_adjust(tri, m, intrinsics, chosen, inlier=inlier, **adjust_kw)
+    moved = dict(tri)                                                   # the adjusted points; the parallax stays round 26's
+    moved["xyz"] = ba["xyz"]
+    moved["geom"] = torch.cat((ba["geom"][..., :3], tri["geom"][..., 3:]), dim=-1)
+    moved["flag"] = torch.where(torch.isnan(ba["xyz"][..., 2]), torch.full_like(tri["flag"], 255), tri["flag"])
+    result["cloud"] = cloud(moved, max_reproj_px=max_reproj_px, min_parallax_deg=min_parallax_deg, inlier=inlier,
+                            max_rel_sigma_z=max_rel_sigma_z, cov_x=ba["cov_x"], sigma=ba["stats"][:, 7])
+    return result

@@ -1479,6 +1479,72 @@ int cpn_depth_scale(const float* geom, const uint8_t* flag, const float* xy, con
                     const float* rel_pose, int B, int N, int S, double max_reproj_px, double min_parallax_deg, int min_rows,
                     double* scale, double* stats, void* stream);
 
+/* ==== two-view bundle adjustment over the pose and the points, with covariances (round 27) =====================================
+ * Round 16's refinement minimises the Sampson residual and round 26 places the points under a pose that something else found.
+ * This round minimises the reprojection error itself over the pose and one point per match, by Levenberg-Marquardt on the Schur
+ * complement of the points, and states the Gauss-Newton covariance of the pose and of every point.  One additive symbol: the ABI
+ * version stays.  One launch, grid B, ONE workgroup of 256 threads per pair, every sweep inside it; no atomics, no device value
+ * read on the host, bit-reproducible, and a pair's result does not depend on the batch.  Conventions: round 26's.  THE GAUGE, THE
+ * FORMULA OF sigma, THE LM CONSTANTS, THE STOP RULE AND THE USED-ROW RULE ARE THIS LIBRARY'S definitions; the covariance is the
+ * Gauss-Newton one (it ignores the weights' derivative and the outliers); none of it has been tried on a trained checkpoint.
+ * All float64 from the fp32 inputs, one rounding per operation, sums left to right as the parentheses say; |v|, u x v and u . v as
+ * in round 26; "d += l d" stands for d = d + l d.
+ * cpn_bundle_adjust: xy, count, intrinsics, pose (B, 4, 4) fp32 as in round 26; xyz_in (B, N, 3) fp32 and flag (B, N) uint8 as
+ *   cpn_triangulate_matches wrote them under that pose; inlier NULL or (B, N) uint8; iters >= 0, scale_px and ftol finite, scale_px
+ *   > 0, ftol >= 0, min_rows >= 1 (CPN_E_ARG otherwise); 1 <= B <= 32767, 1 <= N <= 2^24 (CPN_E_SHAPE).  work (B, 2, N, 3)
+ *   float64 holds the kept and the tentative points: in HBM (L2 for a pair of 6 000 rows: 288 KB), NOT in LDS, so that a pair of
+ *   131 072 rows works.  Outputs: pose_out (B, 4, 4) fp32, xyz (B, N, 3) fp32, geom (B, N, 4) fp32, cov_x (B, N, 6) fp32, cov
+ *   (B, 6, 6) float64, stats (B, CPN_BUNDLE_STATS) float64; every element is written.
+ *   THE STATE.  len0 = |t| of pose, R, th = t / len0, and per row the point X = xyz_in / len0 (each coordinate converted, then
+ *   divided), in view 0's frame, X0 = R X1 + th.  R is taken as given and only ever multiplied from the left by exact rotations: it
+ *   is NOT re-orthonormalised, and an fp32 pose's R^T R - I (5e-8) stays in pose_out, as in round 16.  Row i < n is USED iff its four coordinates and X are finite, flag_i = 0, inlier_i
+ *   != 0 where given, and X_2 > 0 and Y_2 > 0 with Y = R^T (X - th) (below).  A pair is NOT USABLE (status 2) iff pose or the
+ *   intrinsics hold a value that is not finite, t = (0, 0, 0) or fewer than min_rows rows are used: pose_out = pose, every other
+ *   output NaN but stats[3] = the used rows (0 where the pose is at fault), stats[4] = stats[5] = 0 and stats[11] = 2.
+ *   THE RESIDUAL of a used row at (R, th, X):  d = X - th;  Y_j = (R_0j d_0 + R_1j d_1) + R_2j d_2;  r = ((fx0 X_0) / X_2 + cx0 - x0,
+ *   (fy0 X_1) / X_2 + cy0 - y0, (fx1 Y_0) / Y_2 + cx1 - x1, (fy1 Y_1) / Y_2 + cy1 - y1);  e2 = ((r_0 r_0 + r_1 r_1) + r_2 r_2) + r_3 r_3;
+ *   u = 1 + e2 / (scale_px scale_px);  cost = (e2 / 2) / u;  w = 1 / (u u): round 16's cost and weight.
+ *   THE JACOBIANS.  A (2 x 3) = [fx0 / X_2, 0, -((fx0 X_0) / X_2) / X_2; 0, fy0 / X_2, -((fy0 X_1) / X_2) / X_2], P likewise from
+ *   camera 1 and Y;  M_ac = (P_a0 R_c0 + P_a1 R_c1) + P_a2 R_c2 (= P R^T);  J_x = [A; M] (4 x 3).  J_p (4 x 6) is 0 in its first two
+ *   rows; rows 2 and 3 are [M [d]x, -M]: (M_a1 d_2 - M_a2 d_1, M_a2 d_0 - M_a0 d_2, M_a0 d_1 - M_a1 d_0, -M_a0, -M_a1, -M_a2): the
+ *   derivative by round 16's step R <- exp([om]x) R, th <- th + dt, BEFORE th is renormalised - the points are divided by the same
+ *   length below, and the residual does not see a common scale.
+ *   THE ROW'S BLOCKS, every sum over the residual's rows in ascending order, left to right, w times the column first ((w J_aj) J_ak):
+ *   V = w J_x^T J_x (3 x 3, upper triangle mirrored), V_cc += lambda V_cc;  W = w J_p^T J_x (6 x 3; rows 2 and 3 alone);
+ *   U = w J_p^T J_p (upper triangle);  gx = w J_x^T r;  gp = w J_p^T r.  Vi = V^-1, column k = round 16's Cholesky solve of
+ *   V with the right side -e_k, on a fresh copy of V each;  T = W Vi: T_jc = (W_j0 Vi_0c + W_j1 Vi_1c) + W_j2 Vi_2c.
+ *   SWEEP A: thread t walks the used rows t, t + 256, .. in ascending order and adds, where the three solves succeed,
+ *   U_jk - ((T_j0 W_k0 + T_j1 W_k1) + T_j2 W_k2) to the 21 sums of S (j <= k, by rows) and gp_j - ((T_j0 gx_0 + T_j1 gx_1) +
+ *   T_j2 gx_2) to the 6 of g; and for every used row the cost, w and 1: round 16's 30 sums, reduced as there (wave butterfly 32 .. 1,
+ *   then (w0 + w1) + (w2 + w3)).  The KEPT COST is this sweep's cost sum.
+ *   THE SOLVE (thread 0): p = ((((S_00 + S_11) + S_22) + S_33) + S_44) + S_55) / 6;  S_jj += lambda S_jj;  the translation block +=
+ *   p (th_i th_j);  delta = -S^-1 g by round 16's Cholesky;  R' = exp([delta_012]x) R (Rodrigues, the device library's sin and
+ *   cos; the identity below 1e-12), tn = th + delta_345, len = |tn|, th' = tn / len.  A failed solve or a step that is not finite:
+ *   status 1, the state is kept and the iteration ends.
+ *   SWEEP B: every thread forms V, W, gx and Vi of its rows again at the kept state;  v_c = gx_c + (((((W_0c delta_0 + W_1c delta_1)
+ *   + W_2c delta_2) + W_3c delta_3) + W_4c delta_4) + W_5c delta_5);  dX_a = -((Vi_a0 v_0 + Vi_a1 v_1) + Vi_a2 v_2), 0 where the
+ *   solves failed;  X' = (X + dX) / len, written to the tentative half of work;  the TRIAL COST is the sum, as in sweep A, of
+ *   the cost of X' under (R', th') - or +inf where an X' is not finite or X'_2 > 0 and Y'_2 > 0 do not both hold.
+ *   THE CONTROL.  lambda = 1e-3.  Sweep A; then, while fewer than iters solves were made: solve, sweep B;  trial < kept: ACCEPT
+ *   (the halves of work and the state change places, lambda = max(lambda / 3, 1e-12); stop if kept - trial <= ftol kept);
+ *   otherwise REJECT (lambda = 4 lambda; stop if lambda > 1e8);  sweep A at the kept state with the new lambda.
+ *   THE COVARIANCE.  A last sweep A with lambda = 0 gives S0 and stats[1 .. 3];  p = tr S0 / 6 as above, u = (0, 0, 0, th);
+ *   Cinv = S0 with its translation block += p (th_i th_j); column k of its inverse by the Cholesky solve with the right side -e_k,
+ *   on a fresh copy each;  C_jk = inverse_jk - (u_j u_k) / p: the covariance of (om, dt) in the gauge |th| = 1 for unit pixel
+ *   variance.  A failed solve here: cov, cov_x and stats[8], [9] are NaN and the status is 1.  A last sweep, per used row with V, W,
+ *   Vi and T at lambda = 0:  CT_jb = sum over k = 0 .. 5, left to right, of C_jk T_kb;  Cov_ab = Vi_ab + (sum over j = 0 .. 5, left to
+ *   right, of T_ja CT_jb) for a <= b - NaN where the solves failed.
+ *   THE OUTPUTS.  pose_out = [R | len0 th];  xyz = len0 X;  geom = (len0 X_2, len0 Y_2, sqrt(e2), w);  cov_x = (len0 len0) (Cov_00,
+ *   Cov_01, Cov_02, Cov_11, Cov_12, Cov_22);  cov = C;  rows that are not used, and rows at and beyond n: NaN.  stats: [0] the cost
+ *   of the first sweep A, [1] the last one's cost, [2] its sum of w, [3] the used rows, [4] steps accepted, [5] rejected, [6] the
+ *   last lambda, [7] sigma = sqrt((2 cost) / (rows - 5)), NaN at rows <= 5, [8] sigma sqrt((C_00 + C_11) + C_22) 57.29577951308232,
+ *   [9] sigma sqrt((C_33 + C_44) + C_55) 57.29577951308232, [10] round 16's angle in degrees from pose's rotation to R, [11] the
+ *   status: 0 ok, 1 a solve failed, 2 not usable.                                                                                  */
+#define CPN_BUNDLE_STATS 12
+int cpn_bundle_adjust(const float* xy, const int* count, const float* intrinsics, const float* pose, const float* xyz_in,
+                      const uint8_t* flag, const uint8_t* inlier, int B, int N, int iters, double scale_px, double ftol, int min_rows,
+                      double* work, float* pose_out, float* xyz, float* geom, float* cov_x, double* cov, double* stats, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
